@@ -1,6 +1,6 @@
 """bench.py -- headline measurement of the MI355X hot path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Metric (BASELINE.json): MSDeformAttn fwd+bwd Gpoints/s at T=5, L=4, Q=300, H=8, K=4.
@@ -14,18 +14,28 @@ distinct input sets, so neither the 256 MiB Infinity Cache nor the L2s hold a
 step's inputs from the previous use ("cold" numbers).  The K steps are launched
 as hipGraph replays (a step is three stream operations of a few microseconds;
 launching them from Python one by one would time the interpreter), bracketed by
-barrier + synchronize; rank 0 prints one JSON line.
+barrier + synchronize; exactly K steps are timed, ms_per_step = region / K; rank 0
+prints one JSON line.
+
+--dump-outputs DIR: after the timed region rank 0 writes what the last timed step
+returned (output, grad_value, grad_sampling_loc, grad_attn_weight) as float32
+DIR/<name>.npy, ~30 MB; the input sets are seeded, so two builds run with the same
+arguments can be compared output for output.
 
 N > 1: clips shard across ranks with no data-path collective (the op has no
 exchange step) -- weak scaling, value = all ranks' points / max
 time.  The gradient all-reduce of the model-level step lives with the model path.
 
-Besides the contract keys the line carries:
+A plain run stops there.  --full (minutes) adds, after the headline:
+  repeats       --repeats more timed regions of K steps: median / min / p10 / p90
+  model_step    the SeqFormer-R50 training step under DDP (clips/s), other_configs
   roofline      forward kernel (the kernel the north star sets the 60 % target on),
                 algorithmic bytes / avg launch time measured here with events
   roofline_bwd  the same for the backward kernel (+ its zero-fill)
+  op_cases, roofline_*  the other op shapes and kernel families
   cpu_baseline  the oracle (oracle/, "port") timed on the host cores on the same
                 workload, plus the grid_sample fallback technique of the reference
+--no-cpu / --no-model / --no-cases / --no-spans / --no-warm drop single legs of --full.
 """
 from __future__ import annotations
 
@@ -921,6 +931,14 @@ def headline_line(a, n_gpus, world_readback, ms_per_step, S, nsets, input_bytes,
     }
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` (name -> tensor) as float32 `dirname/<name>.npy`."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def stub_main(a, world, rank):
     """The multi-rank skeleton of main() on CPU tensors and gloo (see StubOp)."""
     import torch.distributed as dist
@@ -941,6 +959,8 @@ def stub_main(a, world, rank):
         step()
     elapsed = timed_region(step, a.steps, world, device)
     readback = dist.get_world_size() if world > 1 else 1
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"output": s["out"], "grad_value": s["gv"]})
     if rank == 0:
         line = headline_line(a, world, readback, elapsed * 1e3 / a.steps, S, 1, s["value"].numel() * 4, a.backend)
         line["data"] = "stub op on CPU (launcher test only; not a measurement)"
@@ -988,9 +1008,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL (the product); gloo: launcher test")
     ap.add_argument("--stub-op", action="store_true", help="launcher test on CPU: torch copies instead of the HIP op")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps: ms_per_step = their region / steps")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=21, help="timed regions of --steps steps each; ms_per_step is their median")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output and gradients as float32 DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated regions, model legs, rooflines, other shapes, CPU baseline")
+    ap.add_argument("--repeats", type=int, default=21,
+                    help="--full: further timed regions of --steps steps each, for the median / min / p10 / p90 spread")
     ap.add_argument("--res", default="360p", choices=list(SHAPES))
     ap.add_argument("--lq", type=int, default=300)
     ap.add_argument("--batch", type=int, default=5)
@@ -1006,6 +1031,8 @@ def main():
     ap.add_argument("--graph-leg", default=None, choices=list(GRAPH_LEGS),
                     help="child mode: one bf16 training leg with its trunk replayed from hipGraphs -> a JSON object (graph_leg_child)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.graph_leg:
         return graph_leg_child(a.graph_leg, a.model_steps)
@@ -1024,10 +1051,11 @@ def main():
         raise SystemExit(f"bench.py: {world} ranks but only {torch.cuda.device_count()} GPUs visible")
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
-    from vnext_amd.train import enable_channels_last
-    channels_last = enable_channels_last()      # before the process's first convolution (the model legs train in channels-last)
-    from vnext_amd import tuning as _tuning
-    conv_search = _tuning.enable_conv_search()  # (likewise: MIOpen reads MIOPEN_USER_DB_PATH at its first convolution)
+    if a.full:
+        from vnext_amd.train import enable_channels_last
+        channels_last = enable_channels_last()      # before the process's first convolution (the model legs train in channels-last)
+        from vnext_amd import tuning as _tuning
+        conv_search = _tuning.enable_conv_search()  # (likewise: MIOpen reads MIOPEN_USER_DB_PATH at its first convolution)
     affinity = None
     if world > 1:
         import torch.distributed as dist
@@ -1060,22 +1088,34 @@ def main():
     prewarm(graph, 0.15)     # clocks up before the W warm-up steps (untimed either way)
     for _ in range(math.ceil(a.warmup / chunk)):
         graph.replay()
-    # the region of EXACTLY K steps (barrier + synchronize on both sides, maximum over ranks) is timed `repeats` times;
-    # `ms_per_step` is the median region / K: at the driver's --steps 20 one region is a single 0.6-ms graph replay, too
-    # thin a sample for the number the bench is read for; p10 / p90 / min ride along
-    region_s = sorted(timed_region(graph.replay, a.steps // chunk, world, device) for _ in range(a.repeats))
-    elapsed = region_s[len(region_s) // 2]
+    # the region of EXACTLY K steps (barrier + synchronize on both sides, maximum over ranks): ms_per_step = region / K
+    elapsed = timed_region(graph.replay, a.steps // chunk, world, device)
     ms_per_step = elapsed * 1e3 / a.steps
+    if rank == 0 and a.dump_outputs:     # the last timed step is step chunk - 1 of the graph's last replay
+        last = sets[(chunk - 1) % nsets]
+        dump_outputs(a.dump_outputs, {"output": last["out"], "grad_value": last["gv"], "grad_sampling_loc": last["gl"],
+                                      "grad_attn_weight": last["ga"]})
     line = headline_line(a, n_gpus, dist.get_world_size() if world > 1 else 1, ms_per_step, S, nsets, input_bytes,
                          "nccl (RCCL)")
+    line["timing"] = ("one timed region of %d steps (a hipGraph of %d fwd+bwd steps replayed %d x), bracketed by barrier + "
+                      "synchronize, maximum over ranks; ms_per_step = region / steps" % (a.steps, chunk, a.steps // chunk))
+    line["rank_cpu_affinity"] = affinity      # rank 0's share of the host cores (None at one GPU: nothing pinned)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: the same region timed `repeats` more times -- at --steps 20 one region is a single 0.6-ms graph replay,
+    # too thin a sample to read much into; the median and min / p10 / p90 of the repeats ride along
+    region_s = sorted(timed_region(graph.replay, a.steps // chunk, world, device) for _ in range(a.repeats))
     line["repeats"] = a.repeats
     line["timed_region_s"] = sum(region_s)
+    line["ms_per_step_median_of_repeats"] = region_s[len(region_s) // 2] * 1e3 / a.steps
     line["ms_per_step_min_p10_p90"] = [region_s[0] * 1e3 / a.steps, region_s[int(0.1 * (len(region_s) - 1) + 0.5)] * 1e3 / a.steps,
                                        region_s[int(0.9 * (len(region_s) - 1) + 0.5)] * 1e3 / a.steps]
-    line["timing"] = ("%d timed regions of %d steps each (a hipGraph of %d fwd+bwd steps replayed %d x), every region bracketed by "
-                      "barrier + synchronize, maximum over ranks; ms_per_step = median region / steps" %
-                      (a.repeats, a.steps, chunk, a.steps // chunk))
-    line["rank_cpu_affinity"] = affinity      # rank 0's share of the host cores (None at one GPU: nothing pinned)
     line["channels_last_trunk"] = channels_last
     line["conv_search"] = conv_search           # MIOpen's algorithms by measurement, from the recorded find-db (tuning/miopen_userdb)
 

@@ -73,3 +73,51 @@ def test_a_graph_leg_that_cannot_run_costs_the_bench_nothing_but_that_entry():
     out = bench.graph_leg("idol_720p_bf16", steps=1, timeout_s=300)
     assert set(out) == {"error"} and "child exited" in out["error"], out
     assert set(bench.GRAPH_LEGS) == {"seqformer_360p_bf16", "seqformer_720p_bf16", "idol_720p_bf16"}
+
+
+def test_dump_outputs_writes_float32_arrays_that_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's arrays as float32 DIR/<name>.npy, from seeded inputs -- two runs with the
+    same arguments write the same arrays (the launcher path with the CPU stub op; the GPU path: test below)."""
+    import numpy as np
+    got = []
+    for run in ("a", "b"):
+        line = run_bench("--backend", "gloo", "--stub-op", "--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+        assert line["steps"] == 4 and line["ms_per_step"] > 0
+        got.append({n: np.load(tmp_path / run / (n + ".npy")) for n in ("output", "grad_value")})
+    for n, arr in got[0].items():
+        assert arr.dtype == np.float32 and arr.size > 0, n
+        assert np.array_equal(arr, got[1][n]), n
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """`bench.py --steps K --warmup W` measures the headline and nothing else (the other legs are --full's), and
+    --dump-outputs writes the output and the three gradients of its last timed step, which the CPU oracle reproduces from
+    the same seeded input set."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import msda_oracle as O
+    line = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "Gpoints/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["value"] - line["config"]["points_per_step"] / (line["ms_per_step"] * 1e-3) / 1e9) < 1e-6
+    for key in ("repeats", "model_step", "roofline", "roofline_bwd", "op_cases", "cpu_baseline"):
+        assert key not in line, key
+    dumped = {n: np.load(tmp_path / (n + ".npy")) for n in ("output", "grad_value", "grad_sampling_loc", "grad_attn_weight")}
+    assert sum(a.nbytes for a in dumped.values()) <= 64 * 2**20
+    assert all(a.dtype == np.float32 for a in dumped.values())
+    # --steps 3: a graph of 3 steps replayed once; its last step uses input set 2, which rank 0 seeds with 2
+    s = bench.make_set("360p", 5, 300, bench.largest_divisor_leq(3, 100) - 1, torch.device("cuda", 0))
+    value, loc, attn = (s[k].double().cpu().numpy() for k in ("value", "loc", "attn"))
+    shapes, lsi = s["shapes"].cpu().numpy(), s["lsi"].cpu().numpy()
+    want = {"output": O.msda_forward(value, shapes, lsi, loc, attn)}
+    want["grad_value"], want["grad_sampling_loc"], want["grad_attn_weight"] = O.msda_backward(
+        value, shapes, lsi, loc, attn, s["grad_out"].double().cpu().numpy())
+    for n, w in want.items():
+        assert dumped[n].shape == w.shape and np.isfinite(dumped[n]).all(), n
+        off = np.abs(dumped[n] - w) > 1e-4 * max(1e-30, float(np.abs(w).max()))
+        # grad_sampling_loc jumps where a sample sits on a cell edge, and fp32 / fp64 may put a few of its 384 000
+        # coordinates on different sides of one; the other three are continuous in the locations
+        assert off.mean() <= (1e-4 if n == "grad_sampling_loc" else 0), f"{n}: {int(off.sum())} entries off"
