@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define VNX_ABI_VERSION 15
+#define VNX_ABI_VERSION 16
 
 /* element types */
 enum {
@@ -435,6 +435,41 @@ int vnx_time_weighted_sum_forward(int dtype, const void* x, const void* logits, 
                                   int queries, int channels, void* hip_stream);
 int vnx_time_weighted_sum_backward(int dtype, const void* grad_out, const void* x, const void* weights, void* grad_x,
                                    void* grad_logits, int clips, int frames, int queries, int channels, void* hip_stream);
+
+/*
+ * Shifted-window multi-head self-attention of a Swin Transformer block (ABI 16) -- what WindowAttention does between its
+ * qkv and proj Linears, with the block's pad / cyclic shift / window partition / reverse / crop around it
+ * (projects/SeqFormer/seqformer/backbone/swin.py:129-169, 233-293, 404-452), for ALL windows, heads and images of a block in
+ * one launch forward and one backward (+ one small reduction launch):
+ *   x_pad = F.pad(tokens to Hp = ceil(H / w) w, Wp = ceil(W / w) w); rolled by (-shift, -shift); windows of w x w;
+ *   out_window = softmax(scale q k^T + relative_position_bias + mask) v,  mask = -100.0 between the reference's 3 x 3 shift
+ *   regions of the rolled Hp x Wp grid (shift > 0 only); then window reverse, the inverse roll and the crop to H x W.
+ * qkv: fp32 [batch * height * width][row_stride], image-row order, a row = q | k | v (channels = heads * head_dim each) of
+ * the UNPADDED, UNSHIFTED token as the qkv GEMM left it, WITHOUT bias; qkv_bias [3 * channels] (may be null) is added here,
+ * and a padded token's q / k / v IS qkv_bias (the reference pads after norm1): padded tokens are keys and values of every
+ * window they fall in; padded query rows are dropped.  bias_table: relative_position_bias_table [(2 w - 1)^2][heads].
+ * scale: head_dim^-0.5 or qk_scale.  Limits (VNX_ERR_UNSUPPORTED, before any launch): head_dim 32, 1 <= window <= 12,
+ * 1 <= heads <= 48; height, width >= 1 and 0 <= shift < window.  qkv, qkv_bias, out, grad_out, grad_qkv 16-byte aligned.
+ * Forward: out [batch * height * width][channels] (real tokens, image-row order: the proj GEMM's input); lse [batch * height
+ * * width][heads] fp32, the log-sum-exp of each query row's scores (the backward recomputes the probabilities from it; the
+ * scores are never stored).
+ * Backward: grad_qkv [batch * height * width][row_stride], the 3 * channels columns of every row written (the gradients
+ * BEFORE the bias: the real tokens' share of qkv_bias's gradient is their column sum); grad_bias_table [(2 w - 1)^2][heads];
+ * grad_pad_bias [3 * channels] (may be null): the k and v gradients summed over the PADDED tokens, q third zero -- add it to
+ * the column sum for qkv_bias's gradient.  partial: caller-allocated scratch of vnx_window_attention_partial_bytes(batch,
+ * height, width, heads, window) bytes = batch * windows * heads * ((2 w - 1)^2 + 64) * 4, windows = ceil(height / w) *
+ * ceil(width / w).  No atomics: the table and pad-bias gradients are per-workgroup partials reduced in a fixed order,
+ * bit-identical run to run.  No allocation, no synchronisation: capturable in a hipGraph.
+ */
+size_t vnx_window_attention_partial_bytes(int batch, int height, int width, int heads, int window);
+int vnx_window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out,
+                                 void* lse, int batch, int height, int width, int heads, int head_dim, int row_stride,
+                                 int window, int shift, float scale, void* hip_stream);
+int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table,
+                                  const void* out, const void* lse, const void* grad_out, void* grad_qkv,
+                                  void* grad_bias_table, void* grad_pad_bias, void* partial, size_t partial_bytes,
+                                  int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
+                                  int shift, float scale, void* hip_stream);
 
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */

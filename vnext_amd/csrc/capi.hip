@@ -746,6 +746,28 @@ int vnx_msda_fused_backward(int value_dtype, int query_dtype, const void* value,
   return VNX_OK;
 }
 
+// ---- the Swin block's shifted-window attention (window_attn.hip) -------------------------------------------------
+size_t vnx_window_attention_partial_bytes(int batch, int height, int width, int heads, int window) {
+  return vnx::window_attention_partial_bytes(batch, height, width, heads, window);
+}
+
+int vnx_window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out,
+                                 void* lse, int batch, int height, int width, int heads, int head_dim, int row_stride,
+                                 int window, int shift, float scale, void* hip_stream) {
+  return vnx::window_attention_forward(dtype, qkv, qkv_bias, bias_table, out, lse, batch, height, width, heads, head_dim,
+                                       row_stride, window, shift, scale, hip_stream);
+}
+
+int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table,
+                                  const void* out, const void* lse, const void* grad_out, void* grad_qkv,
+                                  void* grad_bias_table, void* grad_pad_bias, void* partial, size_t partial_bytes,
+                                  int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
+                                  int shift, float scale, void* hip_stream) {
+  return vnx::window_attention_backward(dtype, qkv, qkv_bias, bias_table, out, lse, grad_out, grad_qkv, grad_bias_table,
+                                        grad_pad_bias, partial, partial_bytes, batch, height, width, heads, head_dim,
+                                        row_stride, window, shift, scale, hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

@@ -99,6 +99,16 @@ __device__ __forceinline__ double floor_acc(double x) { return floor(x); }
 // ---- host side ---------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// window_attn.hip (the Swin block's shifted-window attention; C entry points in capi.hip)
+size_t window_attention_partial_bytes(int batch, int height, int width, int heads, int window);
+int window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out, void* lse,
+                             int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
+                             int shift, float scale, void* hip_stream);
+int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, const void* out,
+                              const void* lse, const void* grad_out, void* grad_qkv, void* grad_bias_table,
+                              void* grad_pad_bias, void* partial, size_t partial_bytes, int batch, int height, int width,
+                              int heads, int head_dim, int row_stride, int window, int shift, float scale,
+                              void* hip_stream);
 
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim

@@ -33,7 +33,7 @@ from ..registry import META_ARCH_REGISTRY
 from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
 from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, select_pos_neg_masks
 from .idol_transformer import DeformableTransformer
-from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, scale_tensor, sine_position
+from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
 
@@ -121,7 +121,7 @@ class IDOL(nn.Module):
             dim_feedforward=m.DIM_FEEDFORWARD, dropout=m.DROPOUT, activation="relu", return_intermediate_dec=True,
             num_frames=self.num_frames, num_feature_levels=m.NUM_FEATURE_LEVELS, dec_n_points=m.DEC_N_POINTS,
             enc_n_points=m.ENC_N_POINTS)
-        detr = DeformableDETR(ResNet50Trunk().freeze(2), transformer, m.NUM_CLASSES, self.num_frames, m.NUM_OBJECT_QUERIES,
+        detr = DeformableDETR(build_backbone(cfg), transformer, m.NUM_CLASSES, self.num_frames, m.NUM_OBJECT_QUERIES,
                               m.NUM_FEATURE_LEVELS, hidden)
         self.detr = CondInstSegmIDOL(detr, hidden)
         weights = {"loss_ce": m.CLASS_WEIGHT, "loss_bbox": m.L1_WEIGHT, "loss_giou": m.GIOU_WEIGHT,

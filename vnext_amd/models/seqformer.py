@@ -237,6 +237,15 @@ class ResNet50Trunk(nn.Module):
         return outs[1:]
 
 
+def build_backbone(cfg):
+    """MODEL.BACKBONE.NAME "D2SwinTransformer": the Swin backbone (models/swin.py); otherwise the ResNet-50 trunk with
+    its stem and res2 frozen."""
+    from .swin import D2SwinTransformer, is_swin
+    if is_swin(cfg):
+        return D2SwinTransformer(cfg)
+    return ResNet50Trunk().freeze(2)
+
+
 def sine_position(mask, num_pos_feats=128, temperature=10000):
     """models/position_encoding.py:35-55 with normalize=True."""
     not_mask = ~mask
@@ -384,7 +393,7 @@ class SeqFormer(nn.Module):
             dim_feedforward=m.DIM_FEEDFORWARD, dropout=m.DROPOUT, activation="relu", return_intermediate_dec=True,
             num_frames=self.num_frames, num_feature_levels=m.NUM_FEATURE_LEVELS, dec_n_points=m.DEC_N_POINTS,
             enc_n_points=m.ENC_N_POINTS)
-        detr = DeformableDETR(ResNet50Trunk().freeze(2), transformer, m.NUM_CLASSES, self.num_frames, m.NUM_OBJECT_QUERIES,
+        detr = DeformableDETR(build_backbone(cfg), transformer, m.NUM_CLASSES, self.num_frames, m.NUM_OBJECT_QUERIES,
                               m.NUM_FEATURE_LEVELS, hidden)
         self.detr = CondInstSegm(detr, hidden)
         weights = {"loss_ce": m.CLASS_WEIGHT, "loss_bbox": m.L1_WEIGHT, "loss_giou": m.GIOU_WEIGHT,

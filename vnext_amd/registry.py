@@ -53,13 +53,27 @@ def _ns(**kw):
     return SimpleNamespace(**kw)
 
 
+def _backbone_ns():
+    """MODEL.BACKBONE: NAME "D2SwinTransformer" builds the Swin backbone (vnext_amd/models/swin.py); anything else (the
+    default, detectron2's "build_resnet_backbone") the ResNet-50 trunk."""
+    return _ns(NAME="build_resnet_backbone", FREEZE_AT=2)
+
+
+def _swin_ns():
+    """MODEL.SWIN: the keys and defaults of projects/SeqFormer/seqformer/config.py:67-83 (IDOL's config.py the same)."""
+    return _ns(PRETRAIN_IMG_SIZE=224, PATCH_SIZE=4, EMBED_DIM=96, DEPTHS=[2, 2, 6, 2], NUM_HEADS=[3, 6, 12, 24],
+               WINDOW_SIZE=7, MLP_RATIO=4.0, QKV_BIAS=True, QK_SCALE=None, DROP_RATE=0.0, ATTN_DROP_RATE=0.0,
+               DROP_PATH_RATE=0.3, APE=False, PATCH_NORM=True, OUT_FEATURES=["res2", "res3", "res4", "res5"],
+               USE_CHECKPOINT=False)
+
+
 def get_seqformer_cfg(**overrides):
     """The key names and defaults of projects/SeqFormer/seqformer/config.py:5-85 (+ the D2 keys the
     meta-arch reads), as attribute namespaces -- yacs is not installed here."""
     cfg = _ns(
         MODEL=_ns(META_ARCHITECTURE="SeqFormer", DEVICE="cuda",
                   PIXEL_MEAN=[123.675, 116.280, 103.530], PIXEL_STD=[58.395, 57.120, 57.375],
-                  MASK_ON=True,
+                  MASK_ON=True, BACKBONE=_backbone_ns(), SWIN=_swin_ns(),
                   SeqFormer=_ns(NUM_CLASSES=40, MASK_WEIGHT=2.0, DICE_WEIGHT=5.0, GIOU_WEIGHT=2.0, L1_WEIGHT=5.0,
                                 CLASS_WEIGHT=2.0, DEEP_SUPERVISION=True, MASK_STRIDE=4, MATCH_STRIDE=4,
                                 FOCAL_ALPHA=0.25, SET_COST_CLASS=2, SET_COST_BOX=5, SET_COST_GIOU=2,
@@ -85,6 +99,7 @@ def get_idol_cfg(**overrides):
     cfg = _ns(
         MODEL=_ns(META_ARCHITECTURE="IDOL", DEVICE="cuda",
                   PIXEL_MEAN=[123.675, 116.280, 103.530], PIXEL_STD=[58.395, 57.120, 57.375], MASK_ON=True,
+                  BACKBONE=_backbone_ns(), SWIN=_swin_ns(),
                   IDOL=_ns(NUM_CLASSES=40, MASK_WEIGHT=2.0, DICE_WEIGHT=5.0, GIOU_WEIGHT=2.0, L1_WEIGHT=5.0,
                            CLASS_WEIGHT=2.0, REID_WEIGHT=2.0, DEEP_SUPERVISION=True, MASK_STRIDE=4, MATCH_STRIDE=4,
                            FOCAL_ALPHA=0.25, SET_COST_CLASS=2, SET_COST_BOX=5, SET_COST_GIOU=2,

@@ -260,6 +260,11 @@ def capture_training_graphs(model, clips, autocast_dtype=None) -> dict:
     -> {"enabled", "why"} for the bench line."""
     if not hasattr(model, "graph_training"):
         return {"enabled": False, "why": "%s has no graph_training switch" % type(model).__name__}
+    from .models.swin import SwinTransformer
+    if any(isinstance(m, SwinTransformer) for m in model.modules()):
+        # stochastic depth draws a fresh mask per step, which a replayed graph would freeze; not built
+        raise NotImplementedError("capture_training_graphs: the Swin backbone trains eagerly (graph capture of its "
+                                  "training trunk is not built)")
     if not torch.cuda.is_available() or not next(model.parameters()).is_cuda:
         return {"enabled": False, "why": "no GPU"}
     if dist.is_available() and dist.is_initialized() and isinstance(model, DistributedDataParallel):
