@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define VNX_ABI_VERSION 16
+#define VNX_ABI_VERSION 17
 
 /* element types */
 enum {
@@ -470,6 +470,36 @@ int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bi
                                   void* grad_bias_table, void* grad_pad_bias, void* partial, size_t partial_bytes,
                                   int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
                                   int shift, float scale, void* hip_stream);
+
+/*
+ * COCO compressed RLE strings of a batch of masks (ABI 17): what a YTVIS results file holds per (instance, frame), the
+ * strings of vnext_amd/utils/ytvis_json.py rle_encode (pycocotools rleEncode + rleToString) byte for byte.  Runs over
+ * the column-major mask, the first run counts zeros; from the fourth count on the string holds count[i] - count[i-2];
+ * 5-bit groups + 48, 0x20 = more follows, sign termination on 0x10 (at most 7 characters per count).
+ * mode VNX_MASK_RLE_LOGITS: input fp32 [masks][height][width] mask logits (4-byte aligned); output pixel (y, x) of the
+ *   out_height x out_width mask takes yi = min(floor(y * (image_height / out_height as fp32)), image_height - 1), xi
+ *   likewise (ATen "nearest" on the crop), and the bit is v > 0 for v = ATen's align_corners=False bilinear value of the
+ *   stride-times upsampled map at (yi, xi) -- sigmoid(v) > 0.5 apart from |v| within fp32 rounding of 0.
+ *   1 <= image_height <= height * stride, 1 <= image_width <= width * stride.
+ * mode VNX_MASK_RLE_BINARY: input uint8 / bool [masks][out_height][out_width], a pixel is set when its byte is non-zero;
+ *   height, width, stride and the image size are not read.
+ * Limits (before any launch): out_height * out_width < 2^31 and height * width < 2^31 (VNX_ERR_UNSUPPORTED); null
+ * pointers, masks < 0, non-positive sizes, a crop larger than the upsampled map, arena_bytes < 0
+ * (VNX_ERR_INVALID_ARGUMENT).  masks == 0 is a no-op.
+ * measure: lengths int64 [masks], each mask's string length.  write: offsets int64 [masks], where each string starts in
+ * arena (an exclusive scan of the lengths), arena of arena_bytes >= the sum of the lengths; the strings are written
+ * without terminators, no byte at or past arena_bytes is written.  One workgroup per mask, no atomics: the output is a
+ * function of the input alone.  No workspace, no allocation, no synchronisation: capturable in a hipGraph.
+ */
+enum {
+  VNX_MASK_RLE_LOGITS = 0,
+  VNX_MASK_RLE_BINARY = 1
+};
+int vnx_mask_rle_measure(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
+                         int image_width, int out_height, int out_width, void* lengths, void* hip_stream);
+int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
+                       int image_width, int out_height, int out_width, const void* offsets, void* arena,
+                       long long arena_bytes, void* hip_stream);
 
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */

@@ -16,9 +16,10 @@ DEV_LIB_PATH = os.path.join(_HERE, "lib", "libvnext_hip_dev.so")
 
 VNX_F32, VNX_F64, VNX_BF16, VNX_F16 = 0, 1, 2, 3
 VNX_OK = 0
-ABI_VERSION = 16
+ABI_VERSION = 17
 MSDA_LEVELS_PACKED = 1
 MSDA_REF_F32 = 0x100       # or-ed into ref_dim of vnx_msda_fused_*: fp32 reference points beside 16-bit offsets / logits
+MASK_RLE_LOGITS, MASK_RLE_BINARY = 0, 1   # vnx_mask_rle_*: input modes
 MSDA_FORK = 2              # vnx_msda_backward: grad_value kernel on the library's side stream (include/vnext_hip.h)
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
@@ -62,6 +63,8 @@ SIGNATURES = {
     "vnx_window_attention_partial_bytes": (_sz, [_i] * 5),
     "vnx_window_attention_forward": (_i, [_i] + [_vp] * 5 + [_i] * 8 + [ctypes.c_float, _vp]),
     "vnx_window_attention_backward": (_i, [_i] + [_vp] * 10 + [_sz] + [_i] * 8 + [ctypes.c_float, _vp]),
+    "vnx_mask_rle_measure": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp]),
+    "vnx_mask_rle_write": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp, _ll, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

@@ -768,6 +768,80 @@ int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bi
                                         row_stride, window, shift, scale, hip_stream);
 }
 
+// ---- COCO RLE strings of a batch of masks (mask_rle.hip) ---------------------------------------------------------
+static int mask_rle_check(const char* fn, int mode, const void* input, int masks, int height, int width, int stride,
+                          int image_height, int image_width, int out_height, int out_width) {
+  if (mode != VNX_MASK_RLE_LOGITS && mode != VNX_MASK_RLE_BINARY) {
+    vnx::set_error("%s: unknown mode %d", fn, mode);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (masks < 0 || out_height < 1 || out_width < 1) {
+    vnx::set_error("%s: bad sizes (masks %d, out %d x %d)", fn, masks, out_height, out_width);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (int64_t(out_height) * out_width >= (int64_t(1) << 31)) {
+    vnx::set_error("%s: out %d x %d has 2^31 pixels or more (int32 counts)", fn, out_height, out_width);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (mode == VNX_MASK_RLE_LOGITS) {
+    if (height < 1 || width < 1 || stride < 1 || image_height < 1 || image_width < 1 ||
+        int64_t(image_height) > int64_t(height) * stride || int64_t(image_width) > int64_t(width) * stride) {
+      vnx::set_error("%s: bad sizes (map %d x %d, stride %d, image %d x %d)", fn, height, width, stride, image_height,
+                     image_width);
+      return VNX_ERR_INVALID_ARGUMENT;
+    }
+    if (int64_t(height) * width >= (int64_t(1) << 31)) {
+      vnx::set_error("%s: map %d x %d has 2^31 elements or more", fn, height, width);
+      return VNX_ERR_UNSUPPORTED;
+    }
+    if (masks > 0 && (reinterpret_cast<uintptr_t>(input) & 3) != 0) {
+      vnx::set_error("%s: logits must be 4-byte aligned", fn);
+      return VNX_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (masks > 0 && !input) {
+    vnx::set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return VNX_OK;
+}
+
+int vnx_mask_rle_measure(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
+                         int image_width, int out_height, int out_width, void* lengths, void* hip_stream) {
+  const char* fn = "vnx_mask_rle_measure";
+  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width))
+    return st;
+  if (masks == 0) return VNX_OK;
+  if (!lengths) {
+    vnx::set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return vnx::mask_rle_launch(false, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width, (int64_t*)lengths, nullptr, nullptr, 0, (hipStream_t)hip_stream);
+}
+
+int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
+                       int image_width, int out_height, int out_width, const void* offsets, void* arena,
+                       long long arena_bytes, void* hip_stream) {
+  const char* fn = "vnx_mask_rle_write";
+  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width))
+    return st;
+  if (arena_bytes < 0) {
+    vnx::set_error("%s: arena_bytes %lld < 0", fn, arena_bytes);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (masks == 0) return VNX_OK;
+  if (!offsets || !arena) {
+    vnx::set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return vnx::mask_rle_launch(true, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width, nullptr, (const int64_t*)offsets, arena, int64_t(arena_bytes),
+                              (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

@@ -110,6 +110,11 @@ int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, 
                               int heads, int head_dim, int row_stride, int window, int shift, float scale,
                               void* hip_stream);
 
+// mask_rle.hip (COCO RLE strings of a batch of masks; C entry points and their argument checks in capi.hip)
+int mask_rle_launch(bool write, int mode, const void* input, int masks, int height, int width, int stride,
+                    int image_height, int image_width, int out_height, int out_width, int64_t* lengths,
+                    const int64_t* offsets, void* arena, int64_t arena_bytes, hipStream_t stream);
+
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim
 // 64-bit slots; each workgroup leaves {its start, its last wave's end} there in constant-rate

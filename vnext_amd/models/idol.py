@@ -36,6 +36,8 @@ from .idol_transformer import DeformableTransformer
 from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
+from ..ops.mask_rle import encode_logits
+from ..utils.ytvis_json import rle_encode, ytvis_records
 
 
 class CondInstSegmIDOL(nn.Module):
@@ -294,6 +296,13 @@ class IDOL(nn.Module):
             return self.losses(batched_inputs)
         return self.inference_video(batched_inputs)
 
+    @torch.no_grad()
+    def ytvis_results(self, batched_inputs):
+        """One video -> its YTVIS result records {"video_id", "score", "category_id", "segmentations"}: the records of
+        `instances_to_coco_json_video(batched_inputs, self(batched_inputs))`, with the masks encoded from the tracks'
+        logits on the device (`_track_masks`, vnext_amd/ops/mask_rle.py) instead of copied to the host as bool masks."""
+        return ytvis_records(batched_inputs, self.inference_video(batched_inputs, rle=True))
+
     # ---- inference ----------------------------------------------------------------------------
     @torch.no_grad()
     def select_candidates(self, logits, boxes):
@@ -384,7 +393,7 @@ class IDOL(nn.Module):
         return out
 
     @torch.no_grad()
-    def inference_video(self, batched_inputs):
+    def inference_video(self, batched_inputs, rle=False):
         """idol.py:236-281: chunks of BATCH_INFER_LEN frames through the network, then the tracker."""
         video = batched_inputs[0]["image"]
         per_frame = []
@@ -399,10 +408,41 @@ class IDOL(nn.Module):
         tracker = (DeviceTracker if on_device else IDOL_Tracker)(**args)
         ih, iw = video[0].shape[-2:]
         oh, ow = batched_inputs[0].get("height", ih), batched_inputs[0].get("width", iw)
-        return self.associate(per_frame, tracker, (oh, ow), (ih, iw), host_factory=lambda: IDOL_Tracker(**args))
+        return self.associate(per_frame, tracker, (oh, ow), (ih, iw), host_factory=lambda: IDOL_Tracker(**args), rle=rle)
+
+    @staticmethod
+    def _track_masks(tracks, n_frames, image_size, ori_size, rle=False):
+        """The final mask step of `associate`: each track's remembered stride-4 logits [1, H/4, W/4] (None where the
+        track is absent) -> per track, a list over frames of bool masks of `ori_size` on the host (None where absent) or,
+        with `rle`, of their COCO RLE dicts (the empty mask's RLE where absent, as the YTVIS writer puts it).  The RLE
+        form encodes the seen frames of ALL tracks in one device call; no full-resolution mask is formed."""
+        seen = [[i for i, m in enumerate(v["masks"]) if m is not None] for v in tracks]
+        if rle:
+            out = []
+            if tracks:
+                m = torch.cat([torch.stack([v["masks"][i] for i in idx]) for v, idx in zip(tracks, seen)])[:, 0]
+                strings = iter(encode_logits(m, 4, image_size, ori_size))
+                empty = rle_encode(np.zeros(tuple(ori_size), dtype=np.uint8))
+                for idx in seen:
+                    per = [empty] * n_frames
+                    for i in idx:
+                        per[i] = next(strings)
+                    out.append(per)
+            return out
+        masks_out = []
+        for v, idx in zip(tracks, seen):
+            m = torch.stack([v["masks"][i] for i in idx])                         # [k, 1, H/4, W/4]: one pass per track
+            h, w = m.shape[-2:]
+            m = F.interpolate(m, size=(h * 4, w * 4), mode="bilinear", align_corners=False).sigmoid()
+            m = (F.interpolate(m[:, :, :image_size[0], :image_size[1]], size=ori_size, mode="nearest") > 0.5)[:, 0].cpu()
+            per = [None] * n_frames
+            for j, i in enumerate(idx):
+                per[i] = m[j]
+            masks_out.append(per)
+        return masks_out
 
     @torch.no_grad()
-    def associate(self, per_frame, tracker, ori_size, image_size, host_factory=None):
+    def associate(self, per_frame, tracker, ori_size, image_size, host_factory=None, rle=False):
         """IDOL.inference (idol.py:313-471) on the pre-selected candidates of every frame.
 
         With a `DeviceTracker` the association of the whole video is enqueued without a host round trip:
@@ -413,7 +453,9 @@ class IDOL(nn.Module):
         The device tracker has fixed limits (slots alive at a time, detections per frame, memory_len): a video that
         outgrows its slots is associated AGAIN by `host_factory()` (the host-side tracker, no limits) instead of
         being lost -- a tracklet that found no slot is never remembered, so the device ids up to that point may
-        already differ from the reference's and are discarded as a whole."""
+        already differ from the reference's and are discarded as a whole.
+
+        `rle=True`: "pred_masks" holds each track's COCO RLE dicts instead of bool masks (`_track_masks`)."""
         n_frames = len(per_frame)
         on_device = isinstance(tracker, DeviceTracker)
         probs, frame_ids = [], []
@@ -436,7 +478,7 @@ class IDOL(nn.Module):
             if tracker.counters()[1]:
                 if host_factory is None:
                     raise RuntimeError("DeviceTracker: more simultaneous tracklets than slots; raise `capacity`")
-                return self.associate(per_frame, host_factory(), ori_size, image_size)
+                return self.associate(per_frame, host_factory(), ori_size, image_size, rle=rle)
         video = {}
         for t, (fr, ids) in enumerate(zip(per_frame, frame_ids)):
             for row, k in enumerate(ids.tolist()):
@@ -453,19 +495,11 @@ class IDOL(nn.Module):
             if t > 8:      # drop short noisy sequences (:386-393)
                 for k in [k for k, v in video.items() if v["masks"][-1] is None and v["masks"][-2] is None and v["valid"] < 3]:
                     video.pop(k)
-        cls, masks_out = [], []
+        cls = []
         for v in video.values():
             s = torch.stack([x for x in v["scores"] if x is not None])
             cls.append(s.mean(0) if self.temporal_score_type == "mean" else s.max(0)[0])
-            seen = [i for i, m in enumerate(v["masks"]) if m is not None]
-            m = torch.stack([v["masks"][i] for i in seen])                        # [k, 1, H/4, W/4]: one pass per track
-            h, w = m.shape[-2:]
-            m = F.interpolate(m, size=(h * 4, w * 4), mode="bilinear", align_corners=False).sigmoid()
-            m = (F.interpolate(m[:, :, :image_size[0], :image_size[1]], size=ori_size, mode="nearest") > 0.5)[:, 0].cpu()
-            per = [None] * n_frames
-            for j, i in enumerate(seen):
-                per[i] = m[j]
-            masks_out.append(per)
+        masks_out = self._track_masks(list(video.values()), n_frames, image_size, ori_size, rle)
         if not cls:
             return {"image_size": ori_size, "pred_scores": [], "pred_labels": [], "pred_masks": []}
         cls = torch.stack(cls)

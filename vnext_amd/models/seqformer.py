@@ -28,6 +28,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
+from ..ops.mask_rle import encode_logits
+from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh
 from ..registry import META_ARCH_REGISTRY
 from .seqformer_transformer import DeformableTransformer, inverse_sigmoid
@@ -646,26 +648,47 @@ class SeqFormer(nn.Module):
                                             params.float().repeat(T, 1)[None], [n] * T, 8)
         return prob[query], logits_m.view(T, n, *logits_m.shape[-2:]).transpose(0, 1)
 
-    def _report(self, prob, mask_logits, image_size, out_size):
+    def _report(self, prob, mask_logits, image_size, out_size, rle=False):
         """class probabilities [n, K] + mask logits [n, T, H/4, W/4] -> the output dict
-        (`whole_video_inference` :351-410 == `clip_matching_postprocess` :328-349)."""
+        (`whole_video_inference` :351-410 == `clip_matching_postprocess` :328-349).  `rle=True`: "pred_masks" holds
+        each reported pair's T COCO RLE dicts instead of bool masks; every query is encoded once, on the device
+        (vnext_amd/ops/mask_rle.py), and a query reported under several classes shares its strings."""
         if prob.shape[0] == 0:
             return {"image_size": out_size, "pred_scores": [], "pred_labels": [], "pred_masks": []}
-        h, w = mask_logits.shape[-2:]
-        masks = F.interpolate(mask_logits, size=(h * self.mask_stride, w * self.mask_stride), mode="bilinear",
-                              align_corners=False).sigmoid()
         if self.multi_cls:
             who, label = torch.where(prob > self.cls_thres)
             score = prob[who, label]
-            masks = masks[who]
         else:
             score, label = prob.max(-1)
-        masks = F.interpolate(masks[:, :, :image_size[0], :image_size[1]], size=out_size, mode="nearest") > 0.5
+            who = None
+        if rle:
+            n, T, h, w = mask_logits.shape
+            rows = list(range(n)) if who is None else who.tolist()
+            used = sorted(set(rows))
+            strings = encode_logits(mask_logits[used].reshape(len(used) * T, h, w), self.mask_stride, image_size,
+                                    out_size)
+            at = {q: j for j, q in enumerate(used)}
+            masks = [strings[at[q] * T:(at[q] + 1) * T] for q in rows]
+        else:
+            h, w = mask_logits.shape[-2:]
+            masks = F.interpolate(mask_logits, size=(h * self.mask_stride, w * self.mask_stride), mode="bilinear",
+                                  align_corners=False).sigmoid()
+            if who is not None:
+                masks = masks[who]
+            masks = F.interpolate(masks[:, :, :image_size[0], :image_size[1]], size=out_size, mode="nearest") > 0.5
+            masks = [m for m in masks.cpu()]
         return {"image_size": out_size, "pred_scores": score.tolist(), "pred_labels": label.tolist(),
-                "pred_masks": [m for m in masks.cpu()]}
+                "pred_masks": masks}
 
     @torch.no_grad()
-    def inference(self, batched_inputs):
+    def ytvis_results(self, batched_inputs):
+        """One video -> its YTVIS result records {"video_id", "score", "category_id", "segmentations"}: the records of
+        `instances_to_coco_json_video(batched_inputs, self(batched_inputs))`, with the masks encoded from the logits on
+        the device (`_report(rle=True)`) instead of copied to the host as bool masks."""
+        return ytvis_records(batched_inputs, self.inference(batched_inputs, rle=True))
+
+    @torch.no_grad()
+    def inference(self, batched_inputs, rle=False):
         """One video (seqformer.py:227-264).  Default: the whole video as one clip -- the 10 queries
         with the best class score, their masks on every frame, every (query, class) pair above
         APPLY_CLS_THRES reported (the reference runs the mask head for all 300 queries of all 6 decoder
@@ -678,7 +701,7 @@ class SeqFormer(nn.Module):
         out_size = (video.get("height", ih), video.get("width", iw))
         if not self.clip_matching:
             prob, mask_logits = self._top_instances(frames)
-            return self._report(prob, mask_logits, (ih, iw), out_size)
+            return self._report(prob, mask_logits, (ih, iw), out_size, rle)
         from types import SimpleNamespace
         from .clip_matching import Clips, Videos
         n_frames, merged = len(frames), None
@@ -696,4 +719,4 @@ class SeqFormer(nn.Module):
             if last:
                 break
         cls, mask_logits = merged.get_result()
-        return self._report(cls, mask_logits, (ih, iw), out_size)
+        return self._report(cls, mask_logits, (ih, iw), out_size, rle)

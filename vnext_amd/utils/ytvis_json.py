@@ -93,3 +93,12 @@ def instances_to_coco_json_video(inputs, outputs):
             segms.append(rle_encode(np.asarray(m.cpu() if hasattr(m, "cpu") else m)))
         results.append({"video_id": video_id, "score": score, "category_id": label, "segmentations": segms})
     return results
+
+
+def ytvis_records(inputs, outputs):
+    """The records of `instances_to_coco_json_video` from an output whose "pred_masks" already hold the RLE dicts
+    (the models' `ytvis_results`: masks encoded on the device, vnext_amd/ops/mask_rle.py)."""
+    assert len(inputs) == 1, "More than one inputs are loaded for inference!"
+    video_id = inputs[0]["video_id"]
+    return [{"video_id": video_id, "score": score, "category_id": label, "segmentations": list(segms)}
+            for score, label, segms in zip(outputs["pred_scores"], outputs["pred_labels"], outputs["pred_masks"])]
