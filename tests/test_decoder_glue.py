@@ -24,6 +24,17 @@ def test_cpu_takes_the_reference_expressions():
     assert torch.equal(G.time_weighted_sum(x, z), (x * torch.softmax(z, 1)).sum(1))
 
 
+def test_kernel_dtype_rule():
+    """the fp32 kernels take two fp32 tensors, or any two float tensors under autocast (custom_fwd casts them); outside
+    autocast a 16-bit tensor on either side sends the call to the torch expression, which promotes"""
+    f32, b16, f16 = torch.float32, torch.bfloat16, torch.float16
+    for a in (f32, b16, f16, torch.float64, torch.int32):
+        for b in (f32, b16, f16, torch.float64, torch.int32):
+            floats = a in (f32, b16, f16) and b in (f32, b16, f16)
+            assert G.kernel_dtypes_ok(a, b, False) == (a == f32 and b == f32), (a, b)
+            assert G.kernel_dtypes_ok(a, b, True) == floats, (a, b)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("comps", [2, 4])
 @pytest.mark.parametrize("shape", [(2, 5, 300), (1,), (3, 257)])
@@ -65,6 +76,34 @@ def test_refined_boxes_without_a_reference_gradient_skips_it():
     y.sum().backward()
     want = _boxes_reference(delta.detach().double(), ref.double())
     torch.testing.assert_close(delta.grad.double(), want * (1 - want), rtol=0, atol=1e-6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("comps", [2, 4])
+@pytest.mark.parametrize("rdt", [torch.bfloat16, torch.float16])
+def test_refined_boxes_mixed_dtypes_outside_autocast(comps, rdt):
+    """fp32 deltas beside 16-bit reference points, no autocast: nothing casts the references, so the call must not reach the
+    fp32 kernel (which would read the 16-bit buffer as fp32, past its end) -- it gives exactly what the torch expression
+    gives on the same tensors: fp32 boxes, the references' gradient in their own dtype"""
+    g = torch.Generator().manual_seed(comps + 10 * (rdt == torch.float16))
+    delta = (2 * torch.randn(10, 300, 4, generator=g)).to(DEV).requires_grad_(True)
+    # (inside (0, 1): at an fp16 reference of exactly 1.0 the fp16 expression's x / eps overflows and its gradient is NaN)
+    ref = (0.01 + 0.98 * torch.rand(10, 300, comps, generator=g)).to(DEV, rdt).requires_grad_(True)
+    assert not torch.is_autocast_enabled()
+    y = G.refined_boxes(delta, ref)
+    d2, r2 = delta.detach().clone().requires_grad_(True), ref.detach().clone().requires_grad_(True)
+    want = _boxes_reference(d2, r2)
+    assert y.dtype == want.dtype == torch.float32 and y.shape == delta.shape
+    torch.testing.assert_close(y, want, rtol=0, atol=0)
+    go = torch.randn(10, 300, 4, generator=g).to(DEV)
+    y.backward(go)
+    want.backward(go)
+    assert ref.grad.dtype == rdt and delta.grad.dtype == torch.float32
+    torch.testing.assert_close(delta.grad, d2.grad, rtol=0, atol=0)
+    torch.testing.assert_close(ref.grad, r2.grad, rtol=0, atol=0)
+    # and the boxes are those of the fp32 kernel on the references widened to fp32, up to the 16-bit logit's rounding
+    wide = G.refined_boxes(delta.detach(), ref.detach().float())
+    torch.testing.assert_close(y.detach(), wide, rtol=0, atol=3e-2)
 
 
 @pytest.mark.gpu

@@ -15,6 +15,14 @@ from oracle import msda_oracle as O
 from vnext_amd import _lib
 
 QC, ROWS = 304, 768      # VNX_GVD_QC, VNX_GVD_ROWS (vnx_common.h)
+CAP = 4 * QC * 4         # kGvdCap (msda_d32_gvdirect_body.h): taps of a pass the sorted list holds
+SLOTS = 3 * 256          # kIters x 256 groups (msda_d32_gvdirect_body.h): the slots the walk covers
+P360 = [(48, 80), (24, 40), (12, 20), (6, 10)]
+
+
+def pass_queries(Lq, P):
+    """queries a pass stages (the kernel's qc): min(VNX_GVD_QC, 4 * VNX_GVD_QC / P), never more than the call has"""
+    return min(Lq, QC, (4 * QC) // P)
 
 
 def level_table(shapes, Lq, P, batch_heads=2):
@@ -66,7 +74,7 @@ def model_grad_value(value_shape, shapes, lsi, loc, attn, grad_out, rng):
                             qi, ki = np.nonzero(ok)
                             for i, k in zip(qi, ki):
                                 taps.append((int(p[i, k] - r0), int(i), float(a[i, k] * wt[i, k])))
-                        assert len(taps) <= 4 * QC * 4       # the sorted list holds every tap of a pass
+                        assert len(taps) <= CAP       # the sorted list holds every tap of a pass
                         rng.shuffle(taps)      # arrival order of the rank atomics
                         cnt = np.zeros(rows, dtype=np.int64)
                         ranked = []
@@ -89,7 +97,7 @@ def model_grad_value(value_shape, shapes, lsi, loc, attn, grad_out, rng):
                         # the walk, once per channel half: slot = row * groups-per-row + part, 256 slots per round (2-lane
                         # groups); parts meet, part 0 stores -- the first half's sums wait for the second's
                         n_slots = rows << gshift
-                        assert n_slots <= 3 * 256      # what a group's held sums cover (kIters)
+                        assert n_slots <= SLOTS, (l, rows, gshift)      # what a group's held sums cover (kIters)
                         held = {}
                         for cp in (0, 1):
                             ch = slice(16 * cp, 16 * cp + 16)
@@ -142,6 +150,11 @@ def make_case(shapes, B, Lq, M, P, seed, concentrate=False):
     ([(33, 40), (4, 4)], 30, 4, False),                           # 1 320 pixels: three units of rows
     ([(4, 4)], 5, 4, False),
     ([(3, 5), (2, 2)], 330, 4, False),                            # two passes: the second adds onto the rows of the first
+    ([(12, 20), (6, 10)], 300, 8, False),                         # 8 points: two passes of 152 queries, rows on 4 / 8 groups
+    ([(25, 44)], 300, 16, False),                                 # 16 points: four passes of 76 queries, two units of 550 rows
+    ([(25, 44)], 300, 16, True),
+    ([(7, 9), (4, 5)], 40, 16, False),                            # one pass at 16 points
+    ([(5, 6)], 30, 64, False),                                    # 64 points: two passes of 19 queries
 ])
 def test_scheme_reproduces_the_oracle(shapes, Lq, P, concentrate):
     B, M = 1, 2
@@ -166,11 +179,51 @@ def test_baseline_level_tables():
     assert used <= bound and list(units)[0] == 23 and all(r <= 640 for r in rpu)      # the 720p pyramid: units of up to 640 rows
 
 
+def check_level_walks(shapes, Lq, P, units, rpu, gs):
+    """what the kernel relies on per level: the walk (kIters rounds of 256 slots) reaches every row of a unit, and a pass's
+    taps fit the sorted list"""
+    taps = 4 * P * pass_queries(Lq, P)
+    assert taps <= CAP, (shapes, Lq, P, taps)
+    for l, (r, g) in enumerate(zip(rpu, gs)):
+        assert int(r) << int(g) <= SLOTS, f"level {l} {shapes[l]}: {r} rows << gshift {g} = {int(r) << int(g)} slots > {SLOTS} " \
+                                          f"(Lq={Lq}, P={P}): rows past slot {SLOTS} never stored"
+
+
+# (shapes, Lq, P, batch x heads) -> per level (units, rows per unit, gshift)
+LEVEL_TABLES = [
+    # one 1 100-pixel level at 16 points: 4 x 16 x 76 taps per pass, not 4 x 16 x 300 -- one group per row
+    (([(25, 44)], 300, 16, 2), [(2, 550, 0)]),
+    (([(25, 44)], 300, 16, 80), [(2, 550, 0)]),
+    # 8 points at 360p, the decoder's B = 10 call: one unit per small level; 4 x 8 x 152 taps per pass
+    ((P360, 300, 8, 80), [(5, 768, 0), (2, 480, 0), (1, 240, 1), (1, 60, 3)]),
+    # ... B = 5: the small levels cut in two
+    ((P360, 300, 8, 40), [(5, 768, 0), (2, 480, 0), (2, 120, 1), (2, 30, 3)]),
+    # two levels, 8 points, one unit each
+    (([(20, 30), (10, 15)], 300, 8, 1000), [(1, 600, 0), (1, 150, 2)]),
+    # 4 points: the formula is the one before the pass was taken into account (see test_baseline_level_tables)
+    ((P360, 300, 4, 80), [(5, 768, 0), (2, 480, 0), (1, 240, 1), (1, 60, 3)]),
+    (([(25, 44)], 300, 4, 2), [(2, 550, 0)]),
+    # fewer queries than a pass holds: the taps of the call
+    (([(6, 10), (3, 5)], 20, 16, 2), [(2, 30, 1), (2, 8, 3)]),
+    (([(12, 20)], 50, 32, 1000), [(1, 240, 1)]),
+    (([(2, 3)], 1, 64, 1000), [(1, 6, 2)]),
+]
+
+
+@pytest.mark.parametrize("case,want", LEVEL_TABLES, ids=[f"{c[0]}-Lq{c[1]}-P{c[2]}-bm{c[3]}" for c, _ in LEVEL_TABLES])
+def test_level_tables_beyond_four_points(case, want):
+    shapes, Lq, P, bm = case
+    used, bound, units, rpu, gs = level_table(shapes, Lq, P, bm)
+    assert used <= bound
+    check_level_walks(shapes, Lq, P, units, rpu, gs)
+    assert [tuple(int(x) for x in t) for t in zip(units, rpu, gs)] == want
+
+
 @pytest.mark.parametrize("seed", range(4))
 def test_random_pyramids_never_pass_the_bound(seed):
     rnd = random.Random(seed)
     for _ in range(4000):
-        L = rnd.choice([1, 2, 4, 5])
+        L = rnd.randint(1, 5)
         h0, w0 = rnd.randint(1, 400), rnd.randint(1, 1500)
         shapes = [(max(1, -(-h0 // (1 << l)) + rnd.randint(0, 1)), max(1, -(-w0 // (1 << l)) + rnd.randint(0, 1))) for l in range(L)]
         if rnd.random() < 0.2:
@@ -178,11 +231,12 @@ def test_random_pyramids_never_pass_the_bound(seed):
         if rnd.random() < 0.1:
             shapes[rnd.randrange(L)] = (1, rnd.choice([1, 2, 7, 70000]))
         Lq = rnd.choice([1, 7, 100, 300, 900, 1023, 5000])
-        P = rnd.choice([1, 2, 4, 8])
-        bm = rnd.choice([1, 2, 8, 40, 80, 1000])
+        P = rnd.choice([1, 2, 3, 4, 5, 8, 16, 32, 64])
+        bm = rnd.choice([1, 2, 8, 40, 80, 1000]) if rnd.random() < 0.5 else rnd.randint(1, 1000)
         used, bound, units, rpu, gs = level_table(shapes, Lq, P, bm)
         assert used <= bound, (shapes, Lq, P, bm, used, bound)
         for (h, w), u, r, g in zip(shapes, units, rpu, gs):
             n = h * w
             assert 1 <= r <= ROWS and (u - 1) * r < n <= u * r, (shapes, Lq, P)     # every row has one owner, no unit is empty
             assert 0 <= g <= 3
+        check_level_walks(shapes, Lq, P, units, rpu, gs)

@@ -873,7 +873,7 @@ namespace vnx { int msda_gvdirect_units_bound(const MsdaDims& d); }
 extern "C" int vnx_debug_gvdirect_units(const int64_t* host_shapes, int levels, int num_query, int num_point, int batch_heads,
                                         int* units_used, int* units_bound, int* level_units, int* level_rows_per_unit,
                                         int* level_group_shift) {
-  if (!host_shapes || levels <= 0 || !units_used || !units_bound) return VNX_ERR_INVALID_ARGUMENT;
+  if (!host_shapes || levels <= 0 || num_point <= 0 || !units_used || !units_bound) return VNX_ERR_INVALID_ARGUMENT;
   int64_t S = 0;
   for (int l = 0; l < levels; ++l) S += host_shapes[2 * l] * host_shapes[2 * l + 1];
   const int rows = gvd_rows_max(int(S));

@@ -317,9 +317,12 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
     constexpr int kLpr = 4 / kGvdParts;                // lanes per row (part), two 16-B pieces each
     constexpr int kPieces = kGvdPartPieces / kLpr;
     constexpr int kGrp = kThreads / kLpr;              // groups per workgroup = slots per round
-    // slots = rows << gshift <= max(kGvdRows, 2 * taps of a pass / 16)  (gvd_level_split: gshift > 0 only while taps >= (16 << gshift) * n / 2)
+    // slots = rows << gshift <= kGvdRows: rows <= rows_max <= kGvdRows, and gvd_level_split takes the taps of ONE pass (at most
+    // kGvdCap), so gshift > 0 only where n << gshift <= kGvdCap / 8, and it lowers gshift until rpu << gshift <= VNX_GVD_ROWS.
+    // A row whose slot lies past the last round is never summed nor stored.
     constexpr int kSlotsMax = kGvdRows > kGvdCap / 8 ? kGvdRows : kGvdCap / 8;
     constexpr int kIters = (kSlotsMax + kGrp - 1) / kGrp;
+    static_assert(kIters * kGrp >= kSlotsMax && kSlotsMax >= VNX_GVD_ROWS, "the walk covers every slot gvd_level_split allows");
     float4_t held[kGvdParts == 2 ? kIters : 1][kPieces];
     auto walk = [&](auto cp_tag) {
       constexpr int cp = decltype(cp_tag)::value;

@@ -315,9 +315,16 @@ __host__ __device__ inline GvdSplit gvd_level_split(int n, int ut, int Lq, int P
   if (units > n) units = n;
   s.rpu = (n + units - 1) / units;
   s.units = (n + s.rpu - 1) / s.rpu;
-  // taps a row expects: 4 x points x (queries of a pass) / pixels of the level; from 16 up a row takes 2 groups, 32: 4, 64: 8
-  const int64_t taps = int64_t(4) * P * (Lq < VNX_GVD_QC ? Lq : VNX_GVD_QC);
+  // taps a row expects: 4 x points x (queries of a pass) / pixels of the level; from 16 up a row takes 2 groups, 32: 4, 64: 8.
+  // A pass stages min(VNX_GVD_QC, 4 * VNX_GVD_QC / P) queries (the kernel's qc), so taps <= 16 * VNX_GVD_QC = kGvdCap; a
+  // gshift g >= 1 means taps >= (8 << g) * n, so rpu << g <= n << g <= kGvdCap / 8 -- inside the walk's kIters rounds.  (Taken
+  // over the whole call, 4 x P x min(Lq, VNX_GVD_QC), it overcounted a pass from 5 points up: rows past slot 768 were lost.)
+  const int qc = VNX_GVD_QC < 4 * VNX_GVD_QC / P ? VNX_GVD_QC : 4 * VNX_GVD_QC / P;
+  const int64_t taps = int64_t(4) * P * (Lq < qc ? Lq : qc);
   while (s.gshift < 3 && taps >= (int64_t(16) << s.gshift) * n) ++s.gshift;
+  // the walk covers VNX_GVD_ROWS slots of a unit (rows << gshift): fewer groups on a row is always correct, a row past the
+  // last slot is never stored
+  while (s.gshift > 0 && (s.rpu << s.gshift) > VNX_GVD_ROWS) --s.gshift;
   return s;
 }
 

@@ -14,8 +14,9 @@ which ATen runs as three clamps, a subtraction, a division, a log, a slice + add
 
 a softmax, a broadcast multiply and a reduction forward; two multiplies, two reductions and the softmax backward.
 
-Both ARE those expressions (evaluated by torch) wherever the kernels do not apply: CPU, other dtypes.  Under torch.autocast
-the 16-bit tensors a Linear hands over are promoted on the way in and the results are fp32 (round 6).
+Both ARE those expressions (evaluated by torch) wherever the kernels do not apply: CPU, other dtypes, a 16-bit input outside
+autocast (kernel_dtypes_ok).  Under torch.autocast the 16-bit tensors a Linear hands over are promoted on the way in and the
+results are fp32 (round 6).
 """
 from __future__ import annotations
 
@@ -28,6 +29,13 @@ from .. import _lib
 EPS = 1e-5
 _FLOATS = (torch.float32, torch.bfloat16, torch.float16)      # 16-bit inputs only under autocast: promoted by custom_fwd, results fp32
 ENABLE = os.environ.get("VNX_FUSED_DECODER_GLUE", "1") != "0"      # A/B switch: off = the reference expressions, by torch
+
+
+def kernel_dtypes_ok(a, b, autocast):
+    """May the fp32 kernels take inputs of dtypes `a` and `b`?  Both fp32, or any two float dtypes under autocast, where
+    custom_fwd casts both to fp32 on the way in.  Outside autocast nothing casts them: a 16-bit tensor beside an fp32 one
+    would be read as fp32 (past the end of its buffer), so such calls take the torch expression, which promotes."""
+    return a in _FLOATS and b in _FLOATS and ((a == torch.float32 and b == torch.float32) or bool(autocast))
 
 
 def inverse_sigmoid(x, eps=EPS):
@@ -71,8 +79,7 @@ class _RefineBoxes(torch.autograd.Function):
 def refined_boxes(delta, reference_points):
     """The layer's refined boxes (see the module docstring), WITH their graph: they are also the layer's box prediction (the
     reference's detector evaluates the same expression a second time for its loss, deformable_detr.py:195-213)."""
-    if (ENABLE and delta.is_cuda and delta.dtype in _FLOATS and reference_points.dtype in _FLOATS
-            and (delta.dtype == torch.float32 or torch.is_autocast_enabled())
+    if (ENABLE and delta.is_cuda and kernel_dtypes_ok(delta.dtype, reference_points.dtype, torch.is_autocast_enabled())
             and delta.shape[-1] == 4 and reference_points.shape[-1] in (2, 4) and delta.shape[:-1] == reference_points.shape[:-1]):
         return _RefineBoxes.apply(delta, reference_points)
     if reference_points.shape[-1] == 4:
@@ -117,8 +124,7 @@ class _TimeWeightedSum(torch.autograd.Function):
 
 def time_weighted_sum(x, logits):
     """`(x * softmax(logits, 1)).sum(1)`: x [N, T, Q, C], logits [N, T, Q, 1] (or [N, T, Q]) -> [N, Q, C]."""
-    if (ENABLE and x.is_cuda and x.dtype in _FLOATS and logits.dtype in _FLOATS and x.dim() == 4
-            and ((x.dtype == torch.float32 and logits.dtype == torch.float32) or torch.is_autocast_enabled())
+    if (ENABLE and x.is_cuda and kernel_dtypes_ok(x.dtype, logits.dtype, torch.is_autocast_enabled()) and x.dim() == 4
             and 1 <= x.shape[1] <= 16 and x.shape[-1] % 4 == 0 and logits.numel() == x.numel() // x.shape[-1]
             and tuple(logits.shape[:3]) == tuple(x.shape[:3]) and x.numel() > 0):
         return _TimeWeightedSum.apply(x, logits)
