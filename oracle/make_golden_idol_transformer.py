@@ -3,7 +3,11 @@
 Imports the reference's projects/IDOL/idol/models/deformable_transformer.py under a synthetic
 package (its relative imports satisfied with the reference's own MSDeformAttn module file driven
 by the reference's pure-PyTorch op and the reference's inverse_sigmoid), runs two frames through
-it in fp64 and stores state dict, inputs and outputs in tests/golden/transformer_idol.npz.
+it in fp64 and stores state dict, inputs and outputs in tests/golden/transformer_idol.npz.  It then runs the same
+transformer once more in train() mode (dropout is 0) with gradients on, applies seeded upstream gradients to hs, memory,
+init_ref and the per-layer box predictions (formed as deformable_detr.py:199-210 forms them; inter_samples, a top-k the
+training path never computes, gets none) and stores those gradients and the resulting gradients of every parameter,
+src{i}, pos{i} and query_embed in tests/golden/transformer_idol_grad.npz.
 
     python -m oracle.make_golden_idol_transformer
 """
@@ -18,6 +22,7 @@ import numpy as np
 import torch
 
 from oracle.make_golden_modules import load_module_class
+from oracle.make_golden_transformer import detector_boxes
 from oracle.ref_extract import extract
 
 REF = "/root/reference/projects/IDOL/idol"
@@ -75,6 +80,32 @@ def main():
     path = os.path.join(OUT_DIR, "transformer_idol.npz")
     np.savez_compressed(path, **d)
     print("IDOL transformer fixture", os.path.getsize(path) // 1024, "KiB", tuple(hs.shape), tuple(inter_samples.shape))
+    write_gradients(tr, inv, srcs, poss, masks, query_embed)
+
+
+def write_gradients(tr, inv, srcs, poss, masks, query_embed):
+    """train() mode, gradients on: loss = sum_k <G_k, out_k> over the outputs the detector consumes."""
+    tr.train()
+    tr.zero_grad()
+    gen = torch.Generator().manual_seed(137)
+    srcs = [s.clone().requires_grad_(True) for s in srcs]
+    poss = [p.clone().requires_grad_(True) for p in poss]
+    query_embed = query_embed.clone().requires_grad_(True)
+    hs, memory, init_ref, inter_refs, _, _, _ = tr(srcs, masks, poss, query_embed)
+    outs = dict(hs=hs, memory=memory, init_ref=init_ref,
+                boxes=detector_boxes(tr.decoder.bbox_embed, hs, init_ref, inter_refs, inv))
+    gs = {k: torch.randn(v.shape, generator=gen) for k, v in outs.items()}
+    sum((gs[k] * v).sum() for k, v in outs.items()).backward()
+    d = {f"G.{k}": v.numpy() for k, v in gs.items()}
+    d["boxes"] = outs["boxes"].detach().numpy()
+    d.update({f"grad.{n}": p.grad.numpy() for n, p in tr.named_parameters() if p.grad is not None})
+    for i, (s, p) in enumerate(zip(srcs, poss)):
+        d[f"grad.src{i}"], d[f"grad.pos{i}"] = s.grad.numpy(), p.grad.numpy()
+    d["grad.query_embed"] = query_embed.grad.numpy()
+    path = os.path.join(OUT_DIR, "transformer_idol_grad.npz")
+    np.savez_compressed(path, **d)
+    print("IDOL transformer gradient fixture", os.path.getsize(path) // 1024, "KiB,",
+          sum(1 for k in d if k.startswith("grad.")), "gradients")
 
 
 if __name__ == "__main__":

@@ -5,7 +5,11 @@ synthetic package (its two relative imports -- `.ops.modules.MSDeformAttn` and
 `..util.misc.inverse_sigmoid` -- are satisfied with the reference's own module file driven by
 the reference's pure-PyTorch op, and the reference's own inverse_sigmoid cut out with ast), runs
 a small clip through it in fp64 and stores state dict, inputs and outputs in
-tests/golden/transformer_seqformer.npz.
+tests/golden/transformer_seqformer.npz.  It then runs the same transformer once more in train() mode (dropout is
+0) with gradients on, applies seeded upstream gradients to every output the detector consumes -- hs, hs_box, memory,
+init_ref and the per-layer box predictions, formed as the detector forms them (segmentation_condInst.py:134-150) -- and
+stores those gradients and the resulting gradients of every parameter, src{i}, pos{i} and query_embed in
+tests/golden/transformer_seqformer_grad.npz.
 
     python -m oracle.make_golden_transformer
 """
@@ -79,6 +83,46 @@ def main():
     path = os.path.join(OUT_DIR, "transformer_seqformer.npz")
     np.savez_compressed(path, **d)
     print("transformer fixture", os.path.getsize(path) // 1024, "KiB", tuple(hs.shape), tuple(hs_box.shape))
+    write_gradients(tr, inv, srcs, poss, masks, query_embed)
+
+
+def detector_boxes(bbox_embed, hs_box, init_ref, inter_refs, inverse_sigmoid):
+    """The per-layer box predictions as the reference detector forms them (segmentation_condInst.py:134-150)."""
+    boxes = []
+    for lvl in range(hs_box.shape[0]):
+        reference = inverse_sigmoid(init_ref if lvl == 0 else inter_refs[lvl - 1])
+        tmp = bbox_embed[lvl](hs_box[lvl])
+        if reference.shape[-1] == 4:
+            tmp = tmp + reference
+        else:
+            tmp = torch.cat([tmp[..., :2] + reference, tmp[..., 2:]], -1)
+        boxes.append(tmp.sigmoid())
+    return torch.stack(boxes)
+
+
+def write_gradients(tr, inv, srcs, poss, masks, query_embed):
+    """train() mode, gradients on: loss = sum_k <G_k, out_k> over the outputs the detector consumes."""
+    tr.train()
+    tr.zero_grad()
+    gen = torch.Generator().manual_seed(131)
+    srcs = [s.clone().requires_grad_(True) for s in srcs]
+    poss = [p.clone().requires_grad_(True) for p in poss]
+    query_embed = query_embed.clone().requires_grad_(True)
+    hs, hs_box, memory, init_ref, inter_refs, _, _, _ = tr(srcs, masks, poss, query_embed)
+    outs = dict(hs=hs, hs_box=hs_box, memory=memory, init_ref=init_ref,
+                boxes=detector_boxes(tr.decoder.bbox_embed, hs_box, init_ref, inter_refs, inv))
+    gs = {k: torch.randn(v.shape, generator=gen) for k, v in outs.items()}
+    sum((gs[k] * v).sum() for k, v in outs.items()).backward()
+    d = {f"G.{k}": v.numpy() for k, v in gs.items()}
+    d["boxes"] = outs["boxes"].detach().numpy()
+    d.update({f"grad.{n}": p.grad.numpy() for n, p in tr.named_parameters() if p.grad is not None})
+    for i, (s, p) in enumerate(zip(srcs, poss)):
+        d[f"grad.src{i}"], d[f"grad.pos{i}"] = s.grad.numpy(), p.grad.numpy()
+    d["grad.query_embed"] = query_embed.grad.numpy()
+    path = os.path.join(OUT_DIR, "transformer_seqformer_grad.npz")
+    np.savez_compressed(path, **d)
+    print("transformer gradient fixture", os.path.getsize(path) // 1024, "KiB,",
+          sum(1 for k in d if k.startswith("grad.")), "gradients")
 
 
 if __name__ == "__main__":

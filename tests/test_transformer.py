@@ -113,3 +113,48 @@ def test_idol_transformer_on_gpu(dtype, tol):
     if dtype == torch.float32:   # the top-30 order of near-equal weights may differ in fp32
         out = out[:4] + (torch.from_numpy(g["inter_samples"]),) + out[5:]
     check_idol(out, g, tol)
+
+
+# ---------------------------------------------------------------- gradients against the reference (train() mode)
+def _fixture_gradients(kind, g, gg, tr, L):
+    """fp64 on the CPU, MSDA through F.grid_sample: the fixture's upstream gradients on what the detector consumes, then every
+    gradient (each parameter, src{i}, pos{i}, query_embed) and the box predictions within 1e-9 of the reference's.  The set of
+    tensors that receive a gradient must be the reference's: that pins what is detached where.  (The 1e-12 floor is for
+    time_attention_weights.bias, whose gradient is zero in exact arithmetic -- the softmax over the frames does not see a
+    shift -- and ~1e-15 of rounding on both sides; every other gradient here is above 0.2.)"""
+    import model_grad_harness as H
+    tr.train()
+    srcs = [torch.from_numpy(g[f"src{i}"]).requires_grad_(True) for i in range(L)]
+    poss = [torch.from_numpy(g[f"pos{i}"]).requires_grad_(True) for i in range(L)]
+    masks = [torch.from_numpy(g[f"mask{i}"]) for i in range(L)]
+    query_embed = torch.from_numpy(g["query_embed"]).requires_grad_(True)
+    with H.aten_baseline(tr):
+        outs = H.outputs(kind, tr, srcs, masks, poss, query_embed)
+        assert {k[2:] for k in gg if k.startswith("G.")} == set(outs)
+        sum((torch.from_numpy(gg[f"G.{k}"]) * v).sum() for k, v in outs.items()).backward()
+    got = {f"grad.{n}": p.grad for n, p in tr.named_parameters() if p.grad is not None}
+    for i in range(L):
+        got[f"grad.src{i}"], got[f"grad.pos{i}"] = srcs[i].grad, poss[i].grad
+    got["grad.query_embed"] = query_embed.grad
+    got["boxes"] = outs["boxes"].detach()
+    want = {k: v for k, v in gg.items() if not k.startswith("G.")}
+    assert set(got) == set(want), f"missing {sorted(set(want) - set(got))}, extra {sorted(set(got) - set(want))}"
+    for k in sorted(want):
+        assert tuple(got[k].shape) == want[k].shape, k
+        np.testing.assert_allclose(got[k].numpy(), want[k], rtol=0, atol=1e-9 * float(np.abs(want[k]).max()) + 1e-12,
+                                   err_msg=k)
+
+
+def test_transformer_gradients_match_reference_cpu():
+    g = load()
+    gg = dict(np.load(os.path.join(GOLDEN_DIR, "transformer_seqformer_grad.npz")))
+    tr, L = build(g, "cpu", torch.float64)
+    _fixture_gradients("seqformer", g, gg, tr, L)
+
+
+def test_idol_transformer_gradients_match_reference_cpu():
+    g = load_idol()
+    gg = dict(np.load(os.path.join(GOLDEN_DIR, "transformer_idol_grad.npz")))
+    tr, L = build_idol(g, "cpu", torch.float64)
+    tr.decoder.return_samples = False       # the training path: no sample keeper
+    _fixture_gradients("idol", g, gg, tr, L)
