@@ -15,13 +15,38 @@ extern "C" {
 #endif
 
 /*
- * Kernel selection override (process-wide, development build only):
- *   0 = automatic (what the product library always does), 1 = force the generic kernels,
- *   2..69 forced wave / workgroup shapes of the tuned forward and grad_loc kernels, 200..216 grad_value units per
- *   level, 420 / 425 / 430 / 431 grad_value paths, 510 compact location copy, 700..702 / 720 the LDS-staged
- *   forwards of tools/experiments/msda_tile/ (DESIGN.md section 3.1c/d).
- *   100..199 and 400..499 are TIMING ABLATIONS that skip one of the two backward kernels: wrong results by
- *   construction.
+ * Kernel selection override (process-wide, development build only).  Every exported entry point reads it once per call and
+ * decodes it in ONE place -- decode_variant(), vnext_amd/csrc/vnx_common.h -- from which this list is written:
+ *   0          automatic: what the product library always does.  Any number not named below: the same
+ *   1          the generic kernels, forward and backward
+ *   c = 2..5   tuned forward and grad_loc kernel: 8, 4, 2, 1 queries per wave, 4 waves per workgroup
+ *   c = 12..15 the same with 1 wave per workgroup
+ *   20..39     configuration c = variant - 20 (0 = by size) with the forward's prefetch phase on; 40..59: variant - 40, off
+ *   60..67     configuration 13 with heads rotated over the XCDs by variant - 60; 68 the fixed head -> XCD map
+ *   69         automatic configuration, 16-bit rows of the forward as 8 lanes x 8 B
+ *              (below 100 any number but 0 also keeps the gather form of the grad_loc kernel where the slab form would run)
+ *   100 + c    TIMING ABLATION: grad_loc / grad_attn alone, configuration c as above
+ *   200 + u    grad_value units per level at least (u = 1..16)
+ *   300 + c    the one-kernel backward whose grad_value goes through global atomics, configuration c
+ *   400..429, 432..499  TIMING ABLATION: grad_value alone on the record- and tile-fed paths, of which
+ *     408 / 412  record-fed kernel with phase stamps in shader-clock / wall-clock ticks (vnx_debug_read_rec_stamps)
+ *     420 / 425  record-fed kernel in its LDS-slab form / its register-slab form without selection
+ *                (these four force the record-fed path)
+ *     441        whole backward, grad_value on the side stream as VNX_MSDA_FORK asks (self-decoding path)
+ *     442        TIMING ABLATION: grad_value alone on the self-decoding path too
+ *     444        whole backward, two launches where the paired kernel would run
+ *     445..447   whole backward, paired kernel with the grad_value groups first / the grad_loc groups first / alternating
+ *                (441 and 444..447 are whole backwards on the self-decoding path only: a call that takes the record- or
+ *                tile-fed path under them is the ablation of their range)
+ *   430 / 431  force the record-fed / the tile-fed grad_value path (whole backward)
+ *   510        tile-fed path: the grad_loc kernel leaves a compact copy of the locations / weights
+ *   700..702   the LDS-staged forward of tools/experiments/msda_tile/ (DESIGN.md section 3.1c/d); 701 / 702 with stamps of the
+ *              first / second item of every workgroup (vnx_debug_read_tile_stamps); 720 the second LDS-staged forward
+ *   701..798   ALSO, in the mask head's forward: variant - 700 runs per instance; 799 its strip kernel
+ *   730 / 731  force / forbid the slab forward (and with it the slab form of the grad_loc kernel)
+ *   733        the gather form of the grad_loc kernel where the slab form would run (the forward keeps its slab)
+ *   734        the slab form of the fused grad_loc kernel; 737 the large slab for 16-bit values
+ * The TIMING ABLATIONS skip one of the two backward kernels: wrong results by construction.
  */
 void vnx_set_kernel_variant(int variant);
 int vnx_get_kernel_variant(void);

@@ -89,7 +89,7 @@ def test_other_level_and_point_counts(L, P):
 def test_many_queries_with_other_level_and_point_counts(L, P, vdt):
     """from 1 024 queries up a call the tile-fed kernel is not built for (L * P != 16 or P != 4) must NOT take the self-decoding
     kernel (one pass per 304 queries, 16-bit rows rounded once per pass): the record-fed path accumulates in fp32 (capi.hip:
-    use_direct)"""
+    plan_backward)"""
     shapes = [(30, 44), (15, 22), (8, 11), (4, 6), (2, 3)][:L]
     case = uniform_case(shapes, 2, 1500, seed=100 * L + P, M=4, P=P)
     got = run(case, 0, vdt)

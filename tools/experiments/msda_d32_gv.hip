@@ -348,13 +348,10 @@ static int launch_gv(const int64_t* shapes, const int64_t* lsi, const void* loc,
 // grad_value for packed levels; a no-op on the device when the levels are not packed.
 int msda_backward_gv_d32(int vdt, int ldt, const int64_t* shapes, const int64_t* lsi,
                          const void* loc, const void* attn, const void* grad_out, void* grad_value,
-                         MsdaDims d, int variant, hipStream_t stream) {
-  // every level receives Lq*P samples; give each at least this many owners
-  int units_min = 4;
-  if (variant >= 200 && variant < 300) units_min = variant - 200;
-  if (units_min < 1) units_min = 1;
-  if (units_min > 16) units_min = 16;
-  const int ablate = (variant == 401) ? 1 : (variant == 402) ? 2 : 0;  // timing ablations only
+                         MsdaDims d, int gv_units, int ablate, hipStream_t stream) {
+  // every level receives Lq*P samples; give each at least this many owners (gv_units: KernelVariant's, 0 = 4);
+  // ablate 1 / 2: timing ablations only (the development build's 401 / 402 while this was the product path)
+  const int units_min = gv_units ? gv_units : 4;
 #define VNX_ARGS shapes, lsi, loc, attn, grad_out, grad_value, d, units_min, ablate, stream
   if (vdt == VNX_F32) return launch_gv<float, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_F32) return launch_gv<bf16_t, float>(VNX_ARGS);

@@ -23,7 +23,7 @@
 // global memory by the same lanes, so the result is exact for any input; the window only decides speed.
 // When the levels are not packed or do not add up to Lq the same kernel runs on linear blocks of 64
 // queries (still correct, no locality to exploit).  fp32, 32-channel heads, 4 levels x 4 points.
-#include "vnx_common.h"
+#include "msda_launchers.h"
 
 namespace vnx {
 

@@ -20,7 +20,7 @@
 // zero region: exact for any input, the window only decides speed.  Unpacked levels or Lq != S run on linear blocks
 // of queries.  fp32, 32-channel heads, 4 levels x 4 points.  Reference semantics: ms_deform_im2col_cuda.cuh:33-84,
 // 237-299; why an encoder call is local: ops/modules/ms_deform_attn.py:65-73, deformable_transformer.py:183-196.
-#include "vnx_common.h"
+#include "msda_launchers.h"
 
 #include <type_traits>
 

@@ -4,7 +4,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
-#include "vnx_common.h"
+#include "msda_launchers.h"
 #include "../../include/vnext_hip_debug.h"
 #ifdef VNX_DEV_VARIANTS
 #include "../../include/vnext_hip_dev.h"
@@ -14,7 +14,7 @@ namespace vnx {
 
 static thread_local char t_error[512] = "";
 #ifdef VNX_DEV_VARIANTS
-std::atomic<int> g_kernel_variant{0};   // development build: A/B knob (vnx_set_kernel_variant); every entry point reads it once
+std::atomic<int> g_kernel_variant{0};   // development build: A/B knob (vnx_set_kernel_variant); every entry point reads it once (vnx_common.h)
 #endif
 
 void set_error(const char* fmt, ...) {
@@ -34,55 +34,6 @@ int check_launch(const char* what) {
   }
   return VNX_OK;
 }
-
-int msda_forward_generic(int, int, const void*, const int64_t*, const int64_t*, const void*,
-                         const void*, void*, MsdaDims, hipStream_t);
-int msda_backward_generic(int, int, const void*, const int64_t*, const int64_t*, const void*,
-                          const void*, const void*, void*, void*, void*, MsdaDims,
-                          int only_if_not_packed, hipStream_t);
-int convert_f32_to(int, const void*, void*, int64_t, const int64_t*, const int64_t*, int, int,
-                   hipStream_t);
-int zero_if_not_packed(const int64_t*, const int64_t*, int, int, void*, size_t, hipStream_t);
-bool msda_d32_fwd_supported(int vdt, int ldt, const MsdaDims& d);
-#ifdef VNX_DEV_VARIANTS      // the LDS-staged forwards: tools/experiments/msda_tile/ (development build only)
-bool msda_tile_fwd_supported(int vdt, int ldt, const MsdaDims& d);
-int msda_forward_tile(const void*, const int64_t*, const int64_t*, const void*, const void*, void*, MsdaDims,
-                      const FusedArgs*, int debug, hipStream_t);
-bool msda_tile2_fwd_supported(int vdt, int ldt, const MsdaDims& d);
-int msda_forward_tile2(const void*, const int64_t*, const int64_t*, const void*, const void*, void*, MsdaDims, hipStream_t);
-#endif
-bool msda_d32_bwd_supported(int vdt, int ldt, const MsdaDims& d);
-int msda_forward_d32(int, int, const void*, const int64_t*, const int64_t*, const void*,
-                     const void*, void*, MsdaDims, int variant, hipStream_t);
-int msda_backward_d32(int, int, const void*, const int64_t*, const int64_t*, const void*,
-                      const void*, const void*, void*, void*, void*, MsdaDims, int variant,
-                      void* records, void* tile_summary, float* tile_copy, hipStream_t);
-int msda_bwd_tile_queries(const MsdaDims& d, int variant);
-bool msda_d32_gvtiles_supported(int vdt, int ldt, const MsdaDims& d);
-size_t msda_gvtiles_summary_bytes(const MsdaDims& d, int tile_queries);
-size_t msda_gvtiles_partial_bytes(const MsdaDims& d);
-int msda_backward_gvtiles_d32(int vdt, int ldt, const int64_t*, const int64_t*, const void* loc, const void* attn,
-                              const void* summaries, const void* grad_out, void* grad_value, MsdaDims,
-                              int tile_queries, float* partials, bool compact, hipStream_t);
-bool msda_d32_fused_supported(int vdt, int ldt, const MsdaDims& d);
-int msda_fused_d32(bool backward, int vdt, int ldt, const void* value, const int64_t* shapes, const int64_t* lsi,
-                   const void* raw_off, const void* raw_logit, const void* grad_out, void* out_or_grad_off,
-                   void* grad_logit, MsdaDims d, void* records, const void* reference, float* grad_reference,
-                   int ref_dim, int ref_div, void* grad_value_f32, void* tile_summary, float* tile_loc, float* tile_attn,
-                   hipStream_t stream, int ref_f32);
-bool msda_d32_gvrec_supported(int vdt, int ldt, const MsdaDims& d);
-size_t msda_gvrec_record_bytes(const MsdaDims& d);
-int msda_backward_gvrec_d32(int vdt, const int64_t*, const int64_t*, const void* records, const void*,
-                            void*, MsdaDims, int variant, float* split_image, hipStream_t);
-int msda_split_levels_convert(int vdt, const int64_t*, const int64_t*, const float* image, void* grad_value, MsdaDims, bool tiles,
-                              hipStream_t);
-bool msda_d32_gvdirect_supported(int vdt, int ldt, const MsdaDims& d);
-bool msda_backward_pair_supported(int vdt, int ldt, const MsdaDims& d);
-int msda_backward_pair_d32(int vdt, const void* value, const int64_t*, const int64_t*, const void* loc, const void* attn,
-                           const void* grad_out, void* grad_value, void* grad_loc, void* grad_attn, MsdaDims, int order,
-                           hipStream_t);
-int msda_backward_gvdirect_d32(int vdt, int ldt, const int64_t*, const int64_t*, const void* loc, const void* attn,
-                               const void* grad_out, void* grad_value, MsdaDims, bool compact, hipStream_t);
 
 static int check_common(const char* fn, int vdt, int ldt, const void* value,
                         const int64_t* shapes, const int64_t* lsi, const void* loc,
@@ -131,8 +82,8 @@ namespace vnx {
 #ifndef VNX_TILE_UNITS_MIN
 #define VNX_TILE_UNITS_MIN 1
 #endif
-int gv_units_min(const MsdaDims& d, bool tiles, int v) {
-  if (v >= 200 && v < 300) return v - 200 < 1 ? 1 : (v - 200 > 16 ? 16 : v - 200);
+int gv_units_min(const MsdaDims& d, bool tiles, int forced) {
+  if (forced) return forced;
   // Tried with per-unit selection: enough units that each expects about one selection window of
   // samples (10 per level at the encoder shape).  Slower on MI355X -- 353 vs 332 us per encoder-shape
   // backward -- because a unit's chunk count is set by its DISTINCT queries (128 staged rows per
@@ -254,15 +205,7 @@ int vnx_debug_wall_clock_khz(void) {
 
 // The LDS-staged forwards (north-star row n1; tools/experiments/msda_tile/) were measured over
 // two rounds against the per-query L2-gather kernel -- 64-65 vs 55 us at encoder-360p, within 2 % at 720p -- and are retired
-// from the product build: the development build keeps them reachable (variants 700..702 / 720) with their parity tests.
-#ifdef VNX_DEV_VARIANTS
-static bool use_tile_forward(int vdt, int ldt, const MsdaDims& d, int variant) {
-  return variant >= 700 && variant <= 702 && msda_tile_fwd_supported(vdt, ldt, d);
-}
-static bool use_tile2_forward(int vdt, int ldt, const MsdaDims& d, int variant) {
-  return variant == 720 && msda_tile2_fwd_supported(vdt, ldt, d);
-}
-#endif
+// from the product build: the development build keeps them reachable (KernelVariant::tile_fwd) with their parity tests.
 
 int vnx_msda_forward(int value_dtype, int loc_dtype, const void* value,
                      const int64_t* spatial_shapes, const int64_t* level_start_index,
@@ -279,95 +222,160 @@ int vnx_msda_forward(int value_dtype, int loc_dtype, const void* value,
     return VNX_ERR_INVALID_ARGUMENT;
   }
   hipStream_t stream = (hipStream_t)hip_stream;
-  const int variant = kernel_variant();
+  const KernelVariant kv = kernel_variant();
 #ifdef VNX_DEV_VARIANTS
-  if (use_tile2_forward(value_dtype, loc_dtype, d, variant))
+  if (kv.tile_fwd == 2 && msda_tile2_fwd_supported(value_dtype, loc_dtype, d))
     return msda_forward_tile2(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, output, d, stream);
-  if (use_tile_forward(value_dtype, loc_dtype, d, variant))
+  if (kv.tile_fwd == 1 && msda_tile_fwd_supported(value_dtype, loc_dtype, d))
     return msda_forward_tile(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, output, d, nullptr,
-                             variant - 700, stream);
+                             kv.tile_fwd_debug, stream);
 #endif
-  if (variant != 1 && msda_d32_fwd_supported(value_dtype, loc_dtype, d))
+  if (!kv.generic && msda_d32_fwd_supported(value_dtype, loc_dtype, d))
     return msda_forward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
-                            sampling_loc, attn_weight, output, d, variant, stream);
+                            sampling_loc, attn_weight, output, d, kv, stream);
   return msda_forward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
                               sampling_loc, attn_weight, output, d, stream);
 }
 
-static bool bwd_fast_path(int vdt, int ldt, const MsdaDims& d, int variant) {
-  return variant != 1 && !(variant >= 300 && variant < 400) &&
-         msda_d32_bwd_supported(vdt, ldt, d) && msda_d32_gvrec_supported(vdt, ldt, d);
-}
-
-// Workspace layout of the backward: [sample records or tile words (fast path, 256-B aligned size) | fp32
-// grad_value image (16-bit values whenever the general path may run)].
-static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
-
-// Which grad_value path a fast-path call takes: per-sample records + per-unit selection (msda_d32_gvrec.hip: calls
-// with few, scattered queries -- the decoders') or per-tile words (msda_d32_gvtiles.hip: from 1 024 queries up -- the
-// encoders').  Measured on MI355X, T = 5 encoder calls, model-like locations, cold: see DESIGN.md section 3.3b.
-// Variants 430 / 431 force records / tiles for A/B runs; the variants that name a record-fed kernel keep it.
-static bool use_tiles(int vdt, int ldt, const MsdaDims& d, int variant) {
-  if (variant == 430 || variant == 408 || variant == 412 || variant == 420 || variant == 425) return false;
-  if (d.P != 4 || d.L * d.P != 16 || !msda_d32_gvtiles_supported(vdt, ldt, d)) return false;
-  return variant == 431 || d.Lq >= 1024;
-}
-// Calls below 1 024 queries (the decoders'): grad_value by the self-decoding kernel (msda_d32_gvdirect.hip) -- no records, no
-// tags, no workspace, and no dependence on the grad_loc kernel, so the two run concurrently (side_lane below).  The
-// development build keeps the record-fed kernels reachable for A/B runs (variant 430 and the variants that name one).
+// ---- the backward's plan ------------------------------------------------------------------------------------------
+// Which kernels a call runs and where each finds its piece of the workspace, decided ONCE per call by plan_backward(): the
+// two size functions and the two backwards all ask it, so the size a caller is told and the pointers the kernels are handed
+// come from the same numbers.
+//   Generic  zero-filled fp32 image + hardware fp32 / fp64 atomics: the generic kernel (development build: or the tuned
+//            one-kernel backward with atomics)
+//   Pair     below 1 024 queries: both halves as ONE launch where the paired kernel is built for the call (msda_d32.hip:
+//            msda_bwd_pair_kernel; fp32, L*P == 16, the one-wave grad_loc configuration -- the decoders' calls): the grad_value
+//            units first, the grad_loc work in the remaining workgroups, sharing the GPU without a second queue
+//   Direct   below 1 024 queries: grad_value by the self-decoding kernel (msda_d32_gvdirect.hip) -- no records, no tags, no
+//            workspace, and no dependence on the grad_loc kernel, so the two may run concurrently (side_lane above)
+//   Tiles    from 1 024 queries up (the encoders'): the grad_loc kernel leaves one word per (level, tile of queries),
+//            grad_value from the op's inputs and those words (msda_d32_gvtiles.hip)
+//   Records  the grad_loc kernel leaves one 16-B geometry record per sample, grad_value by owner-computes units fed by
+//            those records with per-unit selection (msda_d32_gvrec.hip)
+// Every fast path does nothing on the device unless the levels are packed; unless the caller promised packed levels the
+// general path follows (unpacked_levels_tail), each kernel of which does nothing on the device when the levels ARE packed.
+// No host sync either way.  (The record-less predecessor of Records -- every unit re-deriving its level's geometry -- and
+// the side stream that overlapped it with the grad_loc kernel are archived under tools/experiments/msda_d32_gv.hip.)
 #ifndef VNX_PAIR_ORDER
 #define VNX_PAIR_ORDER -1     // role order of the paired backward kernel's workgroup groups (msda_d32.hip): -1 = the launcher's choice
 #endif
-static bool use_direct(int vdt, int ldt, const MsdaDims& d, int variant) {
-  if (variant == 430 || variant == 408 || variant == 412 || variant == 420 || variant == 425) return false;
-  if (use_tiles(vdt, ldt, d, variant)) return false;
-  // built for calls below 1 024 queries: beyond, every unit would re-stage all grad_out rows of its head once per pass of
-  // VNX_GVD_QC queries, and 16-bit rows would be rounded once per pass -- such calls (L * P != 16 or P != 4 at encoder sizes) keep
-  // the record-fed path, which accumulates in fp32
-  if (d.Lq >= 1024) return false;
-  return msda_d32_gvdirect_supported(vdt, ldt, d);
-}
-// RECORD-fed path with 16-bit values and enough queries for the query split of the coarse levels (gv_query_splits): the
-// pieces of such a level meet through fp32 atomics, which need an fp32 target -- the same [B, S, M, 32] fp32 image the
-// general path of unpacked levels uses (the two never run on the same call: one needs packed levels, the other unpacked
-// ones).  The tile-fed path (every call the models make with >= 1 024 queries) needs none since round 4: its pieces store
-// fp32 partial rows (msda_gvtiles_partial_bytes) and a finishing kernel writes grad_value in its own dtype.
-static bool split_image_needed(int vdt, int ldt, const MsdaDims& d, int variant) {
-  return (vdt == VNX_BF16 || vdt == VNX_F16) && d.P == 4 && d.Lq >= 1024 && !use_tiles(vdt, ldt, d, variant) &&
-         !use_direct(vdt, ldt, d, variant);
-}
-// Tile path: does the grad_loc kernel leave a copy of the locations / weights laid out for the grad_value kernel
-// ([batch][head][level][query][point], fp32, 12 B per sample)?  The fused backward always does (it has to materialise
-// them anyway: 196.7 -> 194.9 us at encoder-360p against the op's own layout).  The plain backward does not: the 12 B per
-// sample the grad_loc kernel then writes cost more than the grad_value kernel's tidier reads save (encoder-360p 186 vs
-// 175 us, 720p B = 2 337 vs 322 us, B = 5 664 vs 654 us -- although that kernel fetches 2 GB per 720p launch, PMC).
-// Variant 510 forces the copy for A/B runs.
-static bool tile_copy_wanted(const MsdaDims& d, int variant) {
-  (void)d;
-  return variant == 510;
-}
-static size_t tile_copy_bytes(const MsdaDims& d) { return align256(size_t(12) * size_t(d.B) * d.Lq * d.M * d.L * d.P); }
-// tile path: [tile words | location copy (variant 510 only) | partial rows of the query-split levels' pieces]
-static size_t tiles_partials_offset(const MsdaDims& d, int variant) {
-  return align256(msda_gvtiles_summary_bytes(d, msda_bwd_tile_queries(d, variant))) + (tile_copy_wanted(d, variant) ? tile_copy_bytes(d) : 0);
-}
-static size_t fast_path_scratch_bytes(int vdt, int ldt, const MsdaDims& d, int variant) {
-  if (use_tiles(vdt, ldt, d, variant)) return tiles_partials_offset(d, variant) + align256(msda_gvtiles_partial_bytes(d));
-  if (use_direct(vdt, ldt, d, variant)) return 0;
-  return align256(msda_gvrec_record_bytes(d));
+enum class BwdPath { Generic, Pair, Direct, Tiles, Records };
+// Workspace: [sample records (Records) or tile words (Tiles) | locations, weights | partial rows (Tiles) | fp32 image], every
+// region a multiple of 256 B; a region a call does not need has no bytes.
+struct MsdaBackwardPlan {
+  BwdPath path;
+  bool only_gl, only_gv;      // development build, timing ablations: one half of the backward alone
+  bool fork, unpacked_tail;   // Direct: grad_value on the side stream between two events; the general path follows the fast one
+  int tile_queries;           // Tiles: queries per tile word
+  bool copy;                  // the locations / weights region exists (fp32, [batch][head][level][query][point], 12 B per sample)
+  // the fp32 [B, S, M, D] image exists: the general path's accumulator for 16-bit values and / or (split_image) the target of
+  // the query pieces' atomics (Records, 16-bit values)
+  bool image, split_image;
+  size_t off_loc, off_attn, off_partials, off_image, total;      // bytes; records / tile words at 0
+};
+
+static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// fused: the fused prologue's backward (ldt VNX_F32: the decoded locations it leaves; flags VNX_MSDA_LEVELS_PACKED: it
+// requires them).  It has its own support check (check_fused), always takes the automatic configuration of the grad_loc
+// kernel, and has neither a generic form nor ablations.
+static MsdaBackwardPlan plan_backward(int vdt, int ldt, const MsdaDims& d, int flags, const KernelVariant& kv, bool fused) {
+  MsdaBackwardPlan p{};
+  const bool sixteen = (vdt == VNX_BF16 || vdt == VNX_F16);
+  const bool packed = (flags & VNX_MSDA_LEVELS_PACKED) != 0;
+  const size_t image_bytes = sixteen ? sizeof(float) * size_t(d.B) * size_t(d.S) * size_t(d.M) * size_t(d.D) : 0;
+  if (!fused && (kv.generic || kv.atomics_backward || !msda_d32_bwd_supported(vdt, ldt, d) ||
+                 !msda_d32_gvrec_supported(vdt, ldt, d))) {
+    p.path = BwdPath::Generic;
+    p.image = sixteen;
+    p.total = image_bytes;
+    return p;
+  }
+  // Per-sample records (calls with few, scattered queries) or per-tile words (from 1 024 queries up)?  Measured on MI355X,
+  // T = 5 encoder calls, model-like locations, cold: see DESIGN.md section 3.3b.  The development build forces records / tiles
+  // for A/B runs (KernelVariant::gv_path; the variants that name a record-fed kernel keep it).
+  // The self-decoding kernel is built for calls below 1 024 queries: beyond, every unit would re-stage all grad_out rows of
+  // its head once per pass of VNX_GVD_QC queries, and 16-bit rows would be rounded once per pass -- such calls (L * P != 16 or
+  // P != 4 at encoder sizes) keep the record-fed path, which accumulates in fp32.
+  const bool records_forced = kv.gv_path == GvPath::Records;
+  if (!records_forced && d.P == 4 && d.L * d.P == 16 && msda_d32_gvtiles_supported(vdt, ldt, d) &&
+      (kv.gv_path == GvPath::Tiles || d.Lq >= 1024))
+    p.path = BwdPath::Tiles;
+  else if (!records_forced && d.Lq < 1024 && msda_d32_gvdirect_supported(vdt, ldt, d))
+    p.path = BwdPath::Direct;
+  else
+    p.path = BwdPath::Records;
+
+  size_t at = 0;
+  if (p.path == BwdPath::Tiles) {
+    p.tile_queries = msda_bwd_tile_queries(d, fused ? FwdCfg{0, 0} : kv.gl_cfg);
+    at = align256(msda_gvtiles_summary_bytes(d, p.tile_queries));
+  } else if (p.path == BwdPath::Records) {
+    at = align256(msda_gvrec_record_bytes(d));
+  }
+  // Does the grad_loc kernel leave the locations / weights laid out for the grad_value kernel?  The fused backward always
+  // does, for the tile-fed and the self-decoding kernel (it has to materialise them anyway -- the two tensors the fused prologue
+  // otherwise never holds, 12 B per sample against the records' 16 + 4: 196.7 -> 194.9 us at encoder-360p against the op's own
+  // layout), as two regions.  The plain backward does not: the 12 B per sample the grad_loc kernel then writes cost more than
+  // the grad_value kernel's tidier reads save (encoder-360p 186 vs 175 us, 720p B = 2 337 vs 322 us, B = 5 664 vs 654 us --
+  // although that kernel fetches 2 GB per 720p launch, PMC); the development build forces the copy on the tile path for A/B
+  // runs (KernelVariant::tile_copy), as one region with the weights right behind the locations.
+  const size_t samples = size_t(d.B) * d.Lq * d.M * d.L * d.P;
+  p.copy = fused ? p.path != BwdPath::Records : (p.path == BwdPath::Tiles && kv.tile_copy);
+  if (p.copy) {
+    p.off_loc = at;
+    p.off_attn = at + (fused ? align256(samples * 8) : samples * 8);
+    at = fused ? p.off_attn + align256(samples * 4) : at + align256(samples * 12);
+  }
+  if (p.path == BwdPath::Tiles) {      // the partial rows of the query-split levels' pieces
+    p.off_partials = at;
+    at += align256(msda_gvtiles_partial_bytes(d));
+  }
+  // RECORD-fed path with 16-bit values and enough queries for the query split of the coarse levels (gv_query_splits): the
+  // pieces of such a level meet through fp32 atomics, which need an fp32 target -- the same [B, S, M, 32] fp32 image the
+  // general path of unpacked levels uses (the two never run on the same call: one needs packed levels, the other unpacked
+  // ones).  The tile-fed path (every call the models make with >= 1 024 queries) needs none since round 4: its pieces store
+  // fp32 partial rows (msda_gvtiles_partial_bytes) and a finishing kernel writes grad_value in its own dtype.
+  p.split_image = sixteen && d.P == 4 && d.Lq >= 1024 && p.path == BwdPath::Records;
+  // packed levels promised: the general path never runs, no fp32 image -- unless the query split needs it
+  p.image = sixteen && (!packed || p.split_image);
+  p.off_image = at;
+  p.total = at + (p.image ? image_bytes : 0);
+
+  // Development build: grad_loc / grad_attn alone, grad_value alone (timing), fork without the flag, the two launches where
+  // the paired kernel would run.
+  const bool direct = p.path == BwdPath::Direct;
+  p.only_gl = !fused && kv.only_gl;
+  p.only_gv = !fused && (direct ? kv.only_gv_direct : kv.only_gv);
+  const bool whole = !p.only_gl && !p.only_gv;
+  p.fork = direct && whole && ((flags & VNX_MSDA_FORK) || kv.fork);
+  p.unpacked_tail = !packed && whole;
+  if (direct && !fused && whole && !p.fork && !kv.no_pair && msda_backward_pair_supported(vdt, ldt, d) && (!sixteen || packed))
+    p.path = BwdPath::Pair;
+  return p;
 }
 
 size_t vnx_msda_backward_workspace_bytes(int value_dtype, int loc_dtype, int batch,
                                          int spatial_size, int num_heads, int channels,
                                          int num_levels, int num_query, int num_point, int flags) {
   const MsdaDims d{batch, spatial_size, num_heads, channels, num_levels, num_query, num_point};
-  const int variant = kernel_variant();
-  const bool sixteen = (value_dtype == VNX_BF16 || value_dtype == VNX_F16);
-  const size_t image = sixteen ? sizeof(float) * size_t(batch) * size_t(spatial_size) * size_t(num_heads) * size_t(channels) : 0;
-  if (!bwd_fast_path(value_dtype, loc_dtype, d, variant)) return image;
-  const size_t records = fast_path_scratch_bytes(value_dtype, loc_dtype, d, variant);
-  // packed levels promised: the general path never runs, no fp32 image -- unless the query split needs it
-  return records + (((flags & VNX_MSDA_LEVELS_PACKED) && !split_image_needed(value_dtype, loc_dtype, d, variant)) ? 0 : image);
+  return plan_backward(value_dtype, loc_dtype, d, flags, kernel_variant(), false).total;
+}
+
+// The general path behind a fast one: every kernel of it does nothing on the device when the levels ARE packed.  acc: the fp32
+// accumulator -- grad_value itself, or the workspace's image for 16-bit values, converted into grad_value at the end.
+static int unpacked_levels_tail(int vdt, int ldt, const void* value, const int64_t* shapes, const int64_t* lsi, const void* loc,
+                                const void* attn, const void* grad_out, void* acc, void* grad_value, void* grad_loc,
+                                void* grad_attn, const MsdaDims& d, hipStream_t stream) {
+  const size_t n_value = size_t(d.B) * size_t(d.S) * size_t(d.M) * size_t(d.D);
+  const bool image = acc != grad_value;
+  int st = zero_if_not_packed(shapes, lsi, d.L, d.S, acc, n_value * (image ? sizeof(float) : size_t(elem_size(vdt))), stream);
+  if (st != VNX_OK) return st;
+  st = msda_backward_generic(vdt, ldt, value, shapes, lsi, loc, attn, grad_out, acc, grad_loc, grad_attn, d,
+                             /*only_if_not_packed=*/1, stream);
+  if (st != VNX_OK) return st;
+  if (image) return convert_f32_to(vdt, acc, grad_value, int64_t(n_value), shapes, lsi, d.L, d.S, stream);
+  return VNX_OK;
 }
 
 int vnx_msda_backward(int value_dtype, int loc_dtype, const void* value,
@@ -382,27 +390,23 @@ int vnx_msda_backward(int value_dtype, int loc_dtype, const void* value,
                         level_start_index, sampling_loc, attn_weight, d);
   if (st != VNX_OK) return st;
   hipStream_t stream = (hipStream_t)hip_stream;
-  const int variant = kernel_variant();
+  const KernelVariant kv = kernel_variant();
+  const MsdaBackwardPlan plan = plan_backward(value_dtype, loc_dtype, d, flags, kv, false);
   const size_t n_value = size_t(batch) * size_t(spatial_size) * size_t(num_heads) * size_t(channels);
-  const size_t need = vnx_msda_backward_workspace_bytes(value_dtype, loc_dtype, batch, spatial_size,
-                                                        num_heads, channels, num_levels, num_query,
-                                                        num_point, flags);
   if (n_value > 0 && !grad_value) {
     set_error("vnx_msda_backward: null grad_value");
     return VNX_ERR_INVALID_ARGUMENT;
   }
   const bool empty = (batch == 0 || num_query == 0);
-  if (need > 0 && !empty && (!workspace || workspace_bytes < need)) {
+  if (plan.total > 0 && !empty && (!workspace || workspace_bytes < plan.total)) {
     set_error("vnx_msda_backward: needs %zu workspace bytes (vnx_msda_backward_workspace_bytes), got %zu",
-              need, workspace_bytes);
+              plan.total, workspace_bytes);
     return VNX_ERR_WORKSPACE;
   }
   if (!empty && (!grad_output || !grad_sampling_loc || !grad_attn_weight)) {
     set_error("vnx_msda_backward: null gradient pointer");
     return VNX_ERR_INVALID_ARGUMENT;
   }
-  const bool sixteen = (value_dtype == VNX_BF16 || value_dtype == VNX_F16);
-  const size_t image_bytes = sixteen ? sizeof(float) * n_value : 0;
   if (empty) {  // no queries: the gradient of value is all zeros, the other two are empty
     if (n_value > 0 &&
         hipMemsetAsync(grad_value, 0, n_value * size_t(elem_size(value_dtype)), stream) != hipSuccess) {
@@ -411,167 +415,107 @@ int vnx_msda_backward(int value_dtype, int loc_dtype, const void* value,
     }
     return VNX_OK;
   }
+  char* const ws = (char*)workspace;
+  void* const image = plan.image ? (void*)(ws + plan.off_image) : nullptr;
+  void* const gv_acc = plan.image ? image : grad_value;      // the generic kernels' fp32 accumulator
 
-  if (bwd_fast_path(value_dtype, loc_dtype, d, variant)) {
-    // (1) grad_loc / grad_attn: per-query gather kernel, no atomics; it also leaves one 16-B
-    //     geometry record per sample in the workspace.
-    // (2) grad_value: owner-computes units fed by those records; does nothing on the device
-    //     unless the levels are packed.
-    // (3) unless the caller promised packed levels: the general path, each kernel of which
-    //     does nothing on the device when the levels ARE packed.  No host sync either way.
-    // (The record-less predecessor of (2) -- every unit re-deriving its level's geometry -- and the side
-    //  stream that overlapped it with (1) are archived under tools/experiments/msda_d32_gv.hip.)
-    if (use_direct(value_dtype, loc_dtype, d, variant)) {
-      // (1) grad_value from the op's own inputs and (2) grad_loc / grad_attn: neither reads what the other writes.  One after
-      // the other on the caller's stream -- or, with VNX_MSDA_FORK, (1) on the side stream between two events and (2) on the
-      // caller's stream, which then waits for (1).  Development build: 441 = fork, 442 = (1) alone, 100..199 = (2) alone (timing).
-      // (Launching (2) without the packet's barrier bit -- hipExtAnyOrderLaunch, same stream, no events -- was tried: the flag is
-      // not honoured on gfx9 parts (hip_ext.h says so; measured 23.70 vs 23.93 us eager, no overlap in the kernel trace).)
-      const bool only_gl = variant >= 100 && variant < 200;
-      const bool only_gv = variant == 442;
-      // Both halves as ONE launch where the paired kernel is built for the call (msda_d32.hip: msda_bwd_pair_kernel; fp32,
-      // L*P == 16, the one-wave grad_loc configuration -- the decoders' calls): the grad_value units first, the grad_loc work in the
-      // remaining workgroups, sharing the GPU without a second queue.  Development build: 444 = the two launches instead,
-      // 445 / 446 / 447 = the paired kernel with the grad_value groups first / the grad_loc groups first / alternating.
-      if (!only_gl && !only_gv && !(flags & VNX_MSDA_FORK) && variant != 441 && variant != 444 &&
-          msda_backward_pair_supported(value_dtype, loc_dtype, d) && (!sixteen || (flags & VNX_MSDA_LEVELS_PACKED))) {
-        const int order = variant == 445 ? 0 : variant == 446 ? 1 : variant == 447 ? 2 : VNX_PAIR_ORDER;
-        st = msda_backward_pair_d32(value_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
-                                    grad_sampling_loc, grad_attn_weight, d, order, stream);
-        if (st != VNX_OK) return st;
-        if (!(flags & VNX_MSDA_LEVELS_PACKED)) {      // the general path, every kernel of which does nothing when the levels ARE packed
-          st = zero_if_not_packed(spatial_shapes, level_start_index, num_levels, spatial_size, grad_value,
-                                  n_value * size_t(elem_size(value_dtype)), stream);
-          if (st != VNX_OK) return st;
-          st = msda_backward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                                     grad_output, grad_value, grad_sampling_loc, grad_attn_weight, d, /*only_if_not_packed=*/1, stream);
-          if (st != VNX_OK) return st;
-        }
-        return VNX_OK;
-      }
-      SideLane* lane = (((flags & VNX_MSDA_FORK) || variant == 441) && !only_gl && !only_gv) ? side_lane() : nullptr;
-      if (lane) {
-        if (hipEventRecord(lane->fork, stream) != hipSuccess || hipStreamWaitEvent(lane->side, lane->fork, 0) != hipSuccess) {
-          (void)hipGetLastError();
-          lane = nullptr;
-        }
-      }
-      int st_gv = VNX_OK;
-      if (!only_gl)
-        st_gv = msda_backward_gvdirect_d32(value_dtype, loc_dtype, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                                           grad_output, grad_value, d, false, lane ? lane->side : stream);
-      if (lane && hipEventRecord(lane->join, lane->side) != hipSuccess) {
-        set_error("vnx_msda_backward: hipEventRecord on the side stream failed");
-        st_gv = VNX_ERR_LAUNCH;
-      }
-      st = VNX_OK;
-      if (!only_gv)
-        st = msda_backward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                               grad_output, nullptr, grad_sampling_loc, grad_attn_weight, d,
-                               only_gl ? variant : 100 + (variant < 100 ? variant : 0), nullptr, nullptr, nullptr, stream);
-      if (lane && hipStreamWaitEvent(stream, lane->join, 0) != hipSuccess) {      // the join: always, once forked
-        set_error("vnx_msda_backward: hipStreamWaitEvent on the caller's stream failed");
+  if (plan.path == BwdPath::Generic) {
+    // zero-filled image + hardware fp32/fp64 atomics
+    const size_t acc_bytes = n_value * (plan.image ? sizeof(float) : size_t(elem_size(value_dtype)));
+    if (acc_bytes > 0) {
+      const hipError_t e = hipMemsetAsync(gv_acc, 0, acc_bytes, stream);
+      if (e != hipSuccess) {
+        set_error("vnx_msda_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
         return VNX_ERR_LAUNCH;
       }
-      if (st_gv != VNX_OK) return st_gv;
-      if (st != VNX_OK) return st;
-      if (!(flags & VNX_MSDA_LEVELS_PACKED) && !only_gl && !only_gv) {
-        // the general path, every kernel of which does nothing on the device when the levels ARE packed
-        void* gv_acc = sixteen ? workspace : grad_value;
-        const size_t acc_bytes = sixteen ? image_bytes : n_value * size_t(elem_size(value_dtype));
-        st = zero_if_not_packed(spatial_shapes, level_start_index, num_levels, spatial_size, gv_acc, acc_bytes, stream);
-        if (st != VNX_OK) return st;
-        st = msda_backward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                                   grad_output, gv_acc, grad_sampling_loc, grad_attn_weight, d, /*only_if_not_packed=*/1, stream);
-        if (st != VNX_OK) return st;
-        if (sixteen)
-          return convert_f32_to(value_dtype, workspace, grad_value, int64_t(n_value), spatial_shapes, level_start_index,
-                                num_levels, spatial_size, stream);
-      }
-      return VNX_OK;
     }
-    const bool tiles = use_tiles(value_dtype, loc_dtype, d, variant);
-    const size_t rec_bytes = fast_path_scratch_bytes(value_dtype, loc_dtype, d, variant);
+    if (kv.atomics_backward && msda_d32_bwd_supported(value_dtype, loc_dtype, d))
+      st = msda_backward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
+                             sampling_loc, attn_weight, grad_output, gv_acc, grad_sampling_loc,
+                             grad_attn_weight, d, /*atomics=*/true, kv, nullptr, nullptr, nullptr, stream);
+    else
+      st = msda_backward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
+                                 sampling_loc, attn_weight, grad_output, gv_acc, grad_sampling_loc,
+                                 grad_attn_weight, d, /*only_if_not_packed=*/0, stream);
+    if (st != VNX_OK) return st;
+    if (plan.image)
+      return convert_f32_to(value_dtype, image, grad_value, int64_t(n_value), nullptr, nullptr, 0, 0, stream);
+    return VNX_OK;
+  }
+
+  if (plan.path == BwdPath::Pair) {
+    st = msda_backward_pair_d32(value_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
+                                grad_value, grad_sampling_loc, grad_attn_weight, d,
+                                kv.pair_order >= 0 ? kv.pair_order : VNX_PAIR_ORDER, stream);
+    if (st != VNX_OK) return st;
+  } else if (plan.path == BwdPath::Direct) {
+    // (1) grad_value from the op's own inputs and (2) grad_loc / grad_attn: neither reads what the other writes.  One after
+    // the other on the caller's stream -- or, with VNX_MSDA_FORK, (1) on the side stream between two events and (2) on the
+    // caller's stream, which then waits for (1).
+    // (Launching (2) without the packet's barrier bit -- hipExtAnyOrderLaunch, same stream, no events -- was tried: the flag is
+    // not honoured on gfx9 parts (hip_ext.h says so; measured 23.70 vs 23.93 us eager, no overlap in the kernel trace).)
+    SideLane* lane = plan.fork ? side_lane() : nullptr;
+    if (lane) {
+      if (hipEventRecord(lane->fork, stream) != hipSuccess || hipStreamWaitEvent(lane->side, lane->fork, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        lane = nullptr;
+      }
+    }
+    int st_gv = VNX_OK;
+    if (!plan.only_gl)
+      st_gv = msda_backward_gvdirect_d32(value_dtype, loc_dtype, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                         grad_output, grad_value, d, false, lane ? lane->side : stream);
+    if (lane && hipEventRecord(lane->join, lane->side) != hipSuccess) {
+      set_error("vnx_msda_backward: hipEventRecord on the side stream failed");
+      st_gv = VNX_ERR_LAUNCH;
+    }
+    st = VNX_OK;
+    if (!plan.only_gv)
+      st = msda_backward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                             grad_output, nullptr, grad_sampling_loc, grad_attn_weight, d, /*atomics=*/false, kv, nullptr,
+                             nullptr, nullptr, stream);
+    if (lane && hipStreamWaitEvent(stream, lane->join, 0) != hipSuccess) {      // the join: always, once forked
+      set_error("vnx_msda_backward: hipStreamWaitEvent on the caller's stream failed");
+      return VNX_ERR_LAUNCH;
+    }
+    if (st_gv != VNX_OK) return st_gv;
+    if (st != VNX_OK) return st;
+  } else {
+    const bool tiles = plan.path == BwdPath::Tiles;
     void* records = tiles ? nullptr : workspace;
     void* tile_words = tiles ? workspace : nullptr;
-    float* tile_copy = (tiles && tile_copy_wanted(d, variant))
-                           ? (float*)((char*)workspace + align256(msda_gvtiles_summary_bytes(d, msda_bwd_tile_queries(d, variant))))
-                           : nullptr;
-    const bool split16 = split_image_needed(value_dtype, loc_dtype, d, variant);
-    void* image = (sixteen && (!(flags & VNX_MSDA_LEVELS_PACKED) || split16)) ? (void*)((char*)workspace + rec_bytes) : nullptr;
-    float* split_image = split16 ? (float*)image : nullptr;
-    float* partials = tiles ? (float*)((char*)workspace + tiles_partials_offset(d, variant)) : nullptr;
-    const bool only_gl = variant >= 100 && variant < 200;  // timing ablations
-    const bool only_gv = (variant >= 400 && variant < 430) || (variant > 431 && variant < 500);
+    float* tile_copy = plan.copy ? (float*)(ws + plan.off_loc) : nullptr;
+    float* split_image = plan.split_image ? (float*)image : nullptr;
+    float* partials = tiles ? (float*)(ws + plan.off_partials) : nullptr;
     // records mode: the accumulation-image argument carries the fp32 target of the query pieces' atomics (grad_value itself
     // or the split image), whose rows of the query-split levels the kernel zeroes (gv_query_splits); tile mode: nothing
     st = msda_backward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
                            sampling_loc, attn_weight, grad_output,
                            tiles ? nullptr : (value_dtype == VNX_F32 ? grad_value : (void*)split_image), grad_sampling_loc,
-                           grad_attn_weight, d, only_gl ? variant : 100 + (variant < 100 ? variant : 0),
-                           records, tile_words, tile_copy, stream);
+                           grad_attn_weight, d, /*atomics=*/false, kv, records, tile_words, tile_copy, stream);
     if (st != VNX_OK) return st;
-    if (!only_gl) {
-      if (tiles)
-        st = tile_copy
-                 ? msda_backward_gvtiles_d32(value_dtype, VNX_F32, spatial_shapes, level_start_index, tile_copy,
-                                             tile_copy + 2 * (int64_t(d.B) * d.Lq * d.M * d.L * d.P), tile_words, grad_output,
-                                             grad_value, d, msda_bwd_tile_queries(d, variant), partials, true, stream)
-                 : msda_backward_gvtiles_d32(value_dtype, loc_dtype, spatial_shapes, level_start_index, sampling_loc,
-                                             attn_weight, tile_words, grad_output, grad_value, d,
-                                             msda_bwd_tile_queries(d, variant), partials, false, stream);
+    if (!plan.only_gl) {
+      if (tiles)      // from the compact fp32 copy where the grad_loc kernel left one, from the op's own inputs otherwise
+        st = msda_backward_gvtiles_d32(value_dtype, tile_copy ? VNX_F32 : loc_dtype, spatial_shapes, level_start_index,
+                                       tile_copy ? (const void*)tile_copy : sampling_loc,
+                                       tile_copy ? (const void*)(ws + plan.off_attn) : attn_weight, tile_words, grad_output,
+                                       grad_value, d, plan.tile_queries, kv.gv_units, partials, plan.copy, stream);
       else
         st = msda_backward_gvrec_d32(value_dtype, spatial_shapes, level_start_index, records, grad_output,
-                                     grad_value, d, variant, split_image, stream);
+                                     grad_value, d, kv, split_image, stream);
       if (st != VNX_OK) return st;
       if (split_image) {
         st = msda_split_levels_convert(value_dtype, spatial_shapes, level_start_index, split_image, grad_value, d,
-                                       tiles, stream);
+                                       tiles, kv.gv_units, stream);
         if (st != VNX_OK) return st;
       }
     }
-    if (!(flags & VNX_MSDA_LEVELS_PACKED) && !only_gl && !only_gv) {
-      void* gv_acc = sixteen ? image : grad_value;
-      const size_t acc_bytes = sixteen ? image_bytes : n_value * size_t(elem_size(value_dtype));
-      st = zero_if_not_packed(spatial_shapes, level_start_index, num_levels, spatial_size, gv_acc,
-                              acc_bytes, stream);
-      if (st != VNX_OK) return st;
-      st = msda_backward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
-                                 sampling_loc, attn_weight, grad_output, gv_acc, grad_sampling_loc,
-                                 grad_attn_weight, d, /*only_if_not_packed=*/1, stream);
-      if (st != VNX_OK) return st;
-      if (sixteen)
-        return convert_f32_to(value_dtype, image, grad_value, int64_t(n_value), spatial_shapes,
-                              level_start_index, num_levels, spatial_size, stream);
-    }
-    return VNX_OK;
   }
-
-  void* gv_acc = sixteen ? workspace : grad_value;
-  const size_t acc_bytes = sixteen ? image_bytes : n_value * size_t(elem_size(value_dtype));
-  // general path: zero-filled image + hardware fp32/fp64 atomics
-  if (acc_bytes > 0) {
-    const hipError_t e = hipMemsetAsync(gv_acc, 0, acc_bytes, stream);
-    if (e != hipSuccess) {
-      set_error("vnx_msda_backward: hipMemsetAsync failed: %s", hipGetErrorString(e));
-      return VNX_ERR_LAUNCH;
-    }
-  }
-  if (variant >= 300 && variant < 400 && msda_d32_bwd_supported(value_dtype, loc_dtype, d))
-    st = msda_backward_d32(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
-                           sampling_loc, attn_weight, grad_output, gv_acc, grad_sampling_loc,
-                           grad_attn_weight, d, variant - 300, nullptr, nullptr, nullptr, stream);
-  else
-    st = msda_backward_generic(value_dtype, loc_dtype, value, spatial_shapes, level_start_index,
-                               sampling_loc, attn_weight, grad_output, gv_acc, grad_sampling_loc,
-                               grad_attn_weight, d, /*only_if_not_packed=*/0, stream);
-  if (st != VNX_OK) return st;
-  if (sixteen)
-    return convert_f32_to(value_dtype, workspace, grad_value, int64_t(n_value), nullptr, nullptr, 0, 0,
-                          stream);
+  if (plan.unpacked_tail)
+    return unpacked_levels_tail(value_dtype, loc_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                grad_output, gv_acc, grad_value, grad_sampling_loc, grad_attn_weight, d, stream);
   return VNX_OK;
 }
-
 
 // ---- fused prologue (include/vnext_hip.h) -----------------------------------------------------
 static int check_fused(const char* fn, int value_dtype, int q_dtype, const MsdaDims& d, int ref_dim, int ref_div) {
@@ -609,8 +553,9 @@ int vnx_msda_fused_forward(int value_dtype, int query_dtype, const void* value, 
     set_error("vnx_msda_fused_forward: null pointer argument");
     return VNX_ERR_INVALID_ARGUMENT;
   }
+  const KernelVariant kv = kernel_variant();
 #ifdef VNX_DEV_VARIANTS
-  if (use_tile_forward(value_dtype, query_dtype, d, kernel_variant())) {
+  if (kv.tile_fwd == 1 && msda_tile_fwd_supported(value_dtype, query_dtype, d)) {
     const FusedArgs fa{reference_points, nullptr, ref_dim, reference_batch_div, nullptr};
     return msda_forward_tile(value, spatial_shapes, level_start_index, sampling_offsets, attention_logits, output, d, &fa, 0,
                              (hipStream_t)hip_stream);
@@ -618,43 +563,18 @@ int vnx_msda_fused_forward(int value_dtype, int query_dtype, const void* value, 
 #endif
   return msda_fused_d32(false, value_dtype, query_dtype, value, spatial_shapes, level_start_index, sampling_offsets,
                         attention_logits, nullptr, output, nullptr, d, nullptr, reference_points, nullptr, ref_dim,
-                        reference_batch_div, nullptr, nullptr, nullptr, nullptr, (hipStream_t)hip_stream, ref_f32);
-}
-
-// Scratch of the fused backward.  Record-fed grad_value: the sample records.  Tile-fed (use_tiles; the fused launcher
-// always takes the automatic configuration, hence tile queries of variant 0): [tile words | decoded locations, fp32,
-// 8 B per sample | softmax weights, fp32, 4 B per sample] -- the two tensors the fused prologue otherwise never
-// materialises, 12 B per sample against the records' 16 + 4.
-struct FusedScratch { bool tiles, direct; size_t words, loc, attn, partials, total; };
-static FusedScratch fused_scratch(int vdt, const MsdaDims& d, int variant) {
-  FusedScratch f{};
-  f.tiles = use_tiles(vdt, VNX_F32, d, variant);
-  f.direct = !f.tiles && use_direct(vdt, VNX_F32, d, variant);
-  if (f.direct) {      // self-decoding grad_value kernel (below 1 024 queries): only the decoded locations / weights, fp32
-    const size_t samples = size_t(d.B) * d.Lq * d.M * d.L * d.P;
-    f.loc = align256(samples * 8);
-    f.attn = align256(samples * 4);
-    f.total = f.loc + f.attn;
-  } else if (f.tiles) {
-    const size_t samples = size_t(d.B) * d.Lq * d.M * d.L * d.P;
-    f.words = align256(msda_gvtiles_summary_bytes(d, msda_bwd_tile_queries(d, 0)));
-    f.loc = align256(samples * 8);
-    f.attn = align256(samples * 4);
-    f.partials = align256(msda_gvtiles_partial_bytes(d));      // the query pieces' partial rows, behind the three
-    f.total = f.words + f.loc + f.attn + f.partials;
-  } else {
-    f.total = align256(msda_gvrec_record_bytes(d));
-  }
-  return f;
+                        reference_batch_div, nullptr, nullptr, nullptr, nullptr, kv, (hipStream_t)hip_stream, ref_f32);
 }
 
 size_t vnx_msda_fused_backward_workspace_bytes(int value_dtype, int batch, int spatial_size, int num_heads, int num_levels,
                                                int num_query, int num_point) {
   const MsdaDims d{batch, spatial_size, num_heads, 32, num_levels, num_query, num_point};
   // the larger of the two layouts: the variant may change between this call and the backward (A/B runs); the record-fed
-  // one (variant 430) needs the fp32 split image for 16-bit values
-  const size_t image = split_image_needed(value_dtype, VNX_F32, d, 430) ? sizeof(float) * size_t(batch) * size_t(spatial_size) * num_heads * 32 : 0;
-  const size_t a = fused_scratch(value_dtype, d, 430).total + image, b = fused_scratch(value_dtype, d, 0).total;
+  // one needs the fp32 split image for 16-bit values
+  KernelVariant records;
+  records.gv_path = GvPath::Records;
+  const size_t a = plan_backward(value_dtype, VNX_F32, d, VNX_MSDA_LEVELS_PACKED, records, true).total;
+  const size_t b = plan_backward(value_dtype, VNX_F32, d, VNX_MSDA_LEVELS_PACKED, KernelVariant{}, true).total;
   return a > b ? a : b;
 }
 
@@ -690,59 +610,43 @@ int vnx_msda_fused_backward(int value_dtype, int query_dtype, const void* value,
     set_error("vnx_msda_fused_backward: null pointer argument");
     return VNX_ERR_INVALID_ARGUMENT;
   }
-  const int variant = kernel_variant();
-  const FusedScratch fs = fused_scratch(value_dtype, d, variant);
-  const size_t rec_bytes = fs.total;
-  const bool split16 = split_image_needed(value_dtype, VNX_F32, d, variant);
-  const size_t need = rec_bytes + (split16 ? sizeof(float) * size_t(batch) * size_t(spatial_size) * num_heads * 32 : 0);
-  if (!workspace || workspace_bytes < need) {
-    set_error("vnx_msda_fused_backward: workspace of %zu bytes needed (got %zu)", need, workspace_bytes);
+  const KernelVariant kv = kernel_variant();
+  const MsdaBackwardPlan plan = plan_backward(value_dtype, VNX_F32, d, VNX_MSDA_LEVELS_PACKED, kv, true);
+  if (!workspace || workspace_bytes < plan.total) {
+    set_error("vnx_msda_fused_backward: workspace of %zu bytes needed (got %zu)", plan.total, workspace_bytes);
     return VNX_ERR_WORKSPACE;
   }
-  float* split_image = split16 ? (float*)((char*)workspace + rec_bytes) : nullptr;
-  void* fp32_target = (fs.tiles || fs.direct) ? nullptr : (value_dtype == VNX_F32 ? grad_value : (void*)split_image);
-  if (fs.direct) {
-    // (1) grad of the Linear outputs (+ reference points) and the decoded locations / softmax weights, laid out
-    // [batch][head][level][query][point]; (2) grad_value by the self-decoding kernel from those (msda_d32_gvdirect.hip):
-    // 12 B per sample where the record-fed kernel was left 16 + 4, no tags to select by, no chunk loop
-    float* d_loc = (float*)workspace;
-    float* d_attn = (float*)((char*)workspace + fs.loc);
-    st = msda_fused_d32(true, value_dtype, query_dtype, value, spatial_shapes, level_start_index, sampling_offsets,
-                        attention_logits, grad_output, grad_sampling_offsets, grad_attention_logits, d, nullptr,
-                        reference_points, grad_reference_points, ref_dim, reference_batch_div, nullptr, nullptr, d_loc, d_attn,
-                        stream, ref_f32);
-    if (st != VNX_OK) return st;
+  char* const ws = (char*)workspace;
+  const bool tiles = plan.path == BwdPath::Tiles, records = plan.path == BwdPath::Records;
+  float* split_image = plan.split_image ? (float*)(ws + plan.off_image) : nullptr;
+  float* d_loc = plan.copy ? (float*)(ws + plan.off_loc) : nullptr;
+  float* d_attn = plan.copy ? (float*)(ws + plan.off_attn) : nullptr;
+  // (1) grad of the Linear outputs (+ reference points), and what the grad_value kernel of the path reads:
+  //   Direct   the decoded locations / softmax weights, laid out [batch][head][level][query][point] -- 12 B per sample where
+  //            the record-fed kernel was left 16 + 4, no tags to select by, no chunk loop
+  //   Tiles    one word per (level, tile of queries) and the decoded locations / weights
+  //   Records  the sample records; the fp32 target of the query pieces' atomics is grad_value itself or the split image
+  // (2) grad_value from those.  Packed levels are required (no-op on the device otherwise).
+  st = msda_fused_d32(true, value_dtype, query_dtype, value, spatial_shapes, level_start_index, sampling_offsets,
+                      attention_logits, grad_output, grad_sampling_offsets, grad_attention_logits, d,
+                      records ? workspace : nullptr, reference_points, grad_reference_points, ref_dim, reference_batch_div,
+                      records ? (value_dtype == VNX_F32 ? grad_value : (void*)split_image) : nullptr,
+                      tiles ? workspace : nullptr, d_loc, d_attn, kv, stream, ref_f32);
+  if (st != VNX_OK) return st;
+  if (plan.path == BwdPath::Direct)
     return msda_backward_gvdirect_d32(value_dtype, VNX_F32, spatial_shapes, level_start_index, d_loc, d_attn, grad_output,
                                       grad_value, d, true, stream);
-  }
-  if (fs.tiles) {
-    // (1) grad of the Linear outputs (+ reference points), one word per (level, tile of queries) and the decoded
-    // locations / weights; (2) grad_value from those.  Packed levels are required (no-op on the device otherwise).
-    void* words = workspace;
-    float* tile_loc = (float*)((char*)workspace + fs.words);
-    float* tile_attn = (float*)((char*)workspace + fs.words + fs.loc);
-    float* partials = (float*)((char*)workspace + fs.words + fs.loc + fs.attn);
-    st = msda_fused_d32(true, value_dtype, query_dtype, value, spatial_shapes, level_start_index, sampling_offsets,
-                        attention_logits, grad_output, grad_sampling_offsets, grad_attention_logits, d, nullptr,
-                        reference_points, grad_reference_points, ref_dim, reference_batch_div, fp32_target, words, tile_loc,
-                        tile_attn, stream, ref_f32);
-    if (st != VNX_OK) return st;
-    st = msda_backward_gvtiles_d32(value_dtype, VNX_F32, spatial_shapes, level_start_index, tile_loc, tile_attn, words,
-                                   grad_output, grad_value, d, msda_bwd_tile_queries(d, 0), partials, true, stream);
-  } else {
-    // (1) grad of the Linear outputs (+ reference points) and the sample records; (2) grad_value from the records
-    st = msda_fused_d32(true, value_dtype, query_dtype, value, spatial_shapes, level_start_index, sampling_offsets,
-                        attention_logits, grad_output, grad_sampling_offsets, grad_attention_logits, d, workspace,
-                        reference_points, grad_reference_points, ref_dim, reference_batch_div, fp32_target, nullptr, nullptr,
-                        nullptr, stream, ref_f32);
-    if (st != VNX_OK) return st;
+  if (tiles)
+    st = msda_backward_gvtiles_d32(value_dtype, VNX_F32, spatial_shapes, level_start_index, d_loc, d_attn, workspace,
+                                   grad_output, grad_value, d, plan.tile_queries, kv.gv_units, (float*)(ws + plan.off_partials),
+                                   true, stream);
+  else
     st = msda_backward_gvrec_d32(value_dtype, spatial_shapes, level_start_index, workspace, grad_output,
-                                 grad_value, d, variant, split_image, stream);
-  }
+                                 grad_value, d, kv, split_image, stream);
   if (st != VNX_OK) return st;
   if (split_image)
     return msda_split_levels_convert(value_dtype, spatial_shapes, level_start_index, split_image, grad_value, d,
-                                     fs.tiles, stream);
+                                     tiles, kv.gv_units, stream);
   return VNX_OK;
 }
 

@@ -1066,7 +1066,7 @@ static int mask_head_forward_impl(int dtype, const void* mask_feats,
                                   const void* reference_points, const void* params,
                                   const int32_t* inst_image, void* out, int num_images,
                                   int channels, int height, int width, int num_insts,
-                                  int num_params, int stride, const MaskHeadZero* zero, void* hip_stream) {
+                                  int num_params, int stride, const MaskHeadZero* zero, const KernelVariant& kv, void* hip_stream) {
   if (dtype != VNX_F32) {
     set_error("vnx_dynamic_mask_head_forward: only f32 is built (got dtype %d)", dtype);
     return VNX_ERR_UNSUPPORTED;
@@ -1087,8 +1087,7 @@ static int mask_head_forward_impl(int dtype, const void* mask_feats,
     set_error("vnx_dynamic_mask_head_forward_train: null gradient buffer");
     return VNX_ERR_INVALID_ARGUMENT;
   }
-  const int variant = kernel_variant();
-  if (zero && (num_insts == 0 || height == 0 || width == 0 || variant == 799)) {
+  if (zero && (num_insts == 0 || height == 0 || width == 0 || kv.mh_strip)) {
     // no forward launch to fold the zero-fill into (or the development build's strip kernel): its own launch
     if (zn0 + zn1 + zn2) {
       size_t blocks = ((zn0 + zn1 + zn2) / 4 + 255) / 256;
@@ -1105,8 +1104,8 @@ static int mask_head_forward_impl(int dtype, const void* mask_feats,
     set_error("vnx_dynamic_mask_head_forward: null pointer argument");
     return VNX_ERR_INVALID_ARGUMENT;
   }
-  if (variant != 799) {                      // (development build: 799 = the strip kernel, 700 + r = r runs per instance)
-    const int runs = mask_head_runs(num_insts, height, width, variant > 700 && variant < 799 ? variant - 700 : 0);
+  if (!kv.mh_strip) {                        // (development build: the strip kernel, or a forced number of runs per instance)
+    const int runs = mask_head_runs(num_insts, height, width, kv.mh_runs);
     const int halo = (width + 1 + 63) / 64 * 64;      // logits kept from the chunk before: the row above + the pixel to the left
     const int64_t waves = int64_t(num_insts) * runs;
     const size_t lds_bytes = size_t(4) * size_t(halo + 384) * sizeof(float);
@@ -1162,7 +1161,7 @@ extern "C" int vnx_dynamic_mask_head_forward(int dtype, const void* mask_feats,
                                              int channels, int height, int width, int num_insts,
                                              int num_params, int stride, void* hip_stream) {
   return mask_head_forward_impl(dtype, mask_feats, reference_points, params, inst_image, out, num_images, channels, height, width,
-                                num_insts, num_params, stride, nullptr, hip_stream);
+                                num_insts, num_params, stride, nullptr, kernel_variant(), hip_stream);
 }
 
 extern "C" int vnx_dynamic_mask_head_forward_train(int dtype, const void* mask_feats,
@@ -1172,7 +1171,7 @@ extern "C" int vnx_dynamic_mask_head_forward_train(int dtype, const void* mask_f
                                                    int num_insts, int num_params, int stride, void* hip_stream) {
   const MaskHeadZero zero{grad_feats, grad_ref, grad_params};
   return mask_head_forward_impl(dtype, mask_feats, reference_points, params, inst_image, out, num_images, channels, height, width,
-                                num_insts, num_params, stride, &zero, hip_stream);
+                                num_insts, num_params, stride, &zero, kernel_variant(), hip_stream);
 }
 
 static int mask_head_backward_impl(int dtype, const void* mask_feats, const void* reference_points,

@@ -22,7 +22,7 @@
 //  * QPW (queries per wave) trades per-wave work for wave count: the 64 lanes
 //    are QPW queries x (8/QPW) sample groups x 8 channel lanes; sample groups
 //    are summed with cross-lane exchanges at the end.
-#include "vnx_common.h"
+#include "msda_launchers.h"
 #include "msda_d32_gvdirect_body.h"
 
 namespace vnx {
@@ -882,13 +882,13 @@ msda_fwd_slab_kernel(const TV* __restrict__ value, const int64_t* __restrict__ s
 }
 
 // the slab kernel takes a call when it is built for it (fp32 values, 4 levels x 4 points) and the call has enough queries per
-// (batch, head) for a workgroup's slab copy to pay (an encoder's; development build: variant 730 forces, 731 forbids)
-static bool use_slab_forward(int vdt, int ldt, const MsdaDims& d, int variant) {
+// (batch, head) for a workgroup's slab copy to pay (an encoder's; forced: KernelVariant::slab_fwd -- the development build forces with +1, forbids with -1)
+static bool use_slab_forward(int vdt, int ldt, const MsdaDims& d, int forced) {
   if (ldt != VNX_F32 || d.L != 4 || d.P != 4 || d.D != 32) return false;
   if (vdt != VNX_F32 && vdt != VNX_BF16 && vdt != VNX_F16) return false;      // (16-bit values: round 6)
   if (int64_t(d.S) * d.M * 128 >= (int64_t(1) << 31) || d.S >= (1 << 23)) return false;
-  if (variant == 731) return false;
-  return variant == 730 || d.Lq >= 2048;
+  if (forced < 0) return false;
+  return forced > 0 || d.Lq >= 2048;
 }
 
 // Workgroups per (batch, head): whole ROUNDS of resident workgroups (two per CU = 512) -- a partly filled last round leaves
@@ -941,31 +941,24 @@ static int launch_fwd_slab_cfg(const void* value, const int64_t* shapes, const i
 // kernel 177.6 / 68.8) -- and NOT the product path: with half of the taps staged instead of a quarter the call is no faster.
 // With 64-byte rows the gathered half was not bound by the L1's delivery to begin with (the same finding as at 360p,
 // DESIGN.md section 3.1g), and a CU's one 16-wave workgroup copies 77 KB per 6-13 tiles where two 8-wave ones copy 15 KB each.
-// Development build: variant 737 takes it (tests/test_msda_slab.py holds it to the oracle), anything else the small slab.
-static bool use_large_slab(const MsdaDims&, int variant) { return variant == 737; }
+// Development build: KernelVariant::large_slab takes it (tests/test_msda_slab.py holds it to the oracle), anything else the small slab.
+static bool use_large_slab(const MsdaDims&, bool forced) { return forced; }
 
 template <typename TV, typename TL>
 static int launch_fwd_slab(const void* value, const int64_t* shapes, const int64_t* lsi, const void* loc, const void* attn,
-                           void* out, const MsdaDims& d, const FusedArgs* fa, hipStream_t stream) {
+                           void* out, const MsdaDims& d, const FusedArgs* fa, bool large_slab, hipStream_t stream) {
   if constexpr (sizeof(TV) == 2) {
-    if (use_large_slab(d, kernel_variant()))
+    if (use_large_slab(d, large_slab))
       return launch_fwd_slab_cfg<TV, TL, kSlabWavesL, kSlabRowsCapL>(value, shapes, lsi, loc, attn, out, d, fa, stream);
   }
   return launch_fwd_slab_cfg<TV, TL, kSlabWaves, kSlabRowsCap>(value, shapes, lsi, loc, attn, out, d, fa, stream);
 }
 
-struct FwdCfg { int qpw; int wpb; };
-
-static FwdCfg pick_fwd_cfg(const MsdaDims& d, int variant) {
-  // variant: 0 auto; 2..5 force QPW = 8,4,2,1 with 4 waves/block; 12..15 the same with 1 wave/block
+static FwdCfg pick_fwd_cfg(const MsdaDims& d, FwdCfg forced) {
+  // forced: KernelVariant::fwd_cfg / gl_cfg (development build); qpw 0 = by size
   const int LP = d.L * d.P;
-  FwdCfg c{8, 4};
-  if (variant >= 20 && variant < 60) variant = (variant - 20) % 20;  // prefetch on/off wrappers
-  if (variant >= 60 && variant < 69) variant = 13;
-  if (variant == 69) variant = 0;                                    // automatic configuration, 8-lane map for 16-bit rows
-  if (variant >= 2 && variant <= 5) c = FwdCfg{8 >> (variant - 2), 4};
-  else if (variant >= 12 && variant <= 15) c = FwdCfg{8 >> (variant - 12), 1};
-  else {
+  FwdCfg c = forced;
+  if (c.qpw == 0) {
     // measured on MI355X (tools/time_variants.py): 4 queries per wave wins from the T=5 decoder
     // call (1 500 rows) to the 360p encoder call (25 500 rows); one query per 8-lane group only
     // pays on very large calls, where occupancy matters more than per-wave parallelism
@@ -981,22 +974,21 @@ static FwdCfg pick_fwd_cfg(const MsdaDims& d, int variant) {
 template <typename TV, typename TL, int QPW, int WPB>
 static int launch_fwd_cfg(const void* value, const int64_t* shapes, const int64_t* lsi,
                           const void* loc, const void* attn, void* out, const MsdaDims& d,
-                          int variant, hipStream_t stream) {
+                          const KernelVariant& kv, hipStream_t stream) {
   const int LP = d.L * d.P;
   const int tiles_per_batch = (d.Lq + QPW * WPB - 1) / (QPW * WPB);
   // phase 0 pays when the call has at least ~2 taps per row of the map (see the kernel);
-  // variants 20..39 force it on for A/B runs, 40..59 force it off
+  // the development build forces it on for A/B runs (KernelVariant::fwd_prefetch)
   const bool dense = int64_t(d.Lq) * LP * 4 >= 2 * int64_t(d.S);
   // Measured (tools/time_variants.py, T=5 decoder call): cold 10.5 vs 11.1 us with uniform
   // locations, but 10.9 vs 9.3 us with model-like ones and 6.7 vs 5.7 us cache-warm -> off by default.
   (void)dense;
-  bool want_prefetch = (variant >= 20 && variant < 40);
+  bool want_prefetch = kv.fwd_prefetch;
   if constexpr (!(QPW * 16 <= 64)) want_prefetch = false;
   if (LP != 16 || sizeof(TL) != 4 || d.L > 4) want_prefetch = false;
   int prefetch_rows = want_prefetch ? (d.S + tiles_per_batch * WPB - 1) / (tiles_per_batch * WPB) : 0;
   if (prefetch_rows > 32 * kPfSteps) prefetch_rows = 32 * kPfSteps;     // a larger share is streamed in part
-  if (variant >= 60 && variant < 68) prefetch_rows |= (variant - 60) << 16;
-  if (variant == 68) prefetch_rows |= 14 << 16;      // the fixed head -> XCD map (A/B record)
+  prefetch_rows |= kv.fwd_head_rot << 16;            // the head -> XCD map (A/B record)
   const int64_t blocks = int64_t(d.B) * tiles_per_batch * d.M;
   if (blocks >= (int64_t(1) << 31)) {
     set_error("msda_forward: %lld workgroups exceed the grid limit", (long long)blocks);
@@ -1012,9 +1004,9 @@ static int launch_fwd_cfg(const void* value, const int64_t* shapes, const int64_
       return check_launch("msda_fwd_d32_pf");
     }
   }
-  // 16-bit values: rows as 4 lanes x 16 B (variant 69 keeps the 8 x 8 B map for A/B runs)
+  // 16-bit values: rows as 4 lanes x 16 B (KernelVariant::fwd_lpr8 keeps the 8 x 8 B map for A/B runs)
   constexpr int kLpr = sizeof(TV) == 2 ? 4 : 8;
-  if (LP == 16 && kLpr == 4 && variant != 69)
+  if (LP == 16 && kLpr == 4 && !kv.fwd_lpr8)
     hipLaunchKernelGGL((msda_fwd_d32_kernel<TV, TL, QPW, WPB, 16, false, false, kLpr>), dim3(uint32_t(blocks)),
                        dim3(64 * WPB), lds, stream, (const TV*)value, shapes, lsi,
                        (const TL*)loc, (const TL*)attn, (TV*)out, d, tiles_per_batch, prefetch_rows,
@@ -1035,11 +1027,11 @@ static int launch_fwd_cfg(const void* value, const int64_t* shapes, const int64_
 template <typename TV, typename TL>
 static int launch_fwd(const void* value, const int64_t* shapes, const int64_t* lsi,
                       const void* loc, const void* attn, void* out, const MsdaDims& d,
-                      int variant, hipStream_t stream) {
-  const FwdCfg c = pick_fwd_cfg(d, variant);
+                      const KernelVariant& kv, hipStream_t stream) {
+  const FwdCfg c = pick_fwd_cfg(d, kv.fwd_cfg);
 #define VNX_CASE(Q, W)                                                                       \
   if (c.qpw == Q && c.wpb == W)                                                              \
-    return launch_fwd_cfg<TV, TL, Q, W>(value, shapes, lsi, loc, attn, out, d, variant, stream);
+    return launch_fwd_cfg<TV, TL, Q, W>(value, shapes, lsi, loc, attn, out, d, kv, stream);
   VNX_CASE(8, 4) VNX_CASE(4, 4) VNX_CASE(2, 4) VNX_CASE(1, 4)
   VNX_CASE(8, 1) VNX_CASE(4, 1) VNX_CASE(2, 1) VNX_CASE(1, 1)
   VNX_CASE(4, 2)
@@ -1062,17 +1054,17 @@ bool msda_d32_fwd_supported(int vdt, int ldt, const MsdaDims& d) {
 
 int msda_forward_d32(int vdt, int ldt, const void* value, const int64_t* shapes,
                      const int64_t* lsi, const void* loc, const void* attn, void* out, MsdaDims d,
-                     int variant, hipStream_t stream) {
-  if (use_slab_forward(vdt, ldt, d, variant)) {
-    if (vdt == VNX_F32) return launch_fwd_slab<float, float>(value, shapes, lsi, loc, attn, out, d, nullptr, stream);
-    if (vdt == VNX_BF16) return launch_fwd_slab<bf16_t, float>(value, shapes, lsi, loc, attn, out, d, nullptr, stream);
-    return launch_fwd_slab<f16_t, float>(value, shapes, lsi, loc, attn, out, d, nullptr, stream);
+                     const KernelVariant& kv, hipStream_t stream) {
+  if (use_slab_forward(vdt, ldt, d, kv.slab_fwd)) {
+    if (vdt == VNX_F32) return launch_fwd_slab<float, float>(value, shapes, lsi, loc, attn, out, d, nullptr, kv.large_slab, stream);
+    if (vdt == VNX_BF16) return launch_fwd_slab<bf16_t, float>(value, shapes, lsi, loc, attn, out, d, nullptr, kv.large_slab, stream);
+    return launch_fwd_slab<f16_t, float>(value, shapes, lsi, loc, attn, out, d, nullptr, kv.large_slab, stream);
   }
-  if (vdt == VNX_F32) return launch_fwd<float, float>(value, shapes, lsi, loc, attn, out, d, variant, stream);
-  if (vdt == VNX_BF16 && ldt == VNX_F32) return launch_fwd<bf16_t, float>(value, shapes, lsi, loc, attn, out, d, variant, stream);
-  if (vdt == VNX_BF16 && ldt == VNX_BF16) return launch_fwd<bf16_t, bf16_t>(value, shapes, lsi, loc, attn, out, d, variant, stream);
-  if (vdt == VNX_F16 && ldt == VNX_F32) return launch_fwd<f16_t, float>(value, shapes, lsi, loc, attn, out, d, variant, stream);
-  if (vdt == VNX_F16 && ldt == VNX_F16) return launch_fwd<f16_t, f16_t>(value, shapes, lsi, loc, attn, out, d, variant, stream);
+  if (vdt == VNX_F32) return launch_fwd<float, float>(value, shapes, lsi, loc, attn, out, d, kv, stream);
+  if (vdt == VNX_BF16 && ldt == VNX_F32) return launch_fwd<bf16_t, float>(value, shapes, lsi, loc, attn, out, d, kv, stream);
+  if (vdt == VNX_BF16 && ldt == VNX_BF16) return launch_fwd<bf16_t, bf16_t>(value, shapes, lsi, loc, attn, out, d, kv, stream);
+  if (vdt == VNX_F16 && ldt == VNX_F32) return launch_fwd<f16_t, float>(value, shapes, lsi, loc, attn, out, d, kv, stream);
+  if (vdt == VNX_F16 && ldt == VNX_F16) return launch_fwd<f16_t, f16_t>(value, shapes, lsi, loc, attn, out, d, kv, stream);
   set_error("msda_forward_d32: unsupported dtype pair (%d, %d)", vdt, ldt);
   return VNX_ERR_INVALID_ARGUMENT;
 }
@@ -1683,7 +1675,7 @@ msda_bwd_d32_kernel(const TV* __restrict__ value, const int64_t* __restrict__ sh
 template <typename TV, typename TL, int QPW, int WPB>
 static int launch_bwd_cfg(const void* value, const int64_t* shapes, const int64_t* lsi,
                           const void* loc, const void* attn, const void* grad_out, void* gv,
-                          void* grad_loc, void* grad_attn, const MsdaDims& d, bool atomics,
+                          void* grad_loc, void* grad_attn, const MsdaDims& d, bool atomics, int gv_units,
                           void* records, void* tile_summary, float* tile_copy, hipStream_t stream) {
   // records / tile mode: `gv` is not an accumulation image but the fp32 target of the query-split levels' atomics --
   // grad_value itself for fp32 values, the fp32 split image for 16-bit ones (or null) -- whose rows this kernel zeroes
@@ -1703,7 +1695,7 @@ static int launch_bwd_cfg(const void* value, const int64_t* shapes, const int64_
   // the unit ranges sit behind the records in the workspace (gv_unit_ids_offset); only the P == 4
   // grad_value kernel reads them
   void* unit_ids = (records != nullptr && d.P == 4) ? (void*)((char*)records + gv_unit_ids_offset(d)) : nullptr;
-  const int units_min = gv_units_min(d, tile_summary != nullptr, kernel_variant());
+  const int units_min = gv_units_min(d, tile_summary != nullptr, gv_units);
   constexpr int kLpr = (sizeof(TV) == 2 || VNX_K1_F32_LPR4(WPB)) ? 4 : 8;    // 16-bit rows as 4 lanes x 16 B; fp32: VNX_K1_F32_LPR4
 #define VNX_BWD_ARGS (const TV*)value, shapes, lsi, (const TL*)loc, (const TL*)attn, (const TV*)grad_out, (float*)gv, (TL*)grad_loc, \
                      (TL*)grad_attn, d, tiles_per_batch, (uint4_t*)records, (uint32_t*)unit_ids,                \
@@ -1724,15 +1716,13 @@ static int launch_bwd_cfg(const void* value, const int64_t* shapes, const int64_
 template <typename TV, typename TL>
 static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* lsi,
                       const void* loc, const void* attn, const void* grad_out, void* gv,
-                      void* grad_loc, void* grad_attn, const MsdaDims& d, int variant, void* records,
-                      void* tile_summary, float* tile_copy, hipStream_t stream) {
-  // variant 100+v: ablation without the grad_value atomics (timing only, wrong grad_value)
-  const bool atomics = variant < 100;
-  const FwdCfg c = pick_fwd_cfg(d, atomics ? variant : variant - 100);
+                      void* grad_loc, void* grad_attn, const MsdaDims& d, bool atomics, const KernelVariant& kv,
+                      void* records, void* tile_summary, float* tile_copy, hipStream_t stream) {
+  const FwdCfg c = pick_fwd_cfg(d, kv.gl_cfg);
 #define VNX_CASE(Q, W)                                                                       \
   if (c.qpw == Q && c.wpb == W)                                                              \
     return launch_bwd_cfg<TV, TL, Q, W>(value, shapes, lsi, loc, attn, grad_out, gv, grad_loc, \
-                                        grad_attn, d, atomics, records, tile_summary, tile_copy, stream);
+                                        grad_attn, d, atomics, kv.gv_units, records, tile_summary, tile_copy, stream);
   VNX_CASE(8, 4) VNX_CASE(4, 4) VNX_CASE(2, 4) VNX_CASE(1, 4)
   VNX_CASE(8, 1) VNX_CASE(4, 1) VNX_CASE(2, 1) VNX_CASE(1, 1)
   VNX_CASE(4, 2)
@@ -1803,14 +1793,12 @@ msda_bwd_pair_kernel(const TV* __restrict__ value, const int64_t* __restrict__ s
   stamp_end(stamps);
 }
 
-int msda_gvdirect_units_bound(const MsdaDims& d, int ut, int rows);
-
 // -> true when the call is one the paired kernel is built for (what the decoders of both models present: fp32 locations, fp32
 // or 16-bit values, L*P == 16 with 4 points, the one-wave configuration of the grad_loc kernel)
 bool msda_backward_pair_supported(int vdt, int ldt, const MsdaDims& d) {
   if (ldt != VNX_F32 || (vdt != VNX_F32 && vdt != VNX_BF16 && vdt != VNX_F16)) return false;
   if (d.P != 4 || d.L * d.P != 16 || d.Lq >= 1024) return false;
-  const FwdCfg c = pick_fwd_cfg(d, 0);
+  const FwdCfg c = pick_fwd_cfg(d, FwdCfg{0, 0});
   return c.qpw == 4 && c.wpb == 1;
 }
 
@@ -2128,9 +2116,8 @@ static int launch_bwd_slab(const void* value, const int64_t* shapes, const int64
   return check_launch(FUSED ? "msda_bwd_slab_fused" : "msda_bwd_slab");
 }
 
-int msda_bwd_tile_queries(const MsdaDims& d, int variant) {
-  // the grad_loc launcher's variant decoding: < 100 as is, 100..199 (grad_loc only, timing) minus 100, others automatic
-  const FwdCfg c = pick_fwd_cfg(d, variant < 100 ? variant : (variant < 200 ? variant - 100 : 0));
+int msda_bwd_tile_queries(const MsdaDims& d, FwdCfg forced) {      // forced: the grad_loc launcher's (KernelVariant::gl_cfg)
+  const FwdCfg c = pick_fwd_cfg(d, forced);
   return kTilePerWave ? c.qpw : c.qpw * c.wpb;
 }
 
@@ -2143,19 +2130,16 @@ bool msda_d32_bwd_supported(int vdt, int ldt, const MsdaDims& d) {
 int msda_backward_d32(int vdt, int ldt, const void* value, const int64_t* shapes,
                       const int64_t* lsi, const void* loc, const void* attn,
                       const void* grad_out, void* gv, void* grad_loc, void* grad_attn, MsdaDims d,
-                      int variant, void* records, void* tile_summary, float* tile_copy, hipStream_t stream) {
+                      bool atomics, const KernelVariant& kv, void* records, void* tile_summary, float* tile_copy, hipStream_t stream) {
   // the 16-bit row limit of the sample records (h0+1, w0+1 packed into one word)
-#define VNX_ARGS value, shapes, lsi, loc, attn, grad_out, gv, grad_loc, grad_attn, d, variant, records, tile_summary, tile_copy, stream
+#define VNX_ARGS value, shapes, lsi, loc, attn, grad_out, gv, grad_loc, grad_attn, d, atomics, kv, records, tile_summary, tile_copy, stream
   // tile-fed calls (the encoders'), fp32: the coarse levels staged in LDS (msda_bwd_slab_kernel; its boxes are per 4 queries,
-  // as the automatic configuration's).  The launcher's variant decoding: 100..199 = grad_loc only (timing), others automatic.
-  // Development build: 730 forces, 731 / 733 forbid (733: this kernel only, the forward keeps its slab).
-  {
-    const int v = variant >= 100 && variant < 200 ? variant - 100 : (variant < 100 ? variant : 0);
-    const int kv = kernel_variant();
-    if (vdt == VNX_F32 && ldt == VNX_F32 && v == 0 && gv == nullptr && records == nullptr && tile_copy == nullptr &&
-        tile_summary != nullptr && kv != 733 && msda_bwd_tile_queries(d, 0) == 4 && use_slab_forward(vdt, ldt, d, kv))
-      return launch_bwd_slab<false>(value, shapes, lsi, loc, attn, grad_out, grad_loc, grad_attn, tile_summary, d, FusedArgs{}, stream);
-  }
+  // as the automatic configuration's).  Development build: slab_fwd forces / forbids it together with the forward's slab,
+  // no_slab_backward forbids this kernel only (the forward keeps its slab).
+  if (vdt == VNX_F32 && ldt == VNX_F32 && gv == nullptr && records == nullptr && tile_copy == nullptr &&
+      tile_summary != nullptr && !kv.no_slab_backward && msda_bwd_tile_queries(d, FwdCfg{0, 0}) == 4 &&
+      use_slab_forward(vdt, ldt, d, kv.slab_fwd))
+    return launch_bwd_slab<false>(value, shapes, lsi, loc, attn, grad_out, grad_loc, grad_attn, tile_summary, d, FusedArgs{}, stream);
   if (vdt == VNX_F32) return launch_bwd<float, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_F32) return launch_bwd<bf16_t, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_BF16) return launch_bwd<bf16_t, bf16_t>(VNX_ARGS);
@@ -2189,7 +2173,7 @@ template <typename TV, typename TL, int QPW, int WPB>
 static int launch_bwd_fused_cfg(const void* value, const int64_t* shapes, const int64_t* lsi, const void* raw_off,
                                 const void* raw_logit, const void* grad_out, void* grad_off, void* grad_logit,
                                 const MsdaDims& d, void* records, void* tile_summary, const FusedArgs& fa,
-                                hipStream_t stream) {
+                                int gv_units, hipStream_t stream) {
   const int tiles_per_batch = (d.Lq + QPW * WPB - 1) / (QPW * WPB);
   const int64_t blocks = int64_t(d.B) * tiles_per_batch * d.M;
   if (blocks >= (int64_t(1) << 31)) {
@@ -2198,7 +2182,7 @@ static int launch_bwd_fused_cfg(const void* value, const int64_t* shapes, const 
   }
   const size_t lds = size_t(WPB) * 3 * QPW * 17 * 16 + 128;
   void* unit_ids = (records != nullptr && d.P == 4) ? (void*)((char*)records + gv_unit_ids_offset(d)) : nullptr;
-  const int units_min = gv_units_min(d, tile_summary != nullptr, kernel_variant());
+  const int units_min = gv_units_min(d, tile_summary != nullptr, gv_units);
   constexpr int kLpr = (sizeof(TV) == 2 || VNX_K1_F32_LPR4(WPB)) ? 4 : 8;
   hipLaunchKernelGGL((msda_bwd_d32_kernel<TV, TL, QPW, WPB, 16, false, true, kLpr>), dim3(uint32_t(blocks)), dim3(64 * WPB),
                      lds, stream, (const TV*)value, shapes, lsi, (const TL*)raw_off, (const TL*)raw_logit,
@@ -2212,26 +2196,26 @@ template <typename TV, typename TL>
 static int fused_dispatch(bool backward, const void* value, const int64_t* shapes, const int64_t* lsi,
                           const void* raw_off, const void* raw_logit, const void* grad_out, void* out_or_grad_off,
                           void* grad_logit, const MsdaDims& d, void* records, void* tile_summary, const FusedArgs& fa,
-                          hipStream_t stream) {
+                          const KernelVariant& kv, hipStream_t stream) {
   // encoder calls: the coarse levels staged in LDS (msda_fwd_slab_kernel; 16-bit values, and 16-bit offsets / logits: round 6)
-  if (!backward && use_slab_forward(sizeof(TV) == 4 ? VNX_F32 : VNX_BF16, VNX_F32, d, kernel_variant()))
-    return launch_fwd_slab<TV, TL>(value, shapes, lsi, raw_off, raw_logit, out_or_grad_off, d, &fa, stream);
+  if (!backward && use_slab_forward(sizeof(TV) == 4 ? VNX_F32 : VNX_BF16, VNX_F32, d, kv.slab_fwd))
+    return launch_fwd_slab<TV, TL>(value, shapes, lsi, raw_off, raw_logit, out_or_grad_off, d, &fa, kv.large_slab, stream);
   if constexpr (sizeof(TV) == 4 && sizeof(TL) == 4) {
     // ... their backward, tile-fed grad_value: msda_bwd_slab_kernel<true> was built and measured in round 6 (boxes per 4 queries, as
     // the automatic configuration's) and is NOT the product path -- kbench cold, fused backward, slab / gather form of the grad_loc
     // half: encoder-360p B = 5 175.2 / 171.0 us, B = 10 356.6 / 322.5, 720p B = 5 660.7 / 632.0, B = 2 287.0 / 286.0.  The fused
     // form decodes (exp, two 16-lane reductions per sample) and writes the 12-byte decoded copy of every sample on top of the
     // unfused kernel's work, at four waves per SIMD (128 VGPRs, 32 B of scratch): the slab's few per cent (66.0 against 69.7 us
-    // unfused) do not survive it.  Development build only: variant 734.
+    // unfused) do not survive it.  Development build only: KernelVariant::fused_slab_backward.
     if (backward && records == nullptr && tile_summary != nullptr && fa.tile_loc != nullptr && fa.qsplit_zero == nullptr &&
-        kernel_variant() == 734 && msda_bwd_tile_queries(d, 0) == 4 && use_slab_forward(VNX_F32, VNX_F32, d, 0))
+        kv.fused_slab_backward && msda_bwd_tile_queries(d, FwdCfg{0, 0}) == 4 && use_slab_forward(VNX_F32, VNX_F32, d, 0))
       return launch_bwd_slab<true>(value, shapes, lsi, raw_off, raw_logit, grad_out, out_or_grad_off, grad_logit, tile_summary, d, fa, stream);
   }
-  const FwdCfg c = pick_fwd_cfg(d, 0);
+  const FwdCfg c = pick_fwd_cfg(d, FwdCfg{0, 0});
 #define VNX_CASE(Q, W)                                                                                   \
   if (c.qpw == Q && c.wpb == W)                                                                          \
     return backward ? launch_bwd_fused_cfg<TV, TL, Q, W>(value, shapes, lsi, raw_off, raw_logit, grad_out, \
-                                                         out_or_grad_off, grad_logit, d, records, tile_summary, fa, stream) \
+                                                         out_or_grad_off, grad_logit, d, records, tile_summary, fa, kv.gv_units, stream) \
                     : launch_fwd_fused_cfg<TV, TL, Q, W>(value, shapes, lsi, raw_off, raw_logit,           \
                                                          out_or_grad_off, d, fa, stream);
   VNX_CASE(4, 1) VNX_CASE(4, 4) VNX_CASE(8, 4)
@@ -2249,13 +2233,13 @@ int msda_fused_d32(bool backward, int vdt, int ldt, const void* value, const int
                    const void* raw_off, const void* raw_logit, const void* grad_out, void* out_or_grad_off,
                    void* grad_logit, MsdaDims d, void* records, const void* reference, float* grad_reference,
                    int ref_dim, int ref_div, void* grad_value_f32, void* tile_summary, float* tile_loc, float* tile_attn,
-                   hipStream_t stream, int ref_f32) {
+                   const KernelVariant& kv, hipStream_t stream, int ref_f32) {
   // grad_value_f32: the fp32 target of the query-split levels' atomics (grad_value itself for fp32 values, the split
   // image for 16-bit ones), or null.  Backward: either `records` (record-fed grad_value kernel) or tile_summary +
-  // tile_loc + tile_attn (tile-fed one: queries per tile = msda_bwd_tile_queries(d, 0))
+  // tile_loc + tile_attn (tile-fed one: queries per tile = msda_bwd_tile_queries of the automatic configuration)
   const FusedArgs fa{reference, grad_reference, ref_dim, ref_div, backward ? static_cast<float*>(grad_value_f32) : nullptr,
                      backward ? tile_loc : nullptr, backward ? tile_attn : nullptr, ref_f32};
-#define VNX_ARGS backward, value, shapes, lsi, raw_off, raw_logit, grad_out, out_or_grad_off, grad_logit, d, records, tile_summary, fa, stream
+#define VNX_ARGS backward, value, shapes, lsi, raw_off, raw_logit, grad_out, out_or_grad_off, grad_logit, d, records, tile_summary, fa, kv, stream
   if (vdt == VNX_F32) return fused_dispatch<float, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_F32) return fused_dispatch<bf16_t, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_BF16) return fused_dispatch<bf16_t, bf16_t>(VNX_ARGS);

@@ -29,6 +29,7 @@
 // first stored (same owner, same lanes: no atomics).  Levels must be packed (checked on the device; capi.hip).
 // Reference semantics: ms_deform_im2col_cuda.cuh:87-159 (the scatter this replaces), :253-298 (index decode).
 #include "msda_d32_gvdirect_body.h"
+#include "msda_launchers.h"
 
 namespace vnx {
 namespace rec {

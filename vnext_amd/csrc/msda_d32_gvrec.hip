@@ -22,6 +22,7 @@
 //     image for 16-bit tensors; every grad_value row has exactly one owner.
 // Levels must be packed (checked on the device; see msda_d32_gv.hip / capi.hip).
 #include "msda_gv_common.h"
+#include "msda_launchers.h"
 
 namespace vnx {
 namespace rec {
@@ -687,7 +688,7 @@ static int launch_gvrec(const int64_t* shapes, const int64_t* lsi, const void* r
                         const void* grad_out, void* grad_value, const MsdaDims& d, int units_min,
                         int debug, int mode, float* split_image, hipStream_t stream) {
   // mode 0: per-unit sample selection (P == 4); 3: register slab, every unit scans its level;
-  // 1: the LDS-slab form (variants 425 / 420 select the last two)
+  // 1: the LDS-slab form (development build: KernelVariant::rec_form selects the last two)
   const int units_bound = msda_gvrec_units_bound(d, units_min, rec::kRowsMax);
   const int64_t blocks = ((int64_t(d.B) * units_bound + 1) & ~int64_t(1)) * d.M;     // (unit, batch) pairs: even (gv_decode_block)
   if (mode == 0 && d.P == 4 && d.L <= rec::kLevelsMax) {
@@ -716,14 +717,14 @@ static int launch_gvrec(const int64_t* shapes, const int64_t* lsi, const void* r
 
 // grad_value from the sample records; a no-op on the device when the levels are not packed.
 int msda_backward_gvrec_d32(int vdt, const int64_t* shapes, const int64_t* lsi, const void* records,
-                            const void* grad_out, void* grad_value, MsdaDims d, int variant, float* split_image,
-                            hipStream_t stream) {
+                            const void* grad_out, void* grad_value, MsdaDims d, const KernelVariant& kv,
+                            float* split_image, hipStream_t stream) {
   // every level is split into at least gv_units_min(d) units (2: 19 units per (b, head) at 360p = 760
   // workgroups <= the 768 resident at 3 per CU -- one round; 4: 960 workgroups, 39.2 vs 37.3 us)
-  const int units_min = gv_units_min(d, false, kernel_variant());
-  if (vdt == VNX_F32) return launch_gvrec<float>(shapes, lsi, records, grad_out, grad_value, d, units_min, (variant == 408 ? 1 : variant == 412 ? 5 : 0), (variant == 420 ? 1 : variant == 425 ? 3 : 0), split_image, stream);
-  if (vdt == VNX_BF16) return launch_gvrec<bf16_t>(shapes, lsi, records, grad_out, grad_value, d, units_min, (variant == 408 ? 1 : variant == 412 ? 5 : 0), (variant == 420 ? 1 : variant == 425 ? 3 : 0), split_image, stream);
-  if (vdt == VNX_F16) return launch_gvrec<f16_t>(shapes, lsi, records, grad_out, grad_value, d, units_min, (variant == 408 ? 1 : variant == 412 ? 5 : 0), (variant == 420 ? 1 : variant == 425 ? 3 : 0), split_image, stream);
+  const int units_min = gv_units_min(d, false, kv.gv_units);
+  if (vdt == VNX_F32) return launch_gvrec<float>(shapes, lsi, records, grad_out, grad_value, d, units_min, kv.rec_stamps, kv.rec_form, split_image, stream);
+  if (vdt == VNX_BF16) return launch_gvrec<bf16_t>(shapes, lsi, records, grad_out, grad_value, d, units_min, kv.rec_stamps, kv.rec_form, split_image, stream);
+  if (vdt == VNX_F16) return launch_gvrec<f16_t>(shapes, lsi, records, grad_out, grad_value, d, units_min, kv.rec_stamps, kv.rec_form, split_image, stream);
   set_error("msda_backward_gvrec_d32: unsupported dtype %d", vdt);
   return VNX_ERR_INVALID_ARGUMENT;
 }
@@ -771,8 +772,8 @@ split_levels_convert_kernel(const int64_t* __restrict__ shapes, const int64_t* _
 }
 
 int msda_split_levels_convert(int vdt, const int64_t* shapes, const int64_t* lsi, const float* image, void* grad_value,
-                              MsdaDims d, bool tiles, hipStream_t stream) {      // tiles: the grad_value path that ran
-  const int units_min = gv_units_min(d, tiles, kernel_variant());
+                              MsdaDims d, bool tiles, int gv_units, hipStream_t stream) {      // tiles: the grad_value path that ran
+  const int units_min = gv_units_min(d, tiles, gv_units);
   const int64_t n4 = int64_t(d.B) * d.S * d.M * 8;
   int64_t blocks = (n4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;

@@ -27,6 +27,7 @@
 // No records, no tags, no windows.  Levels must be packed (checked on the device).  Reference semantics:
 // ms_deform_im2col_cuda.cuh:87-159 (the scatter this replaces), :253-298 (index decode).
 #include "msda_gv_common.h"
+#include "msda_launchers.h"
 
 namespace vnx {
 namespace rec {
@@ -506,8 +507,8 @@ static int launch_gvtiles(const int64_t* shapes, const int64_t* lsi, const void*
 // a no-op on the device when the levels are not packed.  partials: msda_gvtiles_partial_bytes(d) bytes of scratch.
 int msda_backward_gvtiles_d32(int vdt, int ldt, const int64_t* shapes, const int64_t* lsi, const void* loc,
                               const void* attn, const void* summaries, const void* grad_out, void* grad_value,
-                              MsdaDims d, int tile_queries, float* partials, bool compact, hipStream_t stream) {
-  const int units_min = gv_units_min(d, true, kernel_variant());
+                              MsdaDims d, int tile_queries, int gv_units, float* partials, bool compact, hipStream_t stream) {
+  const int units_min = gv_units_min(d, true, gv_units);
 #define VNX_ARGS shapes, lsi, loc, attn, summaries, grad_out, grad_value, d, units_min, tile_queries, partials, int(compact), stream
   if (vdt == VNX_F32) return launch_gvtiles<float, float>(VNX_ARGS);
   if (vdt == VNX_BF16 && ldt == VNX_F32) return launch_gvtiles<bf16_t, float>(VNX_ARGS);

@@ -11,7 +11,7 @@
 // are reduced with cross-lane shuffles instead of shared memory + a serial
 // thread-0 loop (cuh:376-394), and the location/weight gradients are written
 // once, non-atomically.
-#include "vnx_common.h"
+#include "msda_launchers.h"
 
 namespace vnx {
 

@@ -130,15 +130,95 @@ __device__ __forceinline__ void stamp_begin(unsigned long long* s) {
 __device__ __forceinline__ void stamp_end(unsigned long long* s) {
   if (s && (threadIdx.x & 63) == 0) atomicMax(s + 2 * size_t(blockIdx.x) + 1, (unsigned long long)wall_clock64());
 }
-// Kernel variant of this call: 0 = automatic.  The PRODUCT library has no other value -- the forced configurations, the
-// archived kernels and the timing ablations (which return wrong results by construction) exist only in the development
-// build (-DVNX_DEV_VARIANTS, libvnext_hip_dev.so, include/vnext_hip_dev.h), where vnx_set_kernel_variant sets a
-// process-wide value that every entry point reads once.
+// ---- the kernel variant of a call ---------------------------------------------------------------------------------
+// The PRODUCT library has one: every field at its default, the choice made from the call's own sizes.  The forced
+// configurations, the archived kernels and the timing ablations (which return wrong results by construction) exist only in
+// the development build (-DVNX_DEV_VARIANTS, libvnext_hip_dev.so, include/vnext_hip_dev.h), where vnx_set_kernel_variant
+// sets a process-wide integer.  Each exported entry point reads it ONCE and hands the decoded struct, or
+// the fields a callee needs, down: a value set while a call runs cannot give a call that is half one configuration and half
+// another.  The numbers appear in decode_variant() and nowhere else.
+struct FwdCfg { int qpw; int wpb; };      // queries per wave, waves per workgroup of the forward / grad_loc kernel; qpw 0 = by size (pick_fwd_cfg)
+enum class GvPath { Auto, Records, Tiles };
+struct KernelVariant {
+  bool generic = false;              // the generic kernels, forward and backward
+  // the tuned forward (msda_d32.hip: launch_fwd_cfg)
+  FwdCfg fwd_cfg{0, 0};
+  bool fwd_prefetch = false;         // its phase 0 (off since the measurement beside launch_fwd_cfg)
+  int fwd_head_rot = 0;              // A/B record: which head runs on which XCD (the kernel's prefetch_rows >> 16)
+  bool fwd_lpr8 = false;             // 16-bit rows as 8 lanes x 8 B instead of 4 x 16 B
+  int slab_fwd = 0;                  // the slab forward (and the slab grad_loc kernel with it): +1 forced, -1 forbidden, 0 by size
+  bool large_slab = false;           // 16-bit values: the large slab
+  int tile_fwd = 0, tile_fwd_debug = 0;      // the archived LDS-staged forwards (tools/experiments/msda_tile/): 1 / 2, 0 = none; the first one's stamp mode
+  // the backward (capi.hip: plan_backward)
+  FwdCfg gl_cfg{0, 0};               // the grad_loc kernel's configuration
+  bool atomics_backward = false;     // the one-kernel backward whose grad_value goes through global atomics
+  // TIMING ABLATIONS: grad_loc / grad_attn alone; grad_value alone on the record- and tile-fed paths / on the self-decoding path
+  bool only_gl = false, only_gv = false, only_gv_direct = false;
+  int gv_units = 0;                  // grad_value units per level at least (gv_units_min); 0 = the path's own
+  GvPath gv_path = GvPath::Auto;     // record- or tile-fed grad_value whatever the query count
+  int rec_stamps = 0, rec_form = 0;  // the record-fed kernel's phase stamps (debug mode) and form (launch_gvrec's mode)
+  bool tile_copy = false;            // tile path: the grad_loc kernel leaves a compact copy of the locations / weights
+  bool fork = false, no_pair = false;      // self-decoding path: grad_value on the side stream, as VNX_MSDA_FORK asks; two launches where the paired kernel would run
+  int pair_order = -1;               // the paired kernel's role order; -1 = VNX_PAIR_ORDER
+  // the gather form of the grad_loc kernel where the slab form would run; the slab form of the fused one (measured, not the product path)
+  bool no_slab_backward = false, fused_slab_backward = false;
+  // the mask head's forward (mask_head.hip)
+  int mh_runs = 0;                   // runs per instance; 0 = by size (mask_head_runs)
+  bool mh_strip = false;             // the strip kernel of rounds 1 - 3
+};
 #ifdef VNX_DEV_VARIANTS
 extern std::atomic<int> g_kernel_variant;
-inline int kernel_variant() { return g_kernel_variant.load(std::memory_order_relaxed); }
+inline KernelVariant decode_variant(int variant) {
+  KernelVariant k;
+  // configuration numbers c of the forward / grad_loc kernel: 2..5 = 8, 4, 2, 1 queries per wave with 4 waves per workgroup,
+  // 12..15 the same with 1 wave; 20 + c / 40 + c wrap them (the forward's prefetch on / off); 60..68 take 13; others by size
+  auto cfg = [](int c) {
+    if (c >= 20 && c < 60) c = (c - 20) % 20;
+    if (c >= 60 && c < 69) c = 13;
+    if (c >= 2 && c <= 5) return FwdCfg{8 >> (c - 2), 4};
+    if (c >= 12 && c <= 15) return FwdCfg{8 >> (c - 12), 1};
+    return FwdCfg{0, 0};
+  };
+  k.generic = variant == 1;
+  if (variant < 100) {                                   // 2..69: the forward's and the grad_loc kernel's shape
+    k.fwd_cfg = cfg(variant);
+    k.fwd_prefetch = variant >= 20 && variant < 40;      // (40..59: off, as by default)
+    if (variant >= 60 && variant <= 68) k.fwd_head_rot = variant == 68 ? 14 : variant - 60;      // 14: the fixed head -> XCD map
+    k.fwd_lpr8 = variant == 69;
+  }
+  k.only_gl = variant >= 100 && variant < 200;           // 100 + c
+  k.atomics_backward = variant >= 300 && variant < 400;  // 300 + c
+  // the configuration number the backward carries; the slab grad_loc kernel stands in for configuration 0 only
+  const int c = variant < 100 ? variant : k.only_gl ? variant - 100 : 0;
+  k.gl_cfg = cfg(k.atomics_backward ? variant - 300 : c);
+  if (variant >= 200 && variant < 300)                   // 200 + units (1..16)
+    k.gv_units = variant - 200 < 1 ? 1 : (variant - 200 > 16 ? 16 : variant - 200);
+  k.only_gv = (variant >= 400 && variant < 430) || (variant > 431 && variant < 500);
+  k.rec_stamps = variant == 408 ? 1 : variant == 412 ? 5 : 0;      // shader-clock / wall-clock ticks
+  k.rec_form = variant == 420 ? 1 : variant == 425 ? 3 : 0;        // the LDS-slab form / the register slab without selection
+  // 430 / 431 force records / tiles; the numbers that name a record-fed kernel keep it
+  if (variant == 430 || k.rec_stamps || k.rec_form) k.gv_path = GvPath::Records;
+  if (variant == 431) k.gv_path = GvPath::Tiles;
+  k.fork = variant == 441;
+  k.only_gv_direct = variant == 442;
+  k.no_pair = variant == 444;
+  if (variant >= 445 && variant <= 447) k.pair_order = variant - 445;      // grad_value groups first / grad_loc groups first / alternating
+  k.tile_copy = variant == 510;
+  // 700..702 and 720 select an archived MSDA forward, 701..798 the mask head's runs and 799 its strip kernel: the two
+  // kernel families decode the same range, so 701 / 702 set a field of each (no test or tool runs both under one number)
+  if (variant >= 700 && variant <= 702) { k.tile_fwd = 1; k.tile_fwd_debug = variant - 700; }
+  if (variant == 720) k.tile_fwd = 2;
+  if (variant > 700 && variant < 799) k.mh_runs = variant - 700;
+  k.mh_strip = variant == 799;
+  k.slab_fwd = variant == 730 ? 1 : variant == 731 ? -1 : 0;
+  k.no_slab_backward = variant == 733 || c != 0;
+  k.fused_slab_backward = variant == 734;
+  k.large_slab = variant == 737;
+  return k;
+}
+inline KernelVariant kernel_variant() { return decode_variant(g_kernel_variant.load(std::memory_order_relaxed)); }
 #else
-constexpr int kernel_variant() { return 0; }
+constexpr KernelVariant kernel_variant() { return KernelVariant{}; }
 #endif
 
 struct MsdaDims {
@@ -146,9 +226,9 @@ struct MsdaDims {
 };
 
 // grad_value units: every level is split into at least this many.  Shared by the grad_loc kernel
-// (which tags every sample with the units it touches) and the grad_value kernels.  2 (development
-// build, variants 200+x: x).  `variant`: the value the entry point read (kernel_variant()).
-int gv_units_min(const MsdaDims& d, bool tiles, int variant);
+// (which tags every sample with the units it touches) and the grad_value kernels.  `forced`:
+// KernelVariant::gv_units of the variant the entry point read (0 = 2, or the tile-fed path's own).
+int gv_units_min(const MsdaDims& d, bool tiles, int forced);
 // Backward workspace of the record-fed path: [16-B sample records | 256-B aligned | 4-B unit ranges]
 inline size_t gv_unit_ids_offset(const MsdaDims& d) {
   const size_t n = size_t(d.B) * d.M * d.L * d.Lq * d.P;
