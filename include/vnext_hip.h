@@ -501,6 +501,45 @@ int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int w
                        int image_width, int out_height, int out_width, const void* offsets, void* arena,
                        long long arena_bytes, void* hip_stream);
 
+/*
+ * Linear sum assignment on the device: SeqFormer's Hungarian matching without a host round trip (lsap.hip).
+ * ADDITIVE: these two symbols were added without a change to any existing signature, so VNX_ABI_VERSION stays 17 and a
+ * binding written against the earlier ABI 17 keeps working; a binding that needs them looks the symbols up.
+ *
+ * One launch, one wave64 per problem, shortest augmenting paths with fp64 dual variables on fp32 costs (the algorithm
+ * of scipy.optimize.linear_sum_assignment, Crouse 2016): on the same cost matrix the result is scipy's whenever the
+ * optimum is unique; ties go to the lower index of the long side.  No atomics, fixed evaluation order: bit-identical
+ * run to run.  No workspace, no allocation, no synchronisation: capturable in a hipGraph.
+ * A problem with a non-finite cost entry gets -1 in every output slot (scipy raises there; a kernel cannot).
+ *
+ * vnx_seqformer_match: layers x clips problems, the cost block of each computed in the kernel from
+ *   logits [layers][clips][queries][classes] fp32, boxes [layers][clips][frames][queries][4] fp32 (cx, cy, w, h),
+ *   labels int64 [targets_total] and target_boxes fp32 [targets_total][frames][4] (the clips' targets back to back),
+ *   offsets int32 [clips + 1] (clip i owns targets offsets[i] .. offsets[i + 1] - 1), as
+ *     cost_bbox * || box - target ||_2 over the clip's frames * 4 coordinates
+ *     + cost_class * (pos - neg), the focal terms with alpha 0.25, gamma 2 and 1e-8 inside the logs
+ *     + cost_giou * (- mean over frames of GIoU), the targets clamped to [1e-7, 1] for this term only, 1e-7 on the hull
+ *   (HungarianMatcher.cost of SeqFormer, matcher.py:53-96).  Every target is assigned to one query.
+ *   Outputs int64 [layers][targets_total]: at a clip's offset its matched queries in ascending order (query_index) and
+ *   the target of each, counted from the clip's first (target_index) -- linear_sum_assignment's order with queries as
+ *   rows.  cost_out (may be null): fp32 [layers][clips][queries][targets_total]; the kernel writes the block it solved
+ *   (the columns of the clip's own targets) and leaves the other columns alone.
+ *   targets_max: an upper bound of the largest clip's target count, known on the host; it sizes the LDS.  A clip with
+ *   more targets than that, or a label outside [0, classes), gets -1.  VNX_ERR_UNSUPPORTED before any launch when
+ *   targets_max > queries or queries * targets_max * 4 + queries * 28 + targets_max * 12 bytes exceed 160 KB
+ *   (300 queries: 128 targets) -- the caller then matches on the host.  targets_total == 0 is a no-op.
+ * vnx_lsap_solve: batch problems on cost matrices in device memory, element (b, r, c) at
+ *   cost[b * batch_stride + r * row_stride + c * col_stride] (fp32, strides in elements), minimised, or maximised when
+ *   maximize != 0.  Outputs int64 [batch][min(rows, cols)]: row_index ascending and col_index of each -- what
+ *   linear_sum_assignment returns.  The same LDS limit on min(rows, cols) x max(rows, cols).
+ */
+int vnx_seqformer_match(const void* logits, const void* boxes, const void* labels, const void* target_boxes,
+                        const void* offsets, int layers, int clips, int frames, int queries, int classes,
+                        int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
+                        void* query_index, void* target_index, void* cost_out, void* hip_stream);
+int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long batch_stride, long long row_stride,
+                   long long col_stride, int maximize, void* row_index, void* col_index, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

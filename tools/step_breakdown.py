@@ -1,5 +1,8 @@
 """Where a SeqFormer training step spends its wall time (synchronising between phases, so the sum
-exceeds the pipelined step).  python tools/step_breakdown.py [--graph]"""
+exceeds the pipelined step).  python tools/step_breakdown.py [--graph] [--device-matching]
+
+--device-matching: the same rows with SeqFormer's device-side matcher (train.enable_device_matching), so the "matching"
+row and the step can be read side by side with the host matcher's."""
 import argparse
 import os
 import sys
@@ -14,12 +17,15 @@ from vnext_amd.registry import build_model, get_seqformer_cfg  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--graph", action="store_true")
+ap.add_argument("--device-matching", action="store_true")
 ap.add_argument("--steps", type=int, default=8)
 a = ap.parse_args()
 dev = "cuda:0"
 torch.manual_seed(0)
 model = build_model(get_seqformer_cfg(**{"MODEL.DEVICE": dev})).train()
 model.graph_training = a.graph
+if a.device_matching:
+    T.enable_device_matching(model)
 opt = T.build_optimizer(model)
 clips = T.synthetic_clips(1, 5, 360, 640, dev, seed=100, num_instances=4)
 for _ in range(3):
@@ -47,8 +53,12 @@ for _ in range(a.steps):
         x, srcs, hs, memory, logits, boxes, refs = model._run(clips, want_refs=True)
         feats = model._mask_features(srcs, memory)
     t = tick("trunk forward", t)
-    ind = model.criterion.matcher.match_all_layers(logits, boxes, targets)
-    t = tick("matching (cost + host LSAP)", t)
+    if a.device_matching:
+        ind = model.criterion.matcher.match_all_layers_device(logits, boxes, targets)
+        t = tick("matching (one kernel: cost + LSAP on the device)", t)
+    else:
+        ind = model.criterion.matcher.match_all_layers(logits, boxes, targets)
+        t = tick("matching (cost + host LSAP)", t)
     losses = model(clips)
     t = tick("full forward (all of the above again + mask head + criterion)", t)
     total = sum(losses.values())

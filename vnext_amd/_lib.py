@@ -16,6 +16,7 @@ DEV_LIB_PATH = os.path.join(_HERE, "lib", "libvnext_hip_dev.so")
 
 VNX_F32, VNX_F64, VNX_BF16, VNX_F16 = 0, 1, 2, 3
 VNX_OK = 0
+VNX_ERR_UNSUPPORTED = 2
 ABI_VERSION = 17
 MSDA_LEVELS_PACKED = 1
 MSDA_REF_F32 = 0x100       # or-ed into ref_dim of vnx_msda_fused_*: fp32 reference points beside 16-bit offsets / logits
@@ -65,6 +66,8 @@ SIGNATURES = {
     "vnx_window_attention_backward": (_i, [_i] + [_vp] * 10 + [_sz] + [_i] * 8 + [ctypes.c_float, _vp]),
     "vnx_mask_rle_measure": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp]),
     "vnx_mask_rle_write": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp, _ll, _vp]),
+    "vnx_seqformer_match": (_i, [_vp] * 5 + [_i] * 7 + [ctypes.c_float] * 3 + [_vp] * 4),
+    "vnx_lsap_solve": (_i, [_vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

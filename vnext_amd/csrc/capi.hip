@@ -746,6 +746,61 @@ int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int w
                               (hipStream_t)hip_stream);
 }
 
+// ---- linear sum assignment on the device (lsap.hip) --------------------------------------------------------------------
+int vnx_seqformer_match(const void* logits, const void* boxes, const void* labels, const void* target_boxes,
+                        const void* offsets, int layers, int clips, int frames, int queries, int classes,
+                        int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
+                        void* query_index, void* target_index, void* cost_out, void* hip_stream) {
+  const char* fn = "vnx_seqformer_match";
+  if (layers < 0 || clips < 0 || frames < 1 || queries < 1 || classes < 1 || targets_total < 0 || targets_max < 0 ||
+      targets_max > targets_total) {
+    vnx::set_error("%s: bad sizes (layers %d, clips %d, frames %d, queries %d, classes %d, targets %d, largest clip %d)", fn,
+                   layers, clips, frames, queries, classes, targets_total, targets_max);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (layers == 0 || clips == 0 || targets_total == 0) return VNX_OK;
+  if (targets_max > queries || !vnx::lsap_fits(targets_max, queries)) {
+    vnx::set_error("%s: %d targets of one clip against %d queries: more targets than queries, or more than the LDS of a "
+                   "CU holds", fn, targets_max, queries);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (int64_t(layers) * clips >= (int64_t(1) << 31) ||
+      int64_t(layers) * clips * queries * (int64_t(classes) > int64_t(frames) * 4 ? classes : frames * 4) >= (int64_t(1) << 40)) {
+    vnx::set_error("%s: %d x %d problems are outside what the kernel addresses", fn, layers, clips);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (!logits || !boxes || !labels || !target_boxes || !offsets || !query_index || !target_index) {
+    vnx::set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return vnx::seqformer_match_launch((const float*)logits, (const float*)boxes, (const int64_t*)labels,
+                                     (const float*)target_boxes, (const int32_t*)offsets, layers, clips, frames, queries,
+                                     classes, targets_total, targets_max, cost_class, cost_bbox, cost_giou,
+                                     (int64_t*)query_index, (int64_t*)target_index, (float*)cost_out,
+                                     (hipStream_t)hip_stream);
+}
+
+int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long batch_stride, long long row_stride,
+                   long long col_stride, int maximize, void* row_index, void* col_index, void* hip_stream) {
+  const char* fn = "vnx_lsap_solve";
+  if (batch < 0 || rows < 0 || cols < 0) {
+    vnx::set_error("%s: bad sizes (batch %d, %d x %d)", fn, batch, rows, cols);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (batch == 0 || rows == 0 || cols == 0) return VNX_OK;
+  if (!vnx::lsap_fits(rows < cols ? rows : cols, rows < cols ? cols : rows)) {
+    vnx::set_error("%s: a %d x %d problem does not fit the LDS of a CU", fn, rows, cols);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (!cost || !row_index || !col_index) {
+    vnx::set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return vnx::lsap_solve_launch((const float*)cost, batch, rows, cols, int64_t(batch_stride), int64_t(row_stride),
+                                int64_t(col_stride), maximize != 0, (int64_t*)row_index, (int64_t*)col_index,
+                                (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

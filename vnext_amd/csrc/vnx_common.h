@@ -115,6 +115,15 @@ int mask_rle_launch(bool write, int mode, const void* input, int masks, int heig
                     int image_height, int image_width, int out_height, int out_width, int64_t* lengths,
                     const int64_t* offsets, void* arena, int64_t arena_bytes, hipStream_t stream);
 
+// lsap.hip (linear sum assignment, one wave per problem; C entry points and their argument checks in capi.hip)
+bool lsap_fits(int n_short, int n_long);      // the problem's state fits the LDS of a CU
+int seqformer_match_launch(const float* logits, const float* boxes, const int64_t* labels, const float* tgt_boxes,
+                           const int32_t* offsets, int layers, int clips, int frames, int queries, int classes,
+                           int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
+                           int64_t* query_index, int64_t* target_index, float* cost_out, hipStream_t stream);
+int lsap_solve_launch(const float* cost, int batch, int rows, int cols, int64_t batch_stride, int64_t row_stride,
+                      int64_t col_stride, int maximize, int64_t* row_index, int64_t* col_index, hipStream_t stream);
+
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim
 // 64-bit slots; each workgroup leaves {its start, its last wave's end} there in constant-rate

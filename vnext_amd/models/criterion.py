@@ -11,9 +11,13 @@ mask head runs for), not a kernel.  Differences in *how*, not in *what*:
     host in ONE copy (`match_all_layers`); the reference matches inside the layer loop -> 6
     device syncs per step (deformable_detr.py / segmentation_condInst.py:146-147);
   * the per-frame GIoU loop (matcher.py:69-72) is one broadcast over the frame axis;
-  * `num_boxes` stays a tensor -- no `.item()` sync (deformable_detr.py:417-419).
+  * `num_boxes` stays a tensor -- no `.item()` sync (deformable_detr.py:417-419);
+  * opt-in (`match_all_layers_device`): cost and assignment of every (layer, clip) in ONE kernel on the device
+    (vnext_amd/csrc/lsap.hip), the indices never leave it -- no copy to the host, no scipy, no upload.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -76,6 +80,35 @@ def dice_loss(logits, targets, num_boxes):
     return (1 - (num + 1) / (den + 1)).sum() / num_boxes
 
 
+# What `HungarianMatcher.match_all_layers_device` returns and `SetCriterion.forward_all_layers` accepts in place of the host
+# `indices_list`: int64 device tensors [Ld * n] each (n = all targets of the batch), layer-major, clips in order, a clip's
+# pairs by ascending query.  lay / clip / qry index logits [Ld, N, Q, K]; tgt indexes the batch's concatenated targets.
+DeviceMatch = namedtuple("DeviceMatch", ["lay", "clip", "qry", "tgt"])
+
+_MATCH_CONSTANTS = {}
+
+
+def _match_constants(sizes, layers, device):
+    """What the host knows of a batch's matching from its target counts alone, as device tensors: clip offsets int32
+    [N + 1], and per pair (layer-major) the layer, the clip and the clip's first target.  Made by device-side fills (no
+    upload, so no blocking pageable copy) and kept per (target counts, layers, device), as `scale_tensor` keeps its
+    constants."""
+    key = (tuple(sizes), int(layers), str(device))
+    c = _MATCH_CONSTANTS.get(key)
+    if c is None:
+        if len(_MATCH_CONSTANTS) > 256:
+            _MATCH_CONSTANTS.clear()
+        start = [0]
+        for n in sizes:
+            start.append(start[-1] + n)
+        offsets = torch.cat([torch.full((1,), v, dtype=torch.int32, device=device) for v in start])
+        clip = torch.cat([torch.full((n,), i, dtype=torch.int64, device=device) for i, n in enumerate(sizes)])
+        first = torch.cat([torch.full((n,), start[i], dtype=torch.int64, device=device) for i, n in enumerate(sizes)])
+        lay = torch.arange(layers, dtype=torch.int64, device=device).repeat_interleave(start[-1], output_size=layers * start[-1])
+        c = _MATCH_CONSTANTS[key] = (offsets, lay, clip.repeat(layers), first)
+    return c
+
+
 class HungarianMatcher(nn.Module):
     """One-to-one assignment of queries to ground-truth *clip* instances; a box cost is the
     distance over all frames of the clip (matcher.py:53-96)."""
@@ -131,6 +164,45 @@ class HungarianMatcher(nn.Module):
         sizes = [len(t["labels"]) for t in targets]
         c = self.cost(logits, boxes, targets).cpu().numpy()
         return [self._solve(c[l], sizes) for l in range(c.shape[0])]
+
+    @torch.no_grad()
+    def match_all_layers_device(self, logits, boxes, targets):
+        """`match_all_layers` without leaving the device: logits [Ld, bs, Q, K], boxes [Ld, bs, nf, Q, 4] -> DeviceMatch.
+        One kernel computes the cost blocks and solves them (vnext_amd/ops/lsap.py); nothing is copied to the host and
+        nothing is uploaded.  The same pairs as `match_all_layers` wherever the optimum is unique beyond the fp32
+        rounding of the two cost evaluations.  A clip whose cost is not finite comes back with -1 indices: scipy
+        raises there, this path does not look (looking is a synchronisation).
+        A batch the kernel does not hold (a clip with more than ~128 targets at 300 queries, or more targets than
+        queries) is matched on the host and uploaded."""
+        from ..ops.lsap import LsapUnsupported, seqformer_match
+        sizes = [len(t["labels"]) for t in targets]
+        Ld = logits.shape[0]
+        dev = logits.device
+        if sum(sizes) == 0:                               # nobody has targets: nothing to launch
+            empty = torch.empty(0, dtype=torch.int64, device=dev)
+            return DeviceMatch(empty, empty, empty, empty)
+        offsets, lay, clip, first = _match_constants(sizes, Ld, dev)
+        labels = torch.cat([t["labels"] for t in targets]).to(dev)
+        nf = boxes.shape[-3]
+        tgt_boxes = torch.cat([t["boxes"] for t in targets]).reshape(len(labels), nf, 4).to(dev)
+        try:
+            qry, tgt = seqformer_match(logits, boxes, labels, tgt_boxes, offsets,
+                                       (self.cost_class, self.cost_bbox, self.cost_giou), max_targets=max(sizes))
+        except LsapUnsupported:
+            return self._upload(self.match_all_layers(logits, boxes, targets), sizes, dev)
+        return DeviceMatch(lay, clip, qry.flatten(), (tgt + first).flatten())
+
+    @staticmethod
+    def _upload(indices_list, sizes, device):
+        """host indices_list -> DeviceMatch (the stacked index tensors, one transfer each)"""
+        start = [0]
+        for n in sizes:
+            start.append(start[-1] + n)
+        lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind])
+        clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)])
+        qry = torch.cat([q for ind in indices_list for q, _ in ind])
+        tgt = torch.cat([j + start[i] for ind in indices_list for i, (_, j) in enumerate(ind)])   # into the concatenated targets
+        return DeviceMatch(lay.to(device), clip.to(device), qry.to(device), tgt.to(device))
 
 
 class SetCriterion(nn.Module):
@@ -211,33 +283,30 @@ class SetCriterion(nn.Module):
         `forward` for every decoder layer at once: logits [Ld, N, Q, K], boxes [Ld, N, T, Q, 4],
         masks [Ld * n, T, h, w] (the matched instances' mask logits, layer-major, clips in order,
         instances in matched order -- what the fused mask head returns), indices_list[layer][clip] =
-        (query idx, target idx).  Same names and numbers as `forward` with deep supervision; one set of
+        (query idx, target idx) on the host, or the `DeviceMatch` of `match_all_layers_device` (then nothing here
+        touches the host: same names, same numbers).  Same names and numbers as `forward` with deep supervision; one set of
         kernels instead of one per layer (the Hungarian matching assigns every target in every layer,
         so each layer contributes the same number n of instances)."""
         Ld, N, Q, K = logits.shape
         T = boxes.shape[2]
         dev = logits.device
-        num_boxes = torch.as_tensor([float(sum(len(t["labels"]) for t in targets))], device=dev)
+        num_boxes = torch.full((1,), float(sum(len(t["labels"]) for t in targets)), device=dev)   # a fill, not an upload
         world = 1
         if torch.distributed.is_available() and torch.distributed.is_initialized():
             torch.distributed.all_reduce(num_boxes)
             world = torch.distributed.get_world_size()
         num_boxes = torch.clamp(num_boxes / world, min=1)[0]
-        # stacked index tensors, built on the host, one transfer each
-        lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind]).to(dev)
-        clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)]).to(dev)
-        qry = torch.cat([q for ind in indices_list for q, _ in ind]).to(dev)
-        start = [0]
-        for t in targets:
-            start.append(start[-1] + len(t["labels"]))
-        tgt = torch.cat([j + start[i] for ind in indices_list for i, (_, j) in enumerate(ind)]).to(dev)   # into the concatenated targets
+        if isinstance(indices_list, DeviceMatch):      # matched on the device: the index tensors are there already
+            lay, clip, qry, tgt = indices_list
+        else:                                          # stacked index tensors, built on the host, one transfer each
+            lay, clip, qry, tgt = HungarianMatcher._upload(indices_list, [len(t["labels"]) for t in targets], dev)
         n = len(qry) // Ld
         names = [f"_{l}" for l in range(Ld - 1)] + [""]
         out = {}
         # labels (focal): mean over Q * Q = sum over Q
         all_labels = torch.cat([t["labels"] for t in targets]).to(dev)
         onehot = torch.zeros_like(logits)
-        onehot[lay, clip, qry, all_labels[tgt]] = 1
+        onehot[lay, clip, qry, all_labels[tgt]] = torch.ones((), dtype=logits.dtype, device=dev)   # a Python 1 is uploaded
         p = logits.sigmoid()
         ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
         p_t = p * onehot + (1 - p) * (1 - onehot)

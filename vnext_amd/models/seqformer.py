@@ -412,6 +412,7 @@ class SeqFormer(nn.Module):
         self.clip_matching, self.clip_length, self.clip_stride = m.CLIP_MATCHING, m.CLIP_LENGTH, m.CLIP_STRIDE
         self.graph_inference = True     # replay the inference trunk from a hipGraph (per clip shape)
         self.graph_training = False     # capture the training trunk's forward and backward (opt-in)
+        self.device_matching = False    # match queries to targets on the device: no host round trip in `losses` (opt-in)
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -542,13 +543,23 @@ class SeqFormer(nn.Module):
         else:
             x, srcs, hs, memory, logits, boxes, refs = self._run(batched_inputs, want_refs=True)
             feats = self._mask_features(srcs, memory)
+        return self._losses_after_trunk(targets, hs, logits, boxes, refs, feats)
+
+    def _losses_after_trunk(self, targets, hs, logits, boxes, refs, feats):
+        """Matching, the matched instances' masks and the criterion.  With `device_matching` nothing here copies to the
+        host or uploads (tests/test_device_matching.py runs it under torch's sync-debug mode)."""
         Ld, N, T = boxes.shape[:3]
-        indices_list = self.criterion.matcher.match_all_layers(logits, boxes, targets)
+        if self.device_matching and self.deep_supervision and logits.is_cuda:
+            # cost + assignment of every (layer, clip) in one kernel; the indices stay on the device
+            indices_list = self.criterion.matcher.match_all_layers_device(logits, boxes, targets)
+            lay, clip, qry = indices_list.lay, indices_list.clip, indices_list.qry
+        else:
+            indices_list = self.criterion.matcher.match_all_layers(logits, boxes, targets)
+            lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind]).to(self.device)
+            clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)]).to(self.device)
+            qry = torch.cat([q for ind in indices_list for q, _ in ind]).to(self.device)
         # the matched instances of every decoder layer, on every frame of their clip: one gather, one
         # controller call, one mask-head launch (the reference: a Python loop over layers x clips x frames)
-        lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind]).to(self.device)
-        clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)]).to(self.device)
-        qry = torch.cat([q for ind in indices_list for q, _ in ind]).to(self.device)
         params = self.detr.controller(hs[lay, clip, qry])                         # [Ld*n, 169]
         ref_xy = torch.stack([r[..., :2] for r in refs])                          # [Ld, N, T, Q, 2] pre-sigmoid
         sizes = torch.stack([scale_tensor(t["size"].flip(0).tolist(), self.device) for t in targets])   # [N, (w, h)]

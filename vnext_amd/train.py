@@ -296,6 +296,17 @@ def release_training_graphs(model) -> None:
         torch.cuda.synchronize()
 
 
+def enable_device_matching(model, on: bool = True) -> None:
+    """Opt in to SeqFormer's device-side Hungarian matching (`SeqFormer.device_matching`): cost and assignment of every
+    (decoder layer, clip) in one kernel, the indices never leave the device -- `losses` then runs from `prepare_targets`
+    to the loss dict without a device-to-host copy or a blocking upload.  The same pairs as the host matcher wherever the
+    optimum is unique beyond fp32 rounding of the cost.  Raises for a model without the switch (IDOL's simOTA matcher is a
+    different algorithm)."""
+    if not hasattr(model, "device_matching"):
+        raise ValueError("enable_device_matching: %s has no device_matching switch" % type(model).__name__)
+    model.device_matching = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
