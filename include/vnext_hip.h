@@ -540,6 +540,49 @@ int vnx_seqformer_match(const void* logits, const void* boxes, const void* label
 int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long batch_stride, long long row_stride,
                    long long col_stride, int maximize, void* row_index, void* col_index, void* hip_stream);
 
+/*
+ * The mask losses of both criteria -- sigmoid focal + dice over the matched instances' mask logits -- in one pass each
+ * way, the ground truth read in place (mask_loss.hip).  ADDITIVE: two symbols and one struct, no existing signature
+ * changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ *   logits fp32 [rows][frames][height][width] contiguous (one row = one matched instance of one decoder layer),
+ *   row_gt int64 [rows] on the device: the row's target, counted over the clips' targets laid back to back,
+ *   clips: per clip a bool / uint8 device tensor [n_i][frames][H_i][W_i] at image resolution, contiguous (0 / non-zero).
+ * The target of logit (r, f, y, x) is  masks[row_gt[r]][f][y * stride + stride / 2][x * stride + stride / 2]  where that
+ * pixel exists and 0 where it does not (segmentation_condInst.py / deformable_detr.py: slice [s/2::s], zero-pad to the
+ * canvas).  A row whose row_gt is outside [0, total) has target 0 everywhere.  With p = sigmoid(logit):
+ *   focal[r] = mean over the row of  alpha_t * ce * (1 - p_t)^gamma    (sigmoid_focal_loss before .sum() / num_boxes;
+ *                                                                       alpha < 0: no alpha_t, as there)
+ *   dice[r]  = 1 - (2 sum(p t) + 1) / (sum(p) + sum(t) + 1)            (dice_loss likewise)
+ *   row_sums [rows][3] = {sum(p t), sum(p), sum(t)}: what the backward needs; nothing of the logits' size is kept.
+ * vnx_mask_loss_clips is read on the host during the call and travels to the kernels by value: nothing is uploaded and
+ * the library keeps no pointer to it.  Clip i owns targets first[i] .. first[i + 1] - 1 (the last one up to total - 1);
+ * first[0] = 0; a clip without targets may have a null pointer.
+ * Forward: a workgroup sums one piece of VNX_MASK_LOSS_PIECE logits of a row into partial [rows][pieces][4] fp32
+ * (pieces = ceil(frames * height * width / VNX_MASK_LOSS_PIECE); caller-owned, 16-byte aligned, need not be zeroed), a
+ * second small launch adds a row's pieces in a fixed order.  Backward: one element-wise launch,
+ *   grad_logits = grad_focal[r] / M * dfocal/dlogit + grad_dice[r] * ddice/dp * p (1 - p),
+ * recomputed from logits and masks.  No atomics: bit-identical run to run.  No allocation, no synchronisation:
+ * capturable in a hipGraph.  rows == 0 is a no-op.  Any height, width, H_i, W_i and stride >= 1; 16-byte loads where
+ * width % 4 == 0 (logits) and stride == 4 with W_i % 16 == 0 (masks).
+ */
+#define VNX_MASK_LOSS_MAX_CLIPS 16
+#define VNX_MASK_LOSS_PIECE 4096
+typedef struct vnx_mask_loss_clips {
+  const void* masks[VNX_MASK_LOSS_MAX_CLIPS]; /* device pointer of clip i's [n_i][frames][H_i][W_i] bytes */
+  int height[VNX_MASK_LOSS_MAX_CLIPS];        /* H_i */
+  int width[VNX_MASK_LOSS_MAX_CLIPS];         /* W_i */
+  int first[VNX_MASK_LOSS_MAX_CLIPS];         /* index of clip i's first target among all targets */
+  int count;                                  /* clips in use, 0..VNX_MASK_LOSS_MAX_CLIPS */
+  int total;                                  /* targets of all clips */
+} vnx_mask_loss_clips;
+int vnx_mask_loss_forward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
+                          int height, int width, int stride, float alpha, float gamma, void* partial,
+                          size_t partial_bytes, void* focal, void* dice, void* row_sums, void* hip_stream);
+int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
+                           int height, int width, int stride, float alpha, float gamma, const void* row_sums,
+                           const void* grad_focal, const void* grad_dice, void* grad_logits, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

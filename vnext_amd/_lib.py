@@ -68,6 +68,8 @@ SIGNATURES = {
     "vnx_mask_rle_write": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp, _ll, _vp]),
     "vnx_seqformer_match": (_i, [_vp] * 5 + [_i] * 7 + [ctypes.c_float] * 3 + [_vp] * 4),
     "vnx_lsap_solve": (_i, [_vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp]),
+    "vnx_mask_loss_forward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp, _sz] + [_vp] * 4),
+    "vnx_mask_loss_backward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp] * 5),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -96,6 +98,16 @@ class TrackerConfig(ctypes.Structure):
                                   "long_match", "frame_weight", "temporal_weight")] + \
                [(k, ctypes.c_float) for k in ("nms_thr_pre", "nms_thr_post", "init_score_thr", "addnew_score_thr",
                                               "match_score_thr", "memo_momentum")]
+
+
+MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096      # VNX_MASK_LOSS_MAX_CLIPS, VNX_MASK_LOSS_PIECE
+
+
+class MaskLossClips(ctypes.Structure):
+    """`vnx_mask_loss_clips` of include/vnext_hip.h, field by field: read on the host during the call, handed to the
+    kernels by value."""
+    _fields_ = [("masks", _vp * MASK_LOSS_MAX_CLIPS), ("height", _i * MASK_LOSS_MAX_CLIPS),
+                ("width", _i * MASK_LOSS_MAX_CLIPS), ("first", _i * MASK_LOSS_MAX_CLIPS), ("count", _i), ("total", _i)]
 
 
 _lib = None          # the product library

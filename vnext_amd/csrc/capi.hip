@@ -801,6 +801,23 @@ int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long ba
                                 (hipStream_t)hip_stream);
 }
 
+// ---- mask losses, focal + dice (mask_loss.hip: the argument checks live beside the kernels' addressing limits) --------------
+int vnx_mask_loss_forward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
+                          int height, int width, int stride, float alpha, float gamma, void* partial,
+                          size_t partial_bytes, void* focal, void* dice, void* row_sums, void* hip_stream) {
+  return vnx::mask_loss_forward((const float*)logits, clips, (const int64_t*)row_gt, rows, frames, height, width, stride,
+                                alpha, gamma, (float*)partial, partial_bytes, (float*)focal, (float*)dice,
+                                (float*)row_sums, (hipStream_t)hip_stream);
+}
+
+int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
+                           int height, int width, int stride, float alpha, float gamma, const void* row_sums,
+                           const void* grad_focal, const void* grad_dice, void* grad_logits, void* hip_stream) {
+  return vnx::mask_loss_backward((const float*)logits, clips, (const int64_t*)row_gt, rows, frames, height, width, stride,
+                                 alpha, gamma, (const float*)row_sums, (const float*)grad_focal, (const float*)grad_dice,
+                                 (float*)grad_logits, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

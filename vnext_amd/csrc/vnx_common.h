@@ -124,6 +124,14 @@ int seqformer_match_launch(const float* logits, const float* boxes, const int64_
 int lsap_solve_launch(const float* cost, int batch, int rows, int cols, int64_t batch_stride, int64_t row_stride,
                       int64_t col_stride, int maximize, int64_t* row_index, int64_t* col_index, hipStream_t stream);
 
+// mask_loss.hip (focal + dice of the mask logits against the ground truth in place; argument checks there, C entry points in capi.hip)
+int mask_loss_forward(const float* logits, const vnx_mask_loss_clips* clips, const int64_t* row_gt, int rows, int frames,
+                      int height, int width, int stride, float alpha, float gamma, float* partial, size_t partial_bytes,
+                      float* focal, float* dice, float* row_sums, hipStream_t stream);
+int mask_loss_backward(const float* logits, const vnx_mask_loss_clips* clips, const int64_t* row_gt, int rows, int frames,
+                       int height, int width, int stride, float alpha, float gamma, const float* row_sums,
+                       const float* grad_focal, const float* grad_dice, float* grad_logits, hipStream_t stream);
+
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim
 // 64-bit slots; each workgroup leaves {its start, its last wave's end} there in constant-rate

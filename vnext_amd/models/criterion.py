@@ -14,6 +14,8 @@ mask head runs for), not a kernel.  Differences in *how*, not in *what*:
   * `num_boxes` stays a tensor -- no `.item()` sync (deformable_detr.py:417-419);
   * opt-in (`match_all_layers_device`): cost and assignment of every (layer, clip) in ONE kernel on the device
     (vnext_amd/csrc/lsap.hip), the indices never leave it -- no copy to the host, no scipy, no upload.
+  * opt-in (`fused_mask_loss`): focal + dice of the mask logits from one kernel pass each way (vnext_amd/csrc/mask_loss.hip),
+    the ground truth read in place -- no sliced / padded / gathered float copy, nothing [R, M]-sized kept for the backward.
 """
 from __future__ import annotations
 
@@ -212,6 +214,9 @@ class SetCriterion(nn.Module):
         super().__init__()
         self.num_classes, self.matcher, self.weight_dict, self.losses = num_classes, matcher, weight_dict, losses
         self.focal_alpha, self.mask_out_stride, self.num_frames = focal_alpha, mask_out_stride, num_frames
+        # mask losses from the fused kernel (vnext_amd/ops/mask_loss.py): the ground truth read in place, one pass each
+        # way (opt-in: train.enable_fused_mask_loss).  CUDA tensors only -- there is no fallback behind the switch
+        self.fused_mask_loss = False
 
     @staticmethod
     def _src_idx(indices):
@@ -258,6 +263,8 @@ class SetCriterion(nn.Module):
             src = torch.cat(list(src), 1)[0]
         nf, h, w = src.shape[1:]
         s = self.mask_out_stride
+        if self.fused_mask_loss:
+            return self._loss_masks_fused(src, targets, indices, num_boxes)
         picked = []
         for t, (_, j) in zip(targets, indices):
             m = t["masks"][j.to(t["masks"].device)]                           # [n_i, nf, H_i, W_i]
@@ -272,6 +279,21 @@ class SetCriterion(nn.Module):
             return {"loss_mask": zero, "loss_dice": zero}
         src, tgt = src.flatten(1), tgt.flatten(1)
         return {"loss_mask": sigmoid_focal_loss(src, tgt, num_boxes), "loss_dice": dice_loss(src, tgt, num_boxes)}
+
+    def _loss_masks_fused(self, src, targets, indices, num_boxes):
+        """`loss_masks` through the fused kernel: the matched targets are named by index (into the clips' targets laid
+        back to back) instead of gathered."""
+        from ..ops.mask_loss import mask_focal_dice
+        start, row_gt = 0, []
+        for t, (_, j) in zip(targets, indices):
+            row_gt.append(j.to(torch.int64) + start)
+            start += len(t["labels"])
+        row_gt = torch.cat(row_gt) if row_gt else torch.zeros(0, dtype=torch.int64)
+        if row_gt.numel() == 0:
+            zero = (src * 0).sum()
+            return {"loss_mask": zero, "loss_dice": zero}
+        focal, dice = mask_focal_dice(src, [t["masks"] for t in targets], row_gt.to(src.device), self.mask_out_stride)
+        return {"loss_mask": focal.sum() / num_boxes, "loss_dice": dice.sum() / num_boxes}
 
     # ---- all decoder layers in one pass ------------------------------------------------------
     def forward_all_layers(self, logits, boxes, masks, targets, indices_list, weighted=False):
@@ -328,7 +350,12 @@ class SetCriterion(nn.Module):
         g = giou_loss(box_cxcywh_to_xyxy(pred.flatten(0, 1)), box_cxcywh_to_xyxy(want.flatten(0, 1)))
         g = g.view(Ld, n * T).sum(1) / T / num_boxes
         # masks (focal + dice)
-        if n:
+        if n and self.fused_mask_loss:
+            from ..ops.mask_loss import mask_focal_dice
+            fm, dice = mask_focal_dice(masks, [t["masks"] for t in targets], tgt, self.mask_out_stride)   # [Ld*n] each
+            loss_mask = fm.view(Ld, n).sum(1) / num_boxes
+            loss_dice = dice.view(Ld, n).sum(1) / num_boxes
+        elif n:
             h, w = masks.shape[-2:]
             s_ = self.mask_out_stride
             gt = []

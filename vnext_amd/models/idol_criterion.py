@@ -195,6 +195,9 @@ class IDOLCriterion(nn.Module):
         super().__init__()
         self.num_classes, self.matcher, self.weight_dict, self.losses = num_classes, matcher, weight_dict, losses
         self.focal_alpha, self.mask_out_stride, self.num_frames = focal_alpha, mask_out_stride, num_frames
+        # mask losses from the fused kernel (vnext_amd/ops/mask_loss.py): the ground truth read in place, one pass each
+        # way (opt-in: train.enable_fused_mask_loss).  CUDA tensors only -- there is no fallback behind the switch
+        self.fused_mask_loss = False
 
     @staticmethod
     def _on_device(indices, device):
@@ -233,6 +236,8 @@ class IDOLCriterion(nn.Module):
             src = torch.cat(list(src), 1)[0]
         h, w = src.shape[-2:]
         s = self.mask_out_stride
+        if self.fused_mask_loss:
+            return self._loss_masks_fused(src, targets, indices)
         picked = []
         for i, (_, gt) in enumerate(indices):
             if len(gt):
@@ -246,6 +251,24 @@ class IDOLCriterion(nn.Module):
         assert src.shape == tgt.shape
         return {"loss_mask": sigmoid_focal_loss(src.flatten(1), tgt.flatten(1), n),
                 "loss_dice": dice_loss(src.flatten(1), tgt.flatten(1), n)}
+
+    def _loss_masks_fused(self, src, targets, indices):
+        """`loss_masks` through the fused kernel: the selected targets are named by index (into the images' targets laid
+        back to back) instead of gathered."""
+        from ..ops.mask_loss import mask_focal_dice
+        start, row_gt = 0, []
+        for i, (_, gt) in enumerate(indices):
+            if len(gt):
+                row_gt.append(gt.to(src.device, torch.int64) + start)
+            start += len(targets[i]["labels"])
+        if not row_gt:
+            zero = (src * 0).sum()
+            return {"loss_mask": zero, "loss_dice": zero}
+        row_gt = torch.cat(row_gt)
+        n = src.shape[0]
+        assert n == len(row_gt) and src.shape[1] == 1
+        focal, dice = mask_focal_dice(src, [t["masks"] for t in targets], row_gt, self.mask_out_stride)
+        return {"loss_mask": focal.sum() / n, "loss_dice": dice.sum() / n}
 
     def loss_reid(self, outputs, targets, ref_targets, indices, num_boxes):
         """outputs['pred_qd'] = {"contrast": sum over instances, "aux": sum over instances,
@@ -298,10 +321,15 @@ class IDOLCriterion(nn.Module):
         h, w = masks.shape[-2:]
         s_ = self.mask_out_stride
         gt_masks = []
-        for t in targets:
+        for t in (() if self.fused_mask_loss else targets):       # the fused kernel reads t["masks"] in place
             m = t["masks"][..., s_ // 2::s_, s_ // 2::s_]
             gt_masks.append(F.pad(m.to(masks.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
-        if sum(counts):
+        if sum(counts) and self.fused_mask_loss:
+            from ..ops.mask_loss import mask_focal_dice
+            fm, dice = mask_focal_dice(masks, [t["masks"] for t in targets], tgt, self.mask_out_stride)   # [sum n_l] each
+            loss_mask = per_layer(fm) / denom * present
+            loss_dice = per_layer(dice) / denom * present
+        elif sum(counts):
             gt_m = torch.cat(gt_masks).to(dev)[tgt].flatten(1)
             src = masks.flatten(1)
             pm = src.sigmoid()
