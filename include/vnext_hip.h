@@ -583,6 +583,54 @@ int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips,
                            int height, int width, int stride, float alpha, float gamma, const void* row_sums,
                            const void* grad_focal, const void* grad_dice, void* grad_logits, void* hip_stream);
 
+/*
+ * IDOL's simOTA matching and the contrastive positive / negative sets on the device (ota_match.hip).  ADDITIVE: three
+ * symbols, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * One launch, one workgroup (four wave64) per problem; det_problems detection problems first, then ref_problems
+ * selection problems.  All floating-point inputs fp32 and contiguous:
+ *   det_prob [det_problems][queries][classes], ref_prob [ref_problems][queries][classes]: class PROBABILITIES (the
+ *     caller applies the sigmoid, in the precision its host path does),
+ *   det_boxes [det_problems][queries][4], ref_boxes [ref_problems][queries][4]: (cx, cy, w, h),
+ *   target_boxes [targets_total][4] and labels int64 [targets_total]: the targets of every image back to back, the key
+ *     images' first; valid uint8 [targets_total - valid_first]: the flag of target t at valid[t - valid_first] (read by
+ *     selection problems only, whose targets start at valid_first or later),
+ *   problems int32 [det_problems + ref_problems][2]: (first target, target count) of each problem.
+ * A detection problem is the reference's simOTA matching of one (decoder layer, key image): cost = focal class term
+ * (alpha 0.25, gamma 2, 1e-8 inside the logs) + 3 * -GIoU (1e-7 on the hull) + 100 where the query centre is not in (box
+ * AND centre region, radius 2.5 / 32) + 10000 where it is in no box and no centre region; k of a target = the sum of its
+ * 10 largest IoUs, truncated, at least 1; the target takes its k cheapest queries; a query claimed by several targets
+ * keeps the cheapest; a target left without a query takes its cheapest one after 100000 was added to the rows already
+ * matched (in place, fp32), repeated until every target has a query.  A selection problem does the same on the targets
+ * whose valid flag is set, then a second time with the 100 largest IoUs on the cost the first pass left.  Equal values: the
+ * lower index.  No atomics, fixed evaluation order: bit-identical run to run.  No workspace, no allocation, no
+ * synchronisation.  A call that needs more than 64 KB of LDS (41 targets or more at 300 queries) raises the kernel's
+ * dynamic-LDS limit with hipFuncSetAttribute, once per device, the first time such a call is made there: make that call
+ * once outside a stream capture.  (Capture itself is not exercised by this library's tests.)
+ * out int32 [det_problems + ref_problems][out_stride], out_stride >= vnx_idol_match_out_words(targets_max, queries):
+ *   [0] status: 0 solved; 1 a non-finite cost or IoU; 2 the repair loop reached its bound (count + 8 rounds); 3 a label
+ *       outside [0, classes) or a (first, count) outside the arrays / above targets_max.  Not 0: no result, match on the host.
+ *   [1] n: the problem's targets (detection) / valid targets (selection)
+ *   detection: [2 .. 2 + queries) the lowest target assigned to the query or -1; then n words: the cheapest query
+ *     assigned to each target
+ *   selection: [2 .. 2 + n) the valid targets, counted from the problem's first; from word 2 + targets_max on, bytes
+ *     [targets_max][queries]: bit 0 = assigned by the first pass (positive), bit 1 = NOT assigned by the second (negative)
+ *   the rest of the stride is filled (-1 in index fields, 0 in the bytes).
+ * targets_max: an upper bound of the largest problem's count, known on the host; it sizes the LDS.  VNX_ERR_UNSUPPORTED
+ * before any launch -- the caller then matches on the host -- when
+ *   - with Qp = queries rounded up to a multiple of 4, targets_max * (5 Qp + 8) + 9 Qp + 4 queries + 576 bytes exceed
+ *     163 840 (the 160 KB of a CU).  vnx_idol_match_max_targets(queries) is the largest targets_max that fits: 105 at
+ *     300 queries (105 * 1508 + 4476 = 162 816 bytes; 106 would need 164 324);
+ *   - the device refuses the dynamic-LDS limit such a call needs;
+ *   - there are targets and queries < 10 (< 100 with selection problems).
+ */
+int vnx_idol_match_max_targets(int queries);
+int vnx_idol_match_out_words(int targets_max, int queries);
+int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_prob, const void* ref_boxes,
+                   const void* target_boxes, const void* labels, const void* valid, const void* problems,
+                   int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
+                   int targets_max, void* out, int out_stride, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

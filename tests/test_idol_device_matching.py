@@ -1,0 +1,790 @@
+"""IDOL's simOTA matching and contrastive sets on the device (vnext_amd/csrc/ota_match.hip, vnext_amd/ops/ota_match.py,
+OTAMatcher.match_all_layers_device, IDOL.device_matching).
+
+The yardstick is the host matcher (OTAMatcher, pos_neg_masks / select_pos_neg_masks) run in fp32 on the same fp32
+inputs, plus the reference's own indices in tests/golden/criterion_idol.npz.  Where fp32 rounding of the COST can
+legitimately flip a decision the problem is identified by the host arithmetic alone: `_restated_dynamic_k` below is
+dynamic_k_matching again, recording the margin of every comparison it makes.  A problem is left out of the index
+comparison when
+  * a dynamic-k sum lies within 1e-4 of the integer boundary that would change k, or
+  * two costs compared at a top-k boundary, or the two smallest of an arg-min (repair, loop, `matched`), differ by less
+    than 1e-5 + 16 ulp_fp32(the larger magnitude);
+at most 5 % of the problems of a test may be left out.  The geometric predicates get no margin: they are exact."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN_DIR, ROOT
+from vnext_amd.models.idol_criterion import (OTAMatcher, ota_cost, pos_neg_masks, sample_aux_masks,
+                                             select_pos_neg_masks)
+
+NAMES = ("vnx_idol_match", "vnx_idol_match_out_words", "vnx_idol_match_max_targets")
+DEV = "cuda:0"
+K_MARGIN = 1e-4
+
+
+# ---- the restatement with margins ------------------------------------------------------------------------------------
+def _close(a, b):
+    """two fp32 costs that rounding may order either way"""
+    big = np.float32(max(abs(float(a)), abs(float(b))))
+    return abs(float(a) - float(b)) < 1e-5 + 16 * float(np.spacing(big))
+
+
+def _two_smallest_close(values):
+    if len(values) < 2:
+        return False
+    v = np.sort(np.asarray(values, dtype=np.float32))
+    return _close(v[0], v[1])
+
+
+def _restated_dynamic_k(cost, iou, n_candidate_k):
+    """dynamic_k_matching on fp32 numpy arrays (cost is modified in place as there) -> (M [Q, n] float32, fragile):
+    fragile is True when some comparison of this run is within the margins of the module docstring.  Ties go to the
+    lower index (stable sort, first minimum)."""
+    assert cost.dtype == np.float32 and iou.dtype == np.float32
+    Q, n = cost.shape
+    fragile = False
+    M = np.zeros((Q, n), np.float32)
+    for g in range(n):
+        top = np.sort(iou[:, g])[::-1][:n_candidate_k]
+        s = np.float32(0)
+        for v in top:                         # largest first, fp32
+            s = np.float32(s + v)
+        k = max(int(s), 1)
+        s = float(s)
+        margin = 2.0 - s if s < 2.0 else min(s - np.floor(s), np.floor(s) + 1 - s)      # below 2, k is 1 either way
+        fragile |= margin < K_MARGIN
+        order = np.argsort(cost[:, g], kind="stable")
+        if k < Q:
+            fragile |= _close(cost[order[k - 1], g], cost[order[k], g])
+        M[order[:k], g] = 1
+    multi = M.sum(1) > 1
+
+    def keep_cheapest():
+        nonlocal fragile
+        for q in np.nonzero(multi)[0]:
+            fragile |= _two_smallest_close(cost[q])
+            keep = int(np.argmin(cost[q]))
+            M[q] = 0
+            M[q, keep] = 1
+    if multi.any():
+        keep_cheapest()
+    rounds = 0
+    while (M.sum(0) == 0).any():
+        rounds += 1
+        assert rounds < 100
+        cost[M.sum(1) > 0] += np.float32(100000.0)
+        for g in np.nonzero(M.sum(0) == 0)[0]:
+            fragile |= _two_smallest_close(cost[:, g])
+            M[int(np.argmin(cost[:, g])), g] = 1
+        if (M.sum(1) > 1).any():
+            keep_cheapest()
+    return M, bool(fragile), rounds
+
+
+def _restated_one(boxes, prob, gt, labels):
+    """OTAMatcher._one on host fp32 tensors -> (selected, gt_idx, matched, fragile, rounds of the repair loop)"""
+    cost, iou = ota_cost(boxes, prob, gt, labels)
+    cost, iou = cost.numpy().copy(), iou.numpy().copy()
+    M, fragile, rounds = _restated_dynamic_k(cost, iou, 10)
+    selected = M.sum(1) > 0
+    gt_idx = M[selected].argmax(1)
+    matched = []
+    for g in range(M.shape[1]):
+        rows = np.nonzero(M[:, g])[0]
+        fragile |= _two_smallest_close(cost[rows, g])
+        matched.append(int(rows[np.argmin(cost[rows, g])]))
+    return selected, gt_idx, np.asarray(matched, np.int64), fragile, rounds
+
+
+def _restated_selection(boxes, prob, gt, labels):
+    cost, iou = ota_cost(boxes, prob, gt, labels)
+    cost, iou = cost.numpy().copy(), iou.numpy().copy()
+    pos, f1, _ = _restated_dynamic_k(cost, iou, 10)
+    second, f2, _ = _restated_dynamic_k(cost, iou, 100)
+    return pos > 0, ~(second > 0), f1 or f2
+
+
+# ---- inputs ------------------------------------------------------------------------------------------------------------
+def _fixture():
+    g = dict(np.load(os.path.join(GOLDEN_DIR, "criterion_idol.npz")))
+    bz, Q, K, H, W, layers, C = (int(v) for v in g["cfg"])
+
+    def tg(name):
+        out = []
+        for i in range(bz):
+            t = {k: torch.from_numpy(g[f"{name}{i}.{k}"]) for k in ("labels", "boxes", "valid")}
+            t["boxes"] = t["boxes"].float()
+            out.append(t)
+        return out
+    logits = torch.stack([torch.from_numpy(g[f"l{l}.logits"]) for l in range(layers)]).float()
+    boxes = torch.stack([torch.from_numpy(g[f"l{l}.boxes"]) for l in range(layers)]).float()
+    return g, tg("det"), tg("ref"), logits, boxes, torch.from_numpy(g["ref_logits"]).float(), \
+        torch.from_numpy(g["ref_boxes"]).float(), (bz, Q, K, layers)
+
+
+COUNTS = (4, 9)
+SEEDS = range(10)
+
+
+NEAR = (0, 4, 12)
+
+
+def _model_sized_case(seed, near):
+    """Ld = 6, bz = 2, Q = 300, K = 40, 4 and 9 targets; the distributions of the criterion fixture's recipe (box centres
+    0.2 + 0.6 rand, sizes 0.1 + 0.3 rand, labels randint(K), the reference frame's boxes the key frame's + 0.03 randn,
+    one instance of an image with more than two absent from the reference frame), logits randn - 2, and `near` = 0, 4
+    or 12 queries placed near every box (box + 0.02 (r + 1) randn for the r-th of them, as the recipe does).  The
+    reference frame comes with near = 4, the recipe's own count: 10 seeds x 3 = 30 cases, 360 detection and 20
+    selection problems.  All fp32, on the host.
+    -> logits [Ld, bz, Q, K], boxes, det targets, ref_logits [bz, Q, K] | None, ref_boxes | None, ref targets | None"""
+    Ld, bz, Q, K = 6, 2, 300, 40
+    gen = torch.Generator().manual_seed(3 * seed + NEAR.index(near))
+
+    def rand_boxes(n):
+        return torch.cat([0.2 + 0.6 * torch.rand(n, 2, generator=gen), 0.1 + 0.3 * torch.rand(n, 2, generator=gen)], -1)
+    det, ref = [], []
+    for n in COUNTS:
+        b = rand_boxes(n)
+        labels = torch.randint(0, K, (n,), generator=gen)
+        valid = torch.ones(n, dtype=torch.bool)
+        valid[1] = False
+        det.append({"labels": labels, "boxes": b, "valid": torch.ones(n, dtype=torch.bool)})
+        ref.append({"labels": labels.clone(), "boxes": (b + 0.03 * torch.randn(n, 4, generator=gen)).clamp(0.02, 0.98),
+                    "valid": valid})
+
+    def preds(targets):
+        pb = torch.stack([rand_boxes(Q) for _ in range(bz)])
+        for i, t in enumerate(targets):
+            n = len(t["labels"])
+            for r in range(near):
+                pb[i, r * n:(r + 1) * n] = (t["boxes"] + 0.02 * (r + 1) * torch.randn(n, 4, generator=gen)).clamp(0.02, 0.98)
+        return torch.randn(bz, Q, K, generator=gen) - 2, pb
+    layers = [preds(det) for _ in range(Ld)]
+    ref_logits, ref_boxes = preds(ref) if near == 4 else (None, None)
+    return torch.stack([l for l, _ in layers]), torch.stack([b for _, b in layers]), det, ref_logits, ref_boxes, \
+        ref if near == 4 else None
+
+
+def _to(targets, device):
+    return [{k: v.to(device) for k, v in t.items()} for t in targets]
+
+
+def _host_answers(case):
+    """the restatement on every problem of a case -> (detection {(l, i): (selected, gt, matched, fragile, rounds)},
+    selection {i: (inst, pos, neg, fragile)})"""
+    logits, boxes, det, ref_logits, ref_boxes, ref = case
+    prob = logits.sigmoid()
+    d, s = {}, {}
+    for l in range(logits.shape[0]):
+        for i, t in enumerate(det):
+            d[l, i] = _restated_one(boxes[l, i], prob[l, i], t["boxes"], t["labels"])
+    ref_prob = None if ref is None else ref_logits.sigmoid()
+    for i, t in enumerate(ref or ()):
+        v = t["valid"]
+        s[i] = (torch.nonzero(v).flatten().numpy(),) + _restated_selection(ref_boxes[i], ref_prob[i], t["boxes"][v], t["labels"][v])
+    return d, s
+
+
+@pytest.fixture(scope="module")
+def cases():
+    out = []
+    with torch.no_grad():
+        for seed in SEEDS:
+            for near in NEAR:
+                case = _model_sized_case(seed, near)
+                out.append((case,) + _host_answers(case))
+    return out
+
+
+# ---- CPU -----------------------------------------------------------------------------------------------------------------
+def test_abi_17_gains_the_entry_points():
+    from vnext_amd import _lib
+    assert _lib.ABI_VERSION == 17
+    header = open(os.path.join(ROOT, "include", "vnext_hip.h")).read()
+    assert "#define VNX_ABI_VERSION 17" in header
+    declared = re.findall(r"\b(vnx_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] == "T"}
+    for name in NAMES:
+        assert name in _lib.SIGNATURES
+        assert name in declared
+        assert name in exported
+
+
+def test_cpu_tensors_are_refused():
+    from vnext_amd.ops.ota_match import idol_match
+    with pytest.raises(RuntimeError, match="Not implemented on the CPU"):
+        idol_match(torch.zeros(1, 12, 3), torch.zeros(1, 12, 4), torch.zeros(1, 4), torch.zeros(1, dtype=torch.int64),
+                   torch.tensor([[0, 1]], dtype=torch.int32), 1)
+
+
+def test_the_switch_and_its_setter():
+    import vnext_amd.models  # noqa: F401
+    from vnext_amd import train
+    from vnext_amd.registry import build_model, get_idol_cfg
+    tiny = {"MODEL.IDOL.ENC_LAYERS": 1, "MODEL.IDOL.DEC_LAYERS": 1, "MODEL.IDOL.NUM_OBJECT_QUERIES": 110,
+            "MODEL.IDOL.DIM_FEEDFORWARD": 64}
+    model = build_model(get_idol_cfg(**{"MODEL.DEVICE": "cpu", **tiny}))
+    assert model.device_matching is False
+    train.enable_device_matching(model)
+    assert model.device_matching is True
+    train.enable_device_matching(model, False)
+    assert model.device_matching is False
+    assert hasattr(OTAMatcher, "match_all_layers_device")
+
+
+def test_the_kernel_uses_no_scratch_and_spills_nothing(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "vnext_amd", "csrc", "ota_match.hip")
+    p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-I", os.path.dirname(src),
+                        "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "ota_match.s"),
+                        src], capture_output=True, text=True, check=True)
+    usage = {}
+    for block in re.split(r"remark: Function Name: ", p.stderr)[1:]:
+        name = block.split()[0]
+        usage[name] = {k: int(v) for k, v in re.findall(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+) \[-Rpass", block)}
+    kernels = {k: v for k, v in usage.items() if "idol_match_kernel" in k}
+    print(kernels)
+    assert len(kernels) == 1
+    for name, u in kernels.items():
+        assert u["ScratchSize"] == 0 and u["SGPRs Spill"] == 0 and u["VGPRs Spill"] == 0, (name, u)
+    text = open(tmp_path / "ota_match.s").read()
+    assert not re.search(r"^\s+scratch_", text, re.M)            # no scratch instruction
+    assert [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)] == [0]
+    assert not re.search(r"atomic", text)                        # no atomics: fixed evaluation order
+
+
+def test_the_sampling_loop_is_shared_and_draws_as_before():
+    """select_pos_neg_masks = pos_neg_masks + sample_aux_masks, with the generator's call sequence unchanged."""
+    import random
+    g, det, ref, logits, boxes, ref_logits, ref_boxes, _ = _fixture()
+    random.seed(5)
+    whole = select_pos_neg_masks(ref_boxes, ref_logits.sigmoid(), ref)
+    state = random.getstate()
+    random.seed(5)
+    split = sample_aux_masks(pos_neg_masks(ref_boxes, ref_logits.sigmoid(), ref))
+    assert random.getstate() == state
+    assert len(whole) == len(split) == 3
+    for a, b in zip(whole, split):
+        assert len(a) == len(b) == 4
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and torch.equal(x, y)
+
+
+def test_restatement_equals_the_host_matcher_and_leaves_out_few(cases):
+    """The restatement is dynamic_k_matching (same result on every problem, the fixture's included), and the margins
+    leave out at most 5 % of the chosen inputs."""
+    m = OTAMatcher()
+    problems = left_out = entered = 0
+    sel_problems = sel_left_out = 0
+    with torch.no_grad():
+        for case, d, s in cases:
+            logits, boxes, det, ref_logits, ref_boxes, ref = case
+            host, matched = m.match_all_layers(logits, boxes, det)
+            for (l, i), (selected, gt, mt, fragile, rounds) in d.items():
+                np.testing.assert_array_equal(host[l][i][0].numpy(), selected)
+                np.testing.assert_array_equal(host[l][i][1].numpy(), gt)
+                if l == logits.shape[0] - 1:
+                    np.testing.assert_array_equal(matched[i].numpy(), mt)
+                problems += 1
+                left_out += fragile
+                entered += rounds > 0
+            for i, (inst, pos, neg) in enumerate(() if ref is None else pos_neg_masks(ref_boxes, ref_logits.sigmoid(), ref)):
+                np.testing.assert_array_equal(inst.numpy(), s[i][0])
+                np.testing.assert_array_equal(pos.numpy(), s[i][1])
+                np.testing.assert_array_equal(neg.numpy(), s[i][2])
+                sel_problems += 1
+                sel_left_out += s[i][3]
+        # the fixture, against the reference's own indices
+        g, det, ref, logits, boxes, ref_logits, ref_boxes, (bz, Q, K, layers) = _fixture()
+        prob = logits.sigmoid()
+        for l in range(layers):
+            for i in range(bz):
+                if len(det[i]["labels"]) == 0:
+                    continue
+                selected, gt, mt, fragile, _ = _restated_one(boxes[l, i], prob[l, i], det[i]["boxes"], det[i]["labels"])
+                np.testing.assert_array_equal(selected, g[f"l{l}.sel{i}"])
+                np.testing.assert_array_equal(gt, g[f"l{l}.gt{i}"])
+                if l == layers - 1:
+                    np.testing.assert_array_equal(mt, g[f"matched{i}"])
+    print(f"detection: {problems} problems, {left_out} left out, repair loop entered in {entered}; "
+          f"selection: {sel_problems} problems, {sel_left_out} left out")
+    assert problems == 360 and sel_problems == 20
+    assert left_out + sel_left_out <= 0.05 * (problems + sel_problems)
+    assert left_out <= 0.05 * problems
+
+
+# ---- GPU -----------------------------------------------------------------------------------------------------------------
+class _NoHostMatcher(OTAMatcher):
+    """`match_all_layers_device` redoes a call on the host when the kernel refuses the sizes or sets a status word.  Where
+    a test expects the KERNEL's answer it matches with this class, whose host form raises: a fallback cannot pass for it."""
+
+    def match_all_layers(self, *a, **k):
+        raise AssertionError("the host matcher ran")
+
+
+def _device_match(logits, boxes, det, ref_logits=None, ref_boxes=None, ref=None, matcher=None):
+    """through the matcher's device method; no fallback to the host unless a plain OTAMatcher is handed in"""
+    m = matcher or _NoHostMatcher()
+    r = None if ref is None else (ref_boxes.to(DEV), ref_logits.to(DEV).sigmoid(), _to(ref, DEV))
+    return m.match_all_layers_device(logits.to(DEV), boxes.to(DEV), _to(det, DEV), ref=r)
+
+
+@pytest.mark.gpu
+def test_device_matching_equals_the_reference_indices():
+    g, det, ref, logits, boxes, ref_logits, ref_boxes, (bz, Q, K, layers) = _fixture()
+    assert [len(t["labels"]) for t in det] == [3, 0, 2]             # the empty image sits between two others
+    assert not bool(ref[0]["valid"].all())                          # one instance left the reference frame
+    indices, matched, sel = _device_match(logits, boxes, det, ref_logits, ref_boxes, ref)
+    for l in range(layers):
+        for i in range(bz):
+            s, gt = indices[l][i]
+            assert s.dtype == torch.bool and gt.dtype == torch.int64 and not s.is_cuda
+            np.testing.assert_array_equal(s.numpy(), g[f"l{l}.sel{i}"])
+            np.testing.assert_array_equal(gt.numpy(), g[f"l{l}.gt{i}"])
+    for i in range(bz):
+        assert matched[i].dtype == torch.int64
+        np.testing.assert_array_equal(matched[i].numpy(), g[f"matched{i}"])
+    want = pos_neg_masks(ref_boxes, ref_logits.sigmoid(), ref)
+    j = 0
+    for i in range(bz):
+        for x, y in zip(sel[i], want[i]):
+            assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
+        inst, pos, neg = sel[i]
+        for c in range(len(inst)):
+            label = g[f"item{j}.label"]
+            assert int(pos[:, c].sum()) == int(label.sum()) and int(neg[:, c].sum()) == int((label == 0).sum())
+            j += 1
+    assert j == int(g["n_items"])
+
+
+def _invariants(selected, gt, matched, n, Q):
+    """what holds for every problem, fragile or not, as far as a detection problem's outputs show it: they carry
+    gt_of_query and `matched`, not the matching M, so "gt_of_query is the LOWEST target assigned to the query" cannot be
+    checked here (a query is assigned to one target except where the repair loop added a second) -- it is held by the
+    exact comparison with the host matcher on the problems not left out"""
+    selected, gt, matched = selected.numpy(), gt.numpy(), matched.numpy()
+    assert selected.shape == (Q,) and gt.shape == (int(selected.sum()),) and matched.shape == (n,)
+    assert gt.min() >= 0 and gt.max() < n
+    assert set(gt.tolist()) == set(range(n))                        # every target has at least one query
+    gt_of_query = np.full(Q, -1)
+    gt_of_query[selected] = gt
+    for t in range(n):                                              # matched[t] is a query assigned to t
+        assert 0 <= matched[t] < Q and gt_of_query[matched[t]] == t
+
+
+def _op_args(case):
+    """a case's problems as the op takes them: the detection problems layer-major, then one selection problem per image"""
+    logits, boxes, det, ref_logits, ref_boxes, ref = case
+    Ld, bz, Q, K = logits.shape
+    sizes = [len(t["labels"]) for t in det]
+    first = sum(sizes)
+    table = [(0, sizes[0]), (sizes[0], sizes[1])] * Ld
+    if ref is not None:
+        table += [(first, sizes[0]), (first + sizes[0], sizes[1])]
+    every = det + (ref or [])
+    args = (logits.to(DEV).sigmoid().reshape(Ld * bz, Q, K), boxes.to(DEV).reshape(Ld * bz, Q, 4),
+            torch.cat([t["boxes"] for t in every]).to(DEV), torch.cat([t["labels"] for t in every]).to(DEV),
+            torch.tensor(table, dtype=torch.int32).to(DEV), max(sizes))
+    kw = {} if ref is None else dict(ref_prob=ref_logits.to(DEV).sigmoid(), ref_boxes=ref_boxes.to(DEV),
+                                     valid=torch.cat([t["valid"] for t in ref]).to(DEV), valid_first=first)
+    return args, kw
+
+
+@pytest.mark.gpu
+def test_device_matching_equals_the_host_matcher_at_model_size(cases):
+    from vnext_amd.ops.ota_match import idol_match, unpack
+    problems = left_out = sel_problems = sel_left_out = 0
+    for case, d, s in cases:
+        logits, boxes, det, ref_logits, ref_boxes, ref = case
+        Ld, bz, Q, K = logits.shape
+        args, kw = _op_args(case)
+        status, det_out, sel = unpack(idol_match(*args, **kw).cpu(), Ld * bz, Q, args[-1])
+        assert status.shape == (Ld * bz + len(s),) and not bool(status.any())
+        # the matcher's surface returns what the op returns (`matched` of the last layer only)
+        indices, matched, sel_m = _device_match(*case)
+        for l in range(Ld):
+            for i in range(bz):
+                assert torch.equal(indices[l][i][0], det_out[l * bz + i][0]) and torch.equal(indices[l][i][1], det_out[l * bz + i][1])
+        for i in range(bz):
+            assert torch.equal(matched[i], det_out[(Ld - 1) * bz + i][2])
+            for x, y in zip(sel_m[i] if s else (), sel[i] if s else ()):
+                assert torch.equal(x, y)
+        assert (sel_m is None) == (ref is None) and len(sel) == len(s)
+        for (l, i), (selected, gt, mt, fragile, _) in d.items():
+            got_sel, got_gt, got_mt = det_out[l * bz + i]
+            problems += 1
+            _invariants(got_sel, got_gt, got_mt, len(det[i]["labels"]), Q)
+            if fragile:
+                left_out += 1
+                continue
+            np.testing.assert_array_equal(got_sel.numpy(), selected)
+            np.testing.assert_array_equal(got_gt.numpy(), gt)
+            np.testing.assert_array_equal(got_mt.numpy(), mt)
+        for i in s:
+            inst, pos, neg = sel[i]
+            want_inst, want_pos, want_neg, fragile = s[i]
+            sel_problems += 1
+            np.testing.assert_array_equal(inst.numpy(), want_inst)
+            assert pos.shape == neg.shape == (Q, len(want_inst)) and pos.dtype == neg.dtype == torch.bool
+            # neg is the complement of a matching with at least one query per target and at most one target per query
+            # that the first pass did not leave with several; pos is such a matching itself
+            assert bool((~neg).any(0).all()) and bool(pos.any(0).all())
+            assert bool((pos.sum(1) <= 1).all())
+            if fragile:
+                sel_left_out += 1
+                continue
+            np.testing.assert_array_equal(pos.numpy(), want_pos)
+            np.testing.assert_array_equal(neg.numpy(), want_neg)
+    print(f"detection: {problems} problems, {left_out} left out; selection: {sel_problems} problems, {sel_left_out} left out")
+    assert problems == 360 and sel_problems == 20
+    assert left_out + sel_left_out <= 0.05 * (problems + sel_problems)
+
+
+# ---- crowded targets: the repair loop ----------------------------------------------------------------------------------
+def _crowded_case(seed, n=6, Q=300, K=40, Ld=6):
+    """six boxes of about the same size around one point and no query placed near them: the boxes claim the same few
+    queries, some box loses all of its queries and the repair loop runs (the model-sized inputs enter it once in 360)"""
+    gen = torch.Generator().manual_seed(1000 + seed)
+    centre = 0.3 + 0.4 * torch.rand(1, 2, generator=gen)
+    b = torch.cat([centre + 0.02 * torch.randn(n, 2, generator=gen), 0.2 + 0.05 * torch.rand(n, 2, generator=gen)], -1)
+    det = [{"labels": torch.randint(0, K, (n,), generator=gen), "boxes": b, "valid": torch.ones(n, dtype=torch.bool)}]
+    pb = torch.cat([0.2 + 0.6 * torch.rand(Ld, 1, Q, 2, generator=gen), 0.1 + 0.3 * torch.rand(Ld, 1, Q, 2, generator=gen)], -1)
+    return torch.randn(Ld, 1, Q, K, generator=gen) - 2, pb, det
+
+
+@pytest.fixture(scope="module")
+def crowded():
+    out = []
+    with torch.no_grad():
+        for seed in range(10):
+            logits, pb, det = _crowded_case(seed)
+            prob = logits.sigmoid()
+            answers = [_restated_one(pb[l, 0], prob[l, 0], det[0]["boxes"], det[0]["labels"]) for l in range(logits.shape[0])]
+            selection = _restated_selection(pb[-1, 0], prob[-1, 0], det[0]["boxes"], det[0]["labels"])
+            out.append((logits, pb, det, answers, selection))
+    return out
+
+
+def test_crowded_cases_enter_the_repair_loop(crowded):
+    """what the GPU test below relies on: the restatement is the host matcher here too, and the repair loop is entered in
+    at least 5 problems that the margins do not leave out (the +100000 puts the costs on a 2^-7 grid, so problems that
+    repair are left out more often than others: no cap on the share here, the model-sized test holds that)"""
+    m = OTAMatcher()
+    entered = fragile_count = 0
+    with torch.no_grad():
+        for logits, pb, det, answers, selection in crowded:
+            host, matched = m.match_all_layers(logits, pb, det)
+            for l, (selected, gt, mt, fragile, rounds) in enumerate(answers):
+                np.testing.assert_array_equal(host[l][0][0].numpy(), selected)
+                np.testing.assert_array_equal(host[l][0][1].numpy(), gt)
+                entered += rounds > 0 and not fragile
+                fragile_count += fragile
+            np.testing.assert_array_equal(matched[0].numpy(), answers[-1][2])
+            (inst, pos, neg), = pos_neg_masks(pb[-1], logits[-1].sigmoid(), det)
+            np.testing.assert_array_equal(pos.numpy(), selection[0])
+            np.testing.assert_array_equal(neg.numpy(), selection[1])
+    print(f"crowded: repair loop entered in {entered} problems that are compared, {fragile_count} of 60 left out")
+    assert entered >= 5
+
+
+@pytest.mark.gpu
+def test_device_matching_repairs_as_the_host_matcher_does(crowded):
+    compared = 0
+    for logits, pb, det, answers, selection in crowded:
+        Q = logits.shape[2]
+        indices, matched, sel = _device_match(logits, pb, det, logits[-1], pb[-1], det)
+        for l, (selected, gt, mt, fragile, rounds) in enumerate(answers):
+            got_sel, got_gt = indices[l][0]
+            _invariants(got_sel, got_gt, matched[0] if l == len(answers) - 1 else torch.from_numpy(_matched_of(got_sel, got_gt)),
+                        len(det[0]["labels"]), Q)
+            if fragile:
+                continue
+            compared += 1
+            np.testing.assert_array_equal(got_sel.numpy(), selected)
+            np.testing.assert_array_equal(got_gt.numpy(), gt)
+            if l == len(answers) - 1:
+                np.testing.assert_array_equal(matched[0].numpy(), mt)
+        inst, pos, neg = sel[0]
+        assert bool((~neg).any(0).all()) and bool(pos.any(0).all()) and bool((pos.sum(1) <= 1).all())
+        if not selection[2]:
+            compared += 1
+            np.testing.assert_array_equal(pos.numpy(), selection[0])
+            np.testing.assert_array_equal(neg.numpy(), selection[1])
+    print(f"crowded: {compared} of 70 problems compared")
+    assert compared >= 50
+
+
+def _matched_of(selected, gt):
+    """some assigned query per target, where the matcher's surface does not return `matched` (layers before the last)"""
+    q = np.nonzero(selected.numpy())[0]
+    return np.asarray([q[np.nonzero(gt.numpy() == t)[0][0]] for t in range(int(gt.max()) + 1)], np.int64)
+
+
+@pytest.mark.gpu
+def test_edges():
+    m = OTAMatcher()
+    g = torch.Generator().manual_seed(3)
+    Q, K = 120, 6
+
+    def empty():
+        return {"labels": torch.zeros(0, dtype=torch.int64), "boxes": torch.zeros(0, 4), "valid": torch.zeros(0, dtype=torch.bool)}
+    logits, boxes = torch.randn(2, 2, Q, K, generator=g), torch.rand(2, 2, Q, 4, generator=g) * 0.5 + 0.2
+    ref_logits, ref_boxes = torch.randn(2, Q, K, generator=g), torch.rand(2, Q, 4, generator=g) * 0.5 + 0.2
+    # no targets anywhere
+    indices, matched, sel = _device_match(logits, boxes, [empty(), empty()], ref_logits, ref_boxes, [empty(), empty()])
+    for layer in indices:
+        for s_, gt in layer:
+            assert s_.shape == (Q,) and not bool(s_.any()) and gt.numel() == 0 and gt.dtype == torch.int64
+    assert all(x.numel() == 0 and x.dtype == torch.int64 for x in matched)
+    for inst, pos, neg in sel:
+        assert inst.numel() == 0 and pos.shape == neg.shape == (Q, 0)
+    # all reference targets invalid
+    det = [{"labels": torch.tensor([1, 2]), "boxes": torch.tensor([[0.4, 0.4, 0.2, 0.2], [0.6, 0.5, 0.3, 0.2]]),
+            "valid": torch.ones(2, dtype=torch.bool)}, empty()]
+    ref = [dict(det[0], valid=torch.zeros(2, dtype=torch.bool)), empty()]
+    indices, matched, sel = _device_match(logits, boxes, det, ref_logits, ref_boxes, ref)
+    host, host_matched = m.match_all_layers(logits, boxes, det)
+    want = pos_neg_masks(ref_boxes, ref_logits.sigmoid(), ref)
+    for l in range(2):
+        for i in range(2):
+            assert torch.equal(indices[l][i][0], host[l][i][0]) and torch.equal(indices[l][i][1], host[l][i][1])
+    for i in range(2):
+        assert torch.equal(matched[i], host_matched[i])
+        assert sel[i][0].numel() == 0 and sel[i][1].shape == want[i][1].shape == (Q, 0)
+    # more targets than the kernel's LDS holds: the device method returns the host result
+    from vnext_amd.ops.ota_match import OtaUnsupported, idol_match
+    n, big_q = 110, 300                 # 105 targets fit at 300 queries (test_the_cap_...)
+    many = [{"labels": torch.randint(0, K, (n,), generator=g),
+             "boxes": torch.cat([0.2 + 0.6 * torch.rand(n, 2, generator=g), 0.05 + 0.2 * torch.rand(n, 2, generator=g)], -1),
+             "valid": torch.ones(n, dtype=torch.bool)}]
+    big_logits, big_boxes = torch.randn(1, 1, big_q, K, generator=g), torch.rand(1, 1, big_q, 4, generator=g) * 0.5 + 0.2
+    with pytest.raises(OtaUnsupported):
+        idol_match(big_logits[0].to(DEV).sigmoid(), big_boxes[0].to(DEV), many[0]["boxes"].to(DEV), many[0]["labels"].to(DEV),
+                   torch.tensor([[0, n]], dtype=torch.int32).to(DEV), n)
+    indices, matched, sel = _device_match(big_logits, big_boxes, many, matcher=OTAMatcher())
+    host, host_matched = m.match_all_layers(big_logits, big_boxes, many)
+    assert torch.equal(indices[0][0][0], host[0][0][0]) and torch.equal(indices[0][0][1], host[0][0][1])
+    assert torch.equal(matched[0], host_matched[0]) and sel is None
+    # the selection with fewer than 100 queries raises as the host form does
+    small_q = 60
+    with pytest.raises(RuntimeError) as host_error:
+        pos_neg_masks(ref_boxes[:, :small_q], ref_logits[:, :small_q].sigmoid(), [dict(det[0]), empty()])
+    with pytest.raises(RuntimeError) as device_error:
+        _device_match(logits[:, :, :small_q], boxes[:, :, :small_q], det, ref_logits[:, :small_q], ref_boxes[:, :small_q],
+                      [dict(det[0]), empty()], matcher=OTAMatcher())
+    assert type(device_error.value) is type(host_error.value) and str(device_error.value) == str(host_error.value)
+
+
+# ---- the cap ---------------------------------------------------------------------------------------------------------------
+CAP_300 = 105
+
+
+def _header_lds_bytes(n, Q):
+    """the formula the header states: n (5 Qp + 8) + 9 Qp + 4 Q + 576 with Qp = Q rounded up to a multiple of 4"""
+    Qp = (Q + 3) // 4 * 4
+    return n * (5 * Qp + 8) + 9 * Qp + 4 * Q + 576
+
+
+def test_the_cap_is_what_the_header_says():
+    """the header's formula on both sides of the boundary, the library's own answer, and the figure in the documents"""
+    from vnext_amd.ops.ota_match import max_targets
+    lds = 160 * 1024
+    assert _header_lds_bytes(CAP_300, 300) == 162816 <= lds < _header_lds_bytes(CAP_300 + 1, 300) == 164324
+    assert max_targets(300) == CAP_300
+    for Q in (100, 110, 120, 299, 300, 301, 512, 900):
+        cap = max_targets(Q)
+        assert _header_lds_bytes(cap, Q) <= lds < _header_lds_bytes(cap + 1, Q), Q
+    assert CAP_300 >= 32                                   # what the feature promises at 300 queries
+    header = open(os.path.join(ROOT, "include", "vnext_hip.h")).read()
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "%d at\n *     300 queries" % CAP_300 in header and "n (5 Qp + 8) + 9 Qp + 4 Q + 576" in design
+    assert "The cap is %d targets at `Q = 300`" % CAP_300 in design
+    # where the kernel's LDS goes above 64 KB and has to be asked for
+    assert _header_lds_bytes(40, 300) <= 64 * 1024 < _header_lds_bytes(41, 300)
+
+
+def _big_case(seed, n=CAP_300, Q=300, K=40):
+    """as many targets as fit: small boxes over the whole image, two queries placed on every box, four in five valid on
+    the reference frame (which here is the key frame's own prediction)"""
+    g = torch.Generator().manual_seed(2000 + seed)
+    b = torch.cat([0.1 + 0.8 * torch.rand(n, 2, generator=g), 0.05 + 0.1 * torch.rand(n, 2, generator=g)], -1)
+    det = [{"labels": torch.randint(0, K, (n,), generator=g), "boxes": b, "valid": torch.rand(n, generator=g) > 0.2}]
+    pb = torch.cat([0.1 + 0.8 * torch.rand(1, 1, Q, 2, generator=g), 0.05 + 0.15 * torch.rand(1, 1, Q, 2, generator=g)], -1)
+    pb[0, 0, :2 * n] = (b.repeat(2, 1) + 0.01 * torch.randn(2 * n, 4, generator=g)).clamp(0.02, 0.98)
+    return torch.randn(1, 1, Q, K, generator=g) - 2, pb, det
+
+
+@pytest.mark.gpu
+def test_a_problem_at_the_cap_is_answered_by_the_kernel():
+    """105 targets at 300 queries: 159 KB of dynamic LDS, the path above 64 KB (hipFuncSetAttribute, then one workgroup
+    with nearly the whole LDS of a CU).  The kernel answers (the matcher's host form raises), the invariants hold on every
+    problem and the problems the margins do not leave out equal the host matcher; one target more is refused before any
+    launch.  No cap on the share left out: 105 boxes crowd 300 queries, and most of these problems repair."""
+    from vnext_amd.ops.ota_match import OtaUnsupported, idol_match
+    compared = 0
+    for seed in range(3):
+        logits, pb, det = _big_case(seed)
+        n, Q = len(det[0]["labels"]), logits.shape[2]
+        assert n == CAP_300
+        indices, matched, sel = _device_match(logits, pb, det, logits[-1], pb[-1], det)      # _NoHostMatcher
+        prob = logits.sigmoid()
+        selected, gt, mt, fragile, rounds = _restated_one(pb[0, 0], prob[0, 0], det[0]["boxes"], det[0]["labels"])
+        _invariants(indices[0][0][0], indices[0][0][1], matched[0], n, Q)
+        if not fragile:
+            compared += 1
+            np.testing.assert_array_equal(indices[0][0][0].numpy(), selected)
+            np.testing.assert_array_equal(indices[0][0][1].numpy(), gt)
+            np.testing.assert_array_equal(matched[0].numpy(), mt)
+        v = det[0]["valid"]
+        want_pos, want_neg, sel_fragile = _restated_selection(pb[0, 0], prob[0, 0], det[0]["boxes"][v], det[0]["labels"][v])
+        inst, pos, neg = sel[0]
+        np.testing.assert_array_equal(inst.numpy(), torch.nonzero(v).flatten().numpy())
+        assert bool((~neg).any(0).all()) and bool(pos.any(0).all()) and bool((pos.sum(1) <= 1).all())
+        if not sel_fragile:
+            compared += 1
+            np.testing.assert_array_equal(pos.numpy(), want_pos)
+            np.testing.assert_array_equal(neg.numpy(), want_neg)
+        print(f"cap, seed {seed}: detection left out {fragile} (repair rounds {rounds}), selection left out {sel_fragile}")
+    assert compared >= 1
+    logits, pb, det = _big_case(0, n=CAP_300 + 1)
+    with pytest.raises(OtaUnsupported):
+        idol_match(logits[0].to(DEV).sigmoid(), pb[0].to(DEV), det[0]["boxes"].to(DEV), det[0]["labels"].to(DEV),
+                   torch.tensor([[0, CAP_300 + 1]], dtype=torch.int32).to(DEV), CAP_300 + 1)
+
+
+@pytest.mark.gpu
+def test_sixteen_bit_logits_under_autocast_give_the_host_paths_results(cases):
+    """match_all_layers casts 16-bit logits to fp32 before the sigmoid, `losses` hands the selection a sigmoid computed
+    in the logits' own type: the device path is given the same tensors and makes the same casts."""
+    m = OTAMatcher()
+    checked = total = 0
+    for case, _, _ in [c for c in cases if c[0][5] is not None][:3]:
+        logits, boxes, det, ref_logits, ref_boxes, ref = case
+        l16, b32 = logits.to(DEV, torch.bfloat16), boxes.to(DEV)
+        r16, rb = ref_logits.to(DEV, torch.bfloat16), ref_boxes.to(DEV)
+        det_d, ref_d = _to(det, DEV), _to(ref, DEV)
+        host, host_matched = m.match_all_layers(l16, b32, det_d)
+        want = pos_neg_masks(rb, r16.sigmoid(), ref_d)
+        indices, matched, sel = _NoHostMatcher().match_all_layers_device(l16, b32, det_d, ref=(rb, r16.sigmoid(), ref_d))
+        # the yardstick's own margins, on the tensors the host path sees
+        prob = l16.float().sigmoid().cpu()
+        ref_prob = r16.sigmoid().float().cpu()
+        for l in range(logits.shape[0]):
+            for i, t in enumerate(det):
+                total += 1
+                if _restated_one(boxes[l, i], prob[l, i], t["boxes"], t["labels"])[3]:
+                    continue
+                checked += 1
+                assert torch.equal(indices[l][i][0], host[l][i][0]) and torch.equal(indices[l][i][1], host[l][i][1])
+                if l == logits.shape[0] - 1:
+                    assert torch.equal(matched[i], host_matched[i])
+        for i, t in enumerate(ref):
+            v = t["valid"]
+            total += 1
+            if _restated_selection(ref_boxes[i], ref_prob[i], t["boxes"][v], t["labels"][v])[2]:
+                continue
+            checked += 1
+            for x, y in zip(sel[i], want[i]):
+                assert torch.equal(x, y)
+    print(f"bf16: {checked} of {total} problems compared")
+    assert total == 42 and total - checked <= 0.05 * total
+
+
+@pytest.mark.gpu
+def test_two_calls_are_bit_identical_and_the_op_does_not_synchronise(cases):
+    from vnext_amd.ops.ota_match import idol_match
+    case, _, _ = cases[4]                 # (seed 1, 4 queries near every box): with a reference frame
+    assert case[5] is not None
+    Ld, bz = case[0].shape[:2]
+    args, kw = _op_args(case)
+    a = idol_match(*args, **kw)           # warm-up: the library is loaded, the kernel's LDS attribute asked for
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        b = idol_match(*args, **kw)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert a.is_cuda and a.dtype == torch.int32 and a.shape[0] == Ld * bz + bz
+    assert torch.equal(a, b)
+    assert not bool(a[:, 0].any())        # every status word 0
+
+
+def _step(model, pairs):
+    """one seeded forward + backward -> (loss dict, gradients of the controller, class_embed and the reid head)"""
+    import random
+    model.zero_grad(set_to_none=True)
+    torch.manual_seed(1)
+    random.seed(1)
+    losses = model(pairs)
+    sum(losses.values()).backward()
+    grads = {n: p.grad.detach().clone() for n, p in model.named_parameters()
+             if p.grad is not None and (".controller." in n or "class_embed" in n or "reid_embed_head" in n)}
+    model.zero_grad(set_to_none=True)
+    return {k: v.detach().clone() for k, v in losses.items()}, grads
+
+
+@pytest.mark.gpu
+def test_model_step_is_the_same_with_device_matching():
+    """test_device_matching.py's rule and reasoning: the same indices give the same autograd graph; what is left is the
+    order of ATen's atomic adds, which two host-path runs differ by as well.  The device path is allowed ten times that
+    host-against-host difference, with a floor of 1e-6 * max|tensor|."""
+    import vnext_amd.models  # noqa: F401
+    from vnext_amd import train
+    from vnext_amd.registry import build_model, get_idol_cfg
+    torch.manual_seed(11)
+    tiny = {"MODEL.IDOL.ENC_LAYERS": 1, "MODEL.IDOL.DEC_LAYERS": 2, "MODEL.IDOL.NUM_OBJECT_QUERIES": 110,
+            "MODEL.IDOL.DIM_FEEDFORWARD": 64, "MODEL.IDOL.DROPOUT": 0.0}
+    model = build_model(get_idol_cfg(**{"MODEL.DEVICE": DEV, **tiny})).train()
+    for mod in model.modules():
+        if isinstance(mod, torch.nn.MultiheadAttention):
+            mod.dropout = 0.0
+    pairs = train.synthetic_clips(1, 2, 96, 160, DEV, seed=6, num_instances=3)
+    # the indices, on the trunk's own outputs
+    m = model.criterion.matcher
+    with torch.no_grad():
+        det_t, ref_t = model.prepare_targets(pairs)
+        torch.manual_seed(1)
+        hs, logits, boxes, ref_xy, ref_last, feats, ref_logits, embeds = model._train_trunk(*model._preprocess(
+            [f for video in pairs for f in video["image"]]))
+        host, host_matched = m.match_all_layers(logits, boxes, det_t)
+        want = pos_neg_masks(ref_last, ref_logits.sigmoid(), ref_t)
+        indices, matched, sel = _NoHostMatcher().match_all_layers_device(logits, boxes, det_t,
+                                                                         ref=(ref_last, ref_logits.sigmoid(), ref_t))
+        for l in range(len(host)):
+            for i in range(len(det_t)):
+                assert torch.equal(indices[l][i][0], host[l][i][0]) and torch.equal(indices[l][i][1], host[l][i][1])
+        for i in range(len(det_t)):
+            assert torch.equal(matched[i], host_matched[i])
+            for x, y in zip(sel[i], want[i]):
+                assert torch.equal(x, y)
+    assert model.device_matching is False
+    loss_h1, grad_h1 = _step(model, pairs)
+    loss_h2, grad_h2 = _step(model, pairs)
+    train.enable_device_matching(model)
+    m.__class__ = _NoHostMatcher              # the step with the switch on is the kernel's, not a fallback's
+    try:
+        loss_d, grad_d = _step(model, pairs)
+    finally:
+        m.__class__ = OTAMatcher
+        train.enable_device_matching(model, False)
+    assert set(loss_d) == set(loss_h1) and set(grad_d) == set(grad_h1) and len(grad_d) >= 6
+
+    failures = []
+    for kind, d, h1, h2 in (("loss", loss_d, loss_h1, loss_h2), ("grad", grad_d, grad_h1, grad_h2)):
+        for k in h1:
+            host_diff = float((h1[k] - h2[k]).abs().max())
+            dev_diff = float((d[k] - h1[k]).abs().max())
+            allowed = max(10 * host_diff, 1e-6 * float(h1[k].abs().max()))
+            print(f"{kind} {k}: device-host {dev_diff:.3e}, host-host {host_diff:.3e}, allowed {allowed:.3e}")
+            if not dev_diff <= allowed:
+                failures.append((kind, k, dev_diff, allowed))
+    assert not failures, failures

@@ -70,6 +70,9 @@ SIGNATURES = {
     "vnx_lsap_solve": (_i, [_vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp]),
     "vnx_mask_loss_forward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp, _sz] + [_vp] * 4),
     "vnx_mask_loss_backward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp] * 5),
+    "vnx_idol_match_max_targets": (_i, [_i]),
+    "vnx_idol_match_out_words": (_i, [_i, _i]),
+    "vnx_idol_match": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _i, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

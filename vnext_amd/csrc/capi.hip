@@ -818,6 +818,23 @@ int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips,
                                  (float*)grad_logits, (hipStream_t)hip_stream);
 }
 
+// ---- IDOL's simOTA matching and contrastive sets (ota_match.hip: the argument checks live beside the kernel's LDS layout) ----
+int vnx_idol_match_max_targets(int queries) { return queries < 1 ? 0 : vnx::idol_match_cap(queries); }
+
+int vnx_idol_match_out_words(int targets_max, int queries) {
+  return targets_max < 0 || queries < 1 ? 0 : vnx::idol_match_out_words(targets_max, queries);
+}
+
+int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_prob, const void* ref_boxes,
+                   const void* target_boxes, const void* labels, const void* valid, const void* problems,
+                   int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
+                   int targets_max, void* out, int out_stride, void* hip_stream) {
+  return vnx::idol_match((const float*)det_prob, (const float*)det_boxes, (const float*)ref_prob, (const float*)ref_boxes,
+                         (const float*)target_boxes, (const int64_t*)labels, (const uint8_t*)valid,
+                         (const int32_t*)problems, det_problems, ref_problems, queries, classes, targets_total,
+                         valid_first, targets_max, (int32_t*)out, out_stride, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

@@ -132,6 +132,14 @@ int mask_loss_backward(const float* logits, const vnx_mask_loss_clips* clips, co
                        int height, int width, int stride, float alpha, float gamma, const float* row_sums,
                        const float* grad_focal, const float* grad_dice, float* grad_logits, hipStream_t stream);
 
+// ota_match.hip (IDOL's simOTA matching and contrastive sets, one workgroup per problem; argument checks there, C entry point in capi.hip)
+int idol_match_cap(int queries);                                // targets of one problem at most
+int idol_match_out_words(int targets_max, int queries);         // int32 words of one problem's output
+int idol_match(const float* det_prob, const float* det_boxes, const float* ref_prob, const float* ref_boxes,
+               const float* target_boxes, const int64_t* labels, const uint8_t* valid, const int32_t* problems,
+               int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
+               int targets_max, int32_t* out, int out_stride, hipStream_t stream);
+
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim
 // 64-bit slots; each workgroup leaves {its start, its last wave's end} there in constant-rate

@@ -31,7 +31,7 @@ from torch import nn
 from ..heads import dynamic_mask_head, loss_reid
 from ..registry import META_ARCH_REGISTRY
 from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
-from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, select_pos_neg_masks
+from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, sample_aux_masks, select_pos_neg_masks
 from .idol_transformer import DeformableTransformer
 from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
 from .seqformer_transformer import inverse_sigmoid
@@ -140,6 +140,9 @@ class IDOL(nn.Module):
         self.graph_inference = True      # replay the per-chunk inference trunk from a hipGraph
         self.graph_training = False      # capture the training trunk's forward and backward (opt-in: the trunk's gradients then
         #                                  reach DDP's buckets together, at the end of the replayed backward)
+        # simOTA matching and the contrastive sets by one kernel (vnext_amd/ops/ota_match.py) instead of on the host
+        # (opt-in: train.enable_device_matching); CUDA tensors only, the host matcher otherwise
+        self.device_matching = False
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -261,7 +264,12 @@ class IDOL(nn.Module):
         else:
             hs, logits, boxes, ref_xy, ref_last, feats, ref_logits, embeds = self._train_trunk(*self._preprocess(frames))
         Ld, bz = hs.shape[0], len(det_t)
-        indices_list, matched = self.criterion.matcher.match_all_layers(logits, boxes, det_t)
+        pos_neg = None
+        if self.device_matching and logits.is_cuda:
+            indices_list, matched, pos_neg = self.criterion.matcher.match_all_layers_device(
+                logits, boxes, det_t, ref=(ref_last, ref_logits.detach().sigmoid(), ref_t))
+        else:
+            indices_list, matched = self.criterion.matcher.match_all_layers(logits, boxes, det_t)
         # the selected queries of every decoder layer on every key frame: one gather, one controller
         # call, one mask-head launch
         q_host = [[torch.nonzero(sel).flatten() for sel, _ in ind] for ind in indices_list]
@@ -277,7 +285,10 @@ class IDOL(nn.Module):
             masks = masks + 0 * (feats.sum() + sum(p.sum() for p in self.detr.controller.parameters()))
         masks = masks[:, None]                                                          # [n, 1, H/4, W/4]
         # contrastive sets on the reference frames (last decoder layer), embeddings of both frames
-        selections = select_pos_neg_masks(ref_last, ref_logits.sigmoid(), ref_t)
+        if pos_neg is None:
+            selections = select_pos_neg_masks(ref_last, ref_logits.sigmoid(), ref_t)
+        else:                    # matched on the device above: the sampling loop alone
+            selections = sample_aux_masks(pos_neg)
         qd = reid_terms(embeds[0::2], embeds[1::2], matched, selections, loss_reid)
         if self.deep_supervision:   # every decoder layer's losses in one pass over stacked tensors
             loss = self.criterion.forward_all_layers(logits, boxes, masks, det_t, indices_list, qd)

@@ -18,6 +18,8 @@ Two quirks of the reference are kept on purpose, because they change results: th
 "matched to several boxes" mask in the repair loop is the one computed BEFORE the loop
 (matcher.py:156-158 reuses `anchor_matching_gt`), and the k=10 / k=100 selections of
 pos_neg_select share one cost matrix, so repairs made by the first are seen by the second.
+`OTAMatcher.match_all_layers_device` is the same matching by one kernel (vnext_amd/csrc/ota_match.hip; opt-in through
+`IDOL.device_matching`): the host forms here stay the yardstick it is tested against, and what runs when it declines.
 """
 from __future__ import annotations
 
@@ -150,16 +152,58 @@ class OTAMatcher(nn.Module):
             out = [[self._one(boxes[l, i], prob[l, i], tg[i], nf) for i in range(len(tg))] for l in range(prob.shape[0])]
         return [[r[0] for r in layer] for layer in out], [r[1] for r in out[-1]]
 
+    @torch.no_grad()
+    def match_all_layers_device(self, logits, boxes, targets, ref=None, nf=1):
+        """`match_all_layers`, and with ref = (ref_boxes [bz, Q, 4], ref_prob [bz, Q, K], ref_targets) also `pos_neg_masks`,
+        by one kernel launch (vnext_amd/ops/ota_match.py) and ONE device->host copy of its compact result -- instead of
+        logits, boxes, labels, target boxes and `valid` crossing one by one and ~40 ATen CPU ops per problem.
+        -> (indices_list, matched of the last layer, per reference image (inst, pos, neg) | None): the host forms' structures
+        on the host.  The copy is the one synchronisation left: the counts are needed there (mask head's rows, rng.sample).
+        The whole call is redone on the host when the kernel refuses the sizes (OtaUnsupported) or any problem's status
+        word is set (non-finite cost, repair loop bound)."""
+        from ..ops.ota_match import OtaUnsupported, idol_match, unpack
+
+        def on_host():
+            ind, matched = self.match_all_layers(logits, boxes, targets, nf)
+            return ind, matched, None if ref is None else pos_neg_masks(*ref)
+        Ld, bz, Q, K = (int(v) for v in logits.shape)
+        dev = logits.device
+        sizes = [len(t["labels"]) for t in targets]
+        ref_targets = [] if ref is None else ref[2]
+        ref_sizes = [len(t["labels"]) for t in ref_targets]
+        first = sum(sizes)
+        start, table = 0, []
+        for n in sizes:
+            table.append((start, n))
+            start += n
+        table = table * Ld
+        for n in ref_sizes:
+            table.append((start, n))
+            start += n
+        prob = logits.detach().float().sigmoid() if logits.dtype in (torch.bfloat16, torch.float16) else logits.detach().sigmoid()
+        tgt_boxes = torch.cat([t["boxes"].reshape(n, nf, 4)[:, 0].float() for t, n in zip(targets, sizes)] +
+                              [t["boxes"].reshape(-1, 4).float() for t in ref_targets]).to(dev)
+        labels = torch.cat([t["labels"] for t in targets] + [t["labels"] for t in ref_targets]).to(dev, torch.int64)
+        valid = torch.cat([t["valid"].bool() for t in ref_targets]).to(dev) if ref_targets else None
+        problems = torch.tensor(table, dtype=torch.int32).reshape(-1, 2).to(dev, non_blocking=True)
+        cap = max(sizes + ref_sizes + [0])
+        try:
+            out = idol_match(prob.reshape(Ld * bz, Q, K), boxes.detach().reshape(Ld * bz, Q, 4), tgt_boxes, labels, problems, cap,
+                             ref_prob=None if ref is None else ref[1].detach(), ref_boxes=None if ref is None else ref[0].detach(),
+                             valid=valid, valid_first=first)
+        except OtaUnsupported:
+            return on_host()
+        status, det, sel = unpack(out.cpu(), Ld * bz, Q, cap)
+        if bool(status.any()):
+            return on_host()
+        indices_list = [[det[l * bz + i][:2] for i in range(bz)] for l in range(Ld)]
+        return indices_list, [det[(Ld - 1) * bz + i][2] for i in range(bz)], None if ref is None else sel
+
 
 @torch.no_grad()
-def select_pos_neg_masks(ref_boxes, ref_prob, ref_targets, rng=_random):
-    """The reference frame's contrastive sets (pos_neg_select.py:13-67, 72-124).
-
-    ref_boxes [bz, Q, 4], ref_prob [bz, Q, K] (last decoder layer on the reference frame),
-    ref_targets: per image {"boxes" [n,4], "labels" [n], "valid" [n]} -- same instance order as
-    the key frame's targets.  -> per image (inst [I] indices of the valid instances,
-    pos [Q, I], neg [Q, I], aux [Q, I] bool masks); aux = positives + the negatives drawn with
-    `rng.sample` (host RNG, same call sequence as the reference)."""
+def pos_neg_masks(ref_boxes, ref_prob, ref_targets):
+    """The matching half of `select_pos_neg_masks`, on the host: per image (inst [I] indices of the valid instances,
+    pos [Q, I], neg [Q, I] bool) -- the k = 10 and the k = 100 matching on one cost matrix."""
     out = []
     ref_boxes, ref_prob = _host32(ref_boxes), _host32(ref_prob)
     with _one_thread():
@@ -170,21 +214,45 @@ def select_pos_neg_masks(ref_boxes, ref_prob, ref_targets, rng=_random):
             I = len(inst)
             pos = torch.zeros(Q, I, dtype=torch.bool)
             neg = torch.zeros(Q, I, dtype=torch.bool)
-            aux = torch.zeros(Q, I, dtype=torch.bool)
             if I > 0:
                 gt = t["boxes"].cpu().reshape(-1, 4)[valid].to(ref_boxes)
                 cost, iou = ota_cost(ref_boxes[i], ref_prob[i], gt, t["labels"].cpu()[valid])
                 pos = dynamic_k_matching(cost, iou, 10) > 0
                 neg = ~(dynamic_k_matching(cost, iou, 100) > 0)       # same (already repaired) cost matrix
-                for c in range(I):
-                    P, N = int(pos[:, c].sum()), int(neg[:, c].sum())
-                    k = 10 if P == 0 else (N if P * 10 >= N else P * 10)
-                    picked = rng.sample(list(range(N)), k)
-                    neg_rows = torch.nonzero(neg[:, c]).flatten()
-                    aux[:, c] = pos[:, c]
-                    aux[neg_rows[picked], c] = True
+            out.append((inst, pos, neg))
+    return out
+
+
+def sample_aux_masks(pos_neg, rng=_random):
+    """The sampling half of `select_pos_neg_masks`, shared by the host and the device matching: per image (inst, pos,
+    neg) -> (inst, pos, neg, aux), aux = positives + the negatives drawn with `rng.sample` (host RNG, one call per
+    instance in image and instance order: the reference's call sequence)."""
+    out = []
+    with _one_thread():
+        for inst, pos, neg in pos_neg:
+            aux = torch.zeros(pos.shape[0], len(inst), dtype=torch.bool)
+            for c in range(len(inst)):
+                P, N = int(pos[:, c].sum()), int(neg[:, c].sum())
+                k = 10 if P == 0 else (N if P * 10 >= N else P * 10)
+                picked = rng.sample(list(range(N)), k)
+                neg_rows = torch.nonzero(neg[:, c]).flatten()
+                aux[:, c] = pos[:, c]
+                aux[neg_rows[picked], c] = True
             out.append((inst, pos, neg, aux))
     return out
+
+
+@torch.no_grad()
+def select_pos_neg_masks(ref_boxes, ref_prob, ref_targets, rng=_random):
+    """The reference frame's contrastive sets (pos_neg_select.py:13-67, 72-124).
+
+    ref_boxes [bz, Q, 4], ref_prob [bz, Q, K] (last decoder layer on the reference frame),
+    ref_targets: per image {"boxes" [n,4], "labels" [n], "valid" [n]} -- same instance order as
+    the key frame's targets.  -> per image (inst [I] indices of the valid instances,
+    pos [Q, I], neg [Q, I], aux [Q, I] bool masks); aux = positives + the negatives drawn with
+    `rng.sample` (host RNG, same call sequence as the reference: the matching draws nothing, so
+    matching every image first and sampling afterwards is that sequence)."""
+    return sample_aux_masks(pos_neg_masks(ref_boxes, ref_prob, ref_targets), rng)
 
 
 class IDOLCriterion(nn.Module):

@@ -297,11 +297,14 @@ def release_training_graphs(model) -> None:
 
 
 def enable_device_matching(model, on: bool = True) -> None:
-    """Opt in to SeqFormer's device-side Hungarian matching (`SeqFormer.device_matching`): cost and assignment of every
-    (decoder layer, clip) in one kernel, the indices never leave the device -- `losses` then runs from `prepare_targets`
-    to the loss dict without a device-to-host copy or a blocking upload.  The same pairs as the host matcher wherever the
-    optimum is unique beyond fp32 rounding of the cost.  Raises for a model without the switch (IDOL's simOTA matcher is a
-    different algorithm)."""
+    """Opt in to matching on the device (`SeqFormer.device_matching` / `IDOL.device_matching`).
+    SeqFormer: Hungarian matching, cost and assignment of every (decoder layer, clip) in one kernel, the indices never
+    leave the device -- `losses` then runs from `prepare_targets` to the loss dict without a device-to-host copy or a
+    blocking upload.  The same pairs as the host matcher wherever the optimum is unique beyond fp32 rounding of the cost.
+    IDOL: simOTA matching of every (decoder layer, key image) and the positive / negative sets of every reference image
+    in one kernel; its compact result crosses to the host in one copy (the counts are needed there: the mask head's rows,
+    `rng.sample`), so one synchronisation stays and the host arithmetic goes.  The same indices as the host matcher
+    wherever no comparison is decided by fp32 rounding of the cost.  Raises for a model without the switch."""
     if not hasattr(model, "device_matching"):
         raise ValueError("enable_device_matching: %s has no device_matching switch" % type(model).__name__)
     model.device_matching = bool(on)
