@@ -584,6 +584,46 @@ int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips,
                            const void* grad_focal, const void* grad_dice, void* grad_logits, void* hip_stream);
 
 /*
+ * The class and box losses of both criteria for every decoder layer at once (set_loss.hip): the sigmoid focal loss over
+ * all logits against the one-hot target the pair list implies, the matched boxes' L1 and GIoU losses, and the count of
+ * matched queries whose argmax is their label.  ADDITIVE: two symbols, no existing signature changed, so VNX_ABI_VERSION
+ * stays 17; a binding that needs them looks the symbols up.
+ *
+ *   logits fp32 [layers][clips][queries][classes], boxes fp32 [layers][clips][frames][queries][4] (cx, cy, w, h), contiguous;
+ *   lay, clip, qry, tgt int64 [pairs] on the device: query qry[r] of (layer lay[r], clip clip[r]) is matched to target
+ *     tgt[r], counted over the clips' targets laid back to back;
+ *   labels int64 [targets_total], target_boxes fp32 [targets_total][frames][4].
+ * out fp32 [layers][4], per layer:
+ *   [0] sum over (clip, query, class) of  alpha_t * ce * (1 - p_t)^2  (gamma = 2; alpha < 0: no alpha_t), the target 1 at
+ *       (clip[r], qry[r], labels[tgt[r]]) of the layer's pairs and 0 elsewhere -- never materialised;
+ *   [1] sum over the layer's pairs, frames and coordinates of |box - target box|;
+ *   [2] sum over the layer's pairs and frames of 1 - GIoU of the xyxy forms: intersection only where both extents are
+ *       positive, 1e-7 added to union and hull in the denominators, hull extents not clamped;
+ *   [3] the number of the layer's pairs whose first maximum over the classes is labels[tgt[r]] (not differentiable).
+ * PRECONDITIONS: a (lay, clip, qry) triple appears at most once.  A pair with a negative qry or tgt, or any index outside
+ * its array, contributes nothing; a label outside [0, classes) sets no target and scores no hit.
+ * Forward: a workgroup owns one piece of one (layer, clip): rows = clamp(VNX_SET_LOSS_PIECE / classes, 1,
+ * VNX_SET_LOSS_MAX_ROWS) consecutive queries; it writes one partial [4]; partial fp32 [layers][clips * pieces][4] with
+ * pieces = ceil(queries / rows) is caller-owned, 16-byte aligned like out, and need not be zeroed.  A second small launch
+ * adds a layer's partials in a fixed order.  Backward: ONE launch writes every element of grad_logits (= grad_out[l][0] *
+ * dfocal/dlogit) and of grad_boxes (grad_out[l][1] * sign(box - target) + grad_out[l][2] * d(1 - GIoU)/dbox at matched
+ * (layer, clip, frame, query), 0 elsewhere), recomputed from the inputs; grad_out [layers][4] fp32, its column 3 ignored.
+ * At an exact tie a maximum / minimum splits its gradient evenly between its operands, and sign(0) = 0, as ATen does.
+ * No atomics: bit-identical run to run.  No allocation, no synchronisation: capturable in a hipGraph.  pairs == 0 is valid
+ * (the pair pointers may then be null): column 0 and grad_logits are computed, the rest is 0.
+ */
+#define VNX_SET_LOSS_PIECE 4096
+#define VNX_SET_LOSS_MAX_ROWS 1024
+int vnx_set_loss_forward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                         const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
+                         int queries, int classes, int pairs, int targets_total, float alpha, void* partial,
+                         size_t partial_bytes, void* out, void* hip_stream);
+int vnx_set_loss_backward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                          const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
+                          int queries, int classes, int pairs, int targets_total, float alpha, const void* grad_out,
+                          void* grad_logits, void* grad_boxes, void* hip_stream);
+
+/*
  * IDOL's simOTA matching and the contrastive positive / negative sets on the device (ota_match.hip).  ADDITIVE: three
  * symbols, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
  *

@@ -1,10 +1,12 @@
 """Where a SeqFormer training step spends its wall time (synchronising between phases, so the sum
 exceeds the pipelined step).  python tools/step_breakdown.py [--graph] [--device-matching] [--fused-mask-loss]
+[--fused-set-loss]
 
 --device-matching: the same rows with SeqFormer's device-side matcher (train.enable_device_matching), so the "matching"
 row and the step can be read side by side with the host matcher's.
 --fused-mask-loss: the same rows with the criterion's mask losses from the fused kernel (train.enable_fused_mask_loss):
-the "full forward" and "backward" rows carry the difference."""
+the "full forward" and "backward" rows carry the difference.
+--fused-set-loss: likewise with the criterion's class and box losses from the fused op (train.enable_fused_set_loss)."""
 import argparse
 import os
 import sys
@@ -21,6 +23,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--graph", action="store_true")
 ap.add_argument("--device-matching", action="store_true")
 ap.add_argument("--fused-mask-loss", action="store_true")
+ap.add_argument("--fused-set-loss", action="store_true")
 ap.add_argument("--steps", type=int, default=8)
 a = ap.parse_args()
 dev = "cuda:0"
@@ -31,6 +34,8 @@ if a.device_matching:
     T.enable_device_matching(model)
 if a.fused_mask_loss:
     T.enable_fused_mask_loss(model)
+if a.fused_set_loss:
+    T.enable_fused_set_loss(model)
 opt = T.build_optimizer(model)
 clips = T.synthetic_clips(1, 5, 360, 640, dev, seed=100, num_instances=4)
 for _ in range(3):

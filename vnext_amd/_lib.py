@@ -70,6 +70,8 @@ SIGNATURES = {
     "vnx_lsap_solve": (_i, [_vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp]),
     "vnx_mask_loss_forward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp, _sz] + [_vp] * 4),
     "vnx_mask_loss_backward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp] * 5),
+    "vnx_set_loss_forward": (_i, [_vp] * 8 + [_i] * 7 + [ctypes.c_float, _vp, _sz, _vp, _vp]),
+    "vnx_set_loss_backward": (_i, [_vp] * 8 + [_i] * 7 + [ctypes.c_float] + [_vp] * 4),
     "vnx_idol_match_max_targets": (_i, [_i]),
     "vnx_idol_match_out_words": (_i, [_i, _i]),
     "vnx_idol_match": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _i, _vp]),
@@ -104,6 +106,9 @@ class TrackerConfig(ctypes.Structure):
 
 
 MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096      # VNX_MASK_LOSS_MAX_CLIPS, VNX_MASK_LOSS_PIECE
+
+
+SET_LOSS_PIECE, SET_LOSS_MAX_ROWS = 4096, 1024       # VNX_SET_LOSS_PIECE, VNX_SET_LOSS_MAX_ROWS
 
 
 class MaskLossClips(ctypes.Structure):

@@ -818,6 +818,28 @@ int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips,
                                  (float*)grad_logits, (hipStream_t)hip_stream);
 }
 
+// ---- class and box losses of every decoder layer (set_loss.hip: the argument checks live beside the kernels' addressing limits) ----
+int vnx_set_loss_forward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                         const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
+                         int queries, int classes, int pairs, int targets_total, float alpha, void* partial,
+                         size_t partial_bytes, void* out, void* hip_stream) {
+  return vnx::set_loss_forward((const float*)logits, (const float*)boxes, (const int64_t*)lay, (const int64_t*)clip,
+                               (const int64_t*)qry, (const int64_t*)tgt, (const int64_t*)labels, (const float*)target_boxes,
+                               layers, clips, frames, queries, classes, pairs, targets_total, alpha, (float*)partial,
+                               partial_bytes, (float*)out, (hipStream_t)hip_stream);
+}
+
+int vnx_set_loss_backward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                          const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
+                          int queries, int classes, int pairs, int targets_total, float alpha, const void* grad_out,
+                          void* grad_logits, void* grad_boxes, void* hip_stream) {
+  return vnx::set_loss_backward((const float*)logits, (const float*)boxes, (const int64_t*)lay, (const int64_t*)clip,
+                                (const int64_t*)qry, (const int64_t*)tgt, (const int64_t*)labels,
+                                (const float*)target_boxes, layers, clips, frames, queries, classes, pairs, targets_total,
+                                alpha, (const float*)grad_out, (float*)grad_logits, (float*)grad_boxes,
+                                (hipStream_t)hip_stream);
+}
+
 // ---- IDOL's simOTA matching and contrastive sets (ota_match.hip: the argument checks live beside the kernel's LDS layout) ----
 int vnx_idol_match_max_targets(int queries) { return queries < 1 ? 0 : vnx::idol_match_cap(queries); }
 

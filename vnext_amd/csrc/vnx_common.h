@@ -132,6 +132,16 @@ int mask_loss_backward(const float* logits, const vnx_mask_loss_clips* clips, co
                        int height, int width, int stride, float alpha, float gamma, const float* row_sums,
                        const float* grad_focal, const float* grad_dice, float* grad_logits, hipStream_t stream);
 
+// set_loss.hip (class focal + box L1 / GIoU + argmax hits of every decoder layer; argument checks there, C entry points in capi.hip)
+int set_loss_forward(const float* logits, const float* boxes, const int64_t* lay, const int64_t* clip, const int64_t* qry,
+                     const int64_t* tgt, const int64_t* labels, const float* target_boxes, int layers, int clips,
+                     int frames, int queries, int classes, int pairs, int targets_total, float alpha, float* partial,
+                     size_t partial_bytes, float* out, hipStream_t stream);
+int set_loss_backward(const float* logits, const float* boxes, const int64_t* lay, const int64_t* clip, const int64_t* qry,
+                      const int64_t* tgt, const int64_t* labels, const float* target_boxes, int layers, int clips,
+                      int frames, int queries, int classes, int pairs, int targets_total, float alpha,
+                      const float* grad_out, float* grad_logits, float* grad_boxes, hipStream_t stream);
+
 // ota_match.hip (IDOL's simOTA matching and contrastive sets, one workgroup per problem; argument checks there, C entry point in capi.hip)
 int idol_match_cap(int queries);                                // targets of one problem at most
 int idol_match_out_words(int targets_max, int queries);         // int32 words of one problem's output

@@ -16,6 +16,8 @@ mask head runs for), not a kernel.  Differences in *how*, not in *what*:
     (vnext_amd/csrc/lsap.hip), the indices never leave it -- no copy to the host, no scipy, no upload.
   * opt-in (`fused_mask_loss`): focal + dice of the mask logits from one kernel pass each way (vnext_amd/csrc/mask_loss.hip),
     the ground truth read in place -- no sliced / padded / gathered float copy, nothing [R, M]-sized kept for the backward.
+  * opt-in (`fused_set_loss`): the class focal loss, the boxes' L1 and GIoU losses and `class_error` of every decoder layer
+    from one op (vnext_amd/csrc/set_loss.hip): no one-hot target, no gathers, two launches forward and one backward.
 """
 from __future__ import annotations
 
@@ -217,6 +219,9 @@ class SetCriterion(nn.Module):
         # mask losses from the fused kernel (vnext_amd/ops/mask_loss.py): the ground truth read in place, one pass each
         # way (opt-in: train.enable_fused_mask_loss).  CUDA tensors only -- there is no fallback behind the switch
         self.fused_mask_loss = False
+        # class focal + box L1 / GIoU + class_error of `forward_all_layers` from the fused op (vnext_amd/ops/set_loss.py;
+        # opt-in: train.enable_fused_set_loss).  CUDA tensors only -- there is no fallback behind the switch
+        self.fused_set_loss = False
 
     @staticmethod
     def _src_idx(indices):
@@ -327,28 +332,37 @@ class SetCriterion(nn.Module):
         out = {}
         # labels (focal): mean over Q * Q = sum over Q
         all_labels = torch.cat([t["labels"] for t in targets]).to(dev)
-        onehot = torch.zeros_like(logits)
-        onehot[lay, clip, qry, all_labels[tgt]] = torch.ones((), dtype=logits.dtype, device=dev)   # a Python 1 is uploaded
-        p = logits.sigmoid()
-        ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
-        p_t = p * onehot + (1 - p) * (1 - onehot)
-        focal = ce * (1 - p_t) ** 2.0
-        if self.focal_alpha >= 0:
-            focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
-        loss_ce = focal.mean(2).sum((1, 2)) / num_boxes * Q
-        with torch.no_grad():
-            if n:
-                sel = logits[-1][clip[-n:], qry[-n:]]
-                out["class_error"] = 100 - (sel.argmax(-1) == all_labels[tgt[-n:]]).float().mean() * 100
-            else:
-                out["class_error"] = 100 - torch.zeros([], device=dev)
-        # boxes (L1 + GIoU over the clip's frames)
-        pred = boxes.transpose(2, 3)[lay, clip, qry]                                   # [Ld*n, T, 4]
-        all_boxes = torch.cat([t["boxes"].reshape(-1, T, 4) for t in targets]).to(pred)
-        want = all_boxes[tgt]
-        l1 = (pred - want).abs().flatten(1).sum(1).view(Ld, n).sum(1) / T / num_boxes
-        g = giou_loss(box_cxcywh_to_xyxy(pred.flatten(0, 1)), box_cxcywh_to_xyxy(want.flatten(0, 1)))
-        g = g.view(Ld, n * T).sum(1) / T / num_boxes
+        if self.fused_set_loss:
+            from ..ops.set_loss import set_class_box_losses
+            all_boxes = torch.cat([t["boxes"].reshape(-1, T, 4) for t in targets]).to(dev)
+            sums = set_class_box_losses(logits, boxes, lay, clip, qry, tgt, all_labels, all_boxes, self.focal_alpha)   # [Ld, 4]
+            loss_ce = sums[:, 0] / num_boxes
+            l1 = sums[:, 1] / T / num_boxes
+            g = sums[:, 2] / T / num_boxes
+            out["class_error"] = 100 - sums.detach()[-1, 3] / max(n, 1) * 100
+        else:
+            onehot = torch.zeros_like(logits)
+            onehot[lay, clip, qry, all_labels[tgt]] = torch.ones((), dtype=logits.dtype, device=dev)   # a Python 1 is uploaded
+            p = logits.sigmoid()
+            ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
+            p_t = p * onehot + (1 - p) * (1 - onehot)
+            focal = ce * (1 - p_t) ** 2.0
+            if self.focal_alpha >= 0:
+                focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
+            loss_ce = focal.mean(2).sum((1, 2)) / num_boxes * Q
+            with torch.no_grad():
+                if n:
+                    sel = logits[-1][clip[-n:], qry[-n:]]
+                    out["class_error"] = 100 - (sel.argmax(-1) == all_labels[tgt[-n:]]).float().mean() * 100
+                else:
+                    out["class_error"] = 100 - torch.zeros([], device=dev)
+            # boxes (L1 + GIoU over the clip's frames)
+            pred = boxes.transpose(2, 3)[lay, clip, qry]                                   # [Ld*n, T, 4]
+            all_boxes = torch.cat([t["boxes"].reshape(-1, T, 4) for t in targets]).to(pred)
+            want = all_boxes[tgt]
+            l1 = (pred - want).abs().flatten(1).sum(1).view(Ld, n).sum(1) / T / num_boxes
+            g = giou_loss(box_cxcywh_to_xyxy(pred.flatten(0, 1)), box_cxcywh_to_xyxy(want.flatten(0, 1)))
+            g = g.view(Ld, n * T).sum(1) / T / num_boxes
         # masks (focal + dice)
         if n and self.fused_mask_loss:
             from ..ops.mask_loss import mask_focal_dice

@@ -266,6 +266,9 @@ class IDOLCriterion(nn.Module):
         # mask losses from the fused kernel (vnext_amd/ops/mask_loss.py): the ground truth read in place, one pass each
         # way (opt-in: train.enable_fused_mask_loss).  CUDA tensors only -- there is no fallback behind the switch
         self.fused_mask_loss = False
+        # class focal + box L1 / GIoU of `forward_all_layers` from the fused op (vnext_amd/ops/set_loss.py; opt-in:
+        # train.enable_fused_set_loss).  CUDA tensors only -- there is no fallback behind the switch
+        self.fused_set_loss = False
 
     @staticmethod
     def _on_device(indices, device):
@@ -372,19 +375,27 @@ class IDOLCriterion(nn.Module):
             return torch.zeros(Ld, dtype=values.dtype, device=dev).index_add_(0, lay, values)
         # labels
         all_labels = torch.cat([t["labels"] for t in targets]).to(dev)
-        onehot = torch.zeros_like(logits)
-        onehot[lay, img, qry, all_labels[tgt]] = 1
-        p = logits.sigmoid()
-        ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
-        focal = ce * (1 - (p * onehot + (1 - p) * (1 - onehot))) ** 2.0
-        if self.focal_alpha >= 0:
-            focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
-        loss_ce = focal.mean(2).sum((1, 2)) / denom * Q
-        # boxes
-        pred = boxes[lay, img, qry]
-        want = torch.cat([t["boxes"].reshape(-1, 4) for t in targets]).to(pred)[tgt]
-        l1 = per_layer((pred - want).abs().sum(1)) / denom * present
-        giou = per_layer(giou_loss(box_cxcywh_to_xyxy(pred), box_cxcywh_to_xyxy(want))) / denom * present
+        if self.fused_set_loss:               # per-layer sums from one op: no segment sums over the flat list
+            from ..ops.set_loss import set_class_box_losses
+            all_boxes = torch.cat([t["boxes"].reshape(-1, 1, 4) for t in targets]).to(dev)
+            sums = set_class_box_losses(logits, boxes[:, :, None], lay, img, qry, tgt, all_labels, all_boxes, self.focal_alpha)
+            loss_ce = sums[:, 0] / denom
+            l1 = sums[:, 1] / denom * present
+            giou = sums[:, 2] / denom * present
+        else:
+            onehot = torch.zeros_like(logits)
+            onehot[lay, img, qry, all_labels[tgt]] = 1
+            p = logits.sigmoid()
+            ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
+            focal = ce * (1 - (p * onehot + (1 - p) * (1 - onehot))) ** 2.0
+            if self.focal_alpha >= 0:
+                focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
+            loss_ce = focal.mean(2).sum((1, 2)) / denom * Q
+            # boxes
+            pred = boxes[lay, img, qry]
+            want = torch.cat([t["boxes"].reshape(-1, 4) for t in targets]).to(pred)[tgt]
+            l1 = per_layer((pred - want).abs().sum(1)) / denom * present
+            giou = per_layer(giou_loss(box_cxcywh_to_xyxy(pred), box_cxcywh_to_xyxy(want))) / denom * present
         # masks
         h, w = masks.shape[-2:]
         s_ = self.mask_out_stride

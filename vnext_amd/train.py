@@ -322,6 +322,18 @@ def enable_fused_mask_loss(model, on: bool = True) -> None:
     criterion.fused_mask_loss = bool(on)
 
 
+def enable_fused_set_loss(model, on: bool = True) -> None:
+    """Opt in to the fused class and box losses (`criterion.fused_set_loss`, vnext_amd/ops/set_loss.py): the class focal
+    loss over the logits of every decoder layer, the matched boxes' L1 and GIoU losses and (SeqFormer) `class_error` from
+    one op -- two launches forward, one backward, no one-hot target, no gathers, nothing of the logits' size kept for the
+    backward.  SeqFormer and IDOL alike; same loss names and normalisations, the sums reassociated.  CUDA only: with the
+    switch on, a criterion given CPU tensors raises.  Raises for an object whose criterion has no such switch."""
+    criterion = getattr(model, "criterion", None)
+    if criterion is None or not hasattr(criterion, "fused_set_loss"):
+        raise ValueError("enable_fused_set_loss: %s has no criterion with a fused_set_loss switch" % type(model).__name__)
+    criterion.fused_set_loss = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
