@@ -671,6 +671,42 @@ int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_
                    int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
                    int targets_max, void* out, int out_stride, void* hip_stream);
 
+/*
+ * IDOL's re-identification losses -- the contrastive loss and the auxiliary cosine loss -- of every instance of every image
+ * of a step (reid_loss.hip).  ADDITIVE: two symbols, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding
+ * that needs them looks the symbols up.
+ *
+ *   key fp32 [images][key_rows][channels], ref fp32 [images][ref_rows][channels]: rows contiguous, image i at
+ *     base + i * image_stride ELEMENTS (the two interleaved halves of one [2 images, rows, channels] tensor are read in place);
+ *   img, key_query int32 [instances] on the device: instance j compares row key_query[j] of key image img[j] with every row
+ *     of reference image img[j]; img is non-decreasing;
+ *   flags uint8 [instances][ref_rows]: bit 0 positive (P), bit 1 negative (N), bit 2 aux sample (A).
+ * With k the key row, dot_r = <ref_r, k> and cos_r = dot_r / (max(|ref_r|, 1e-12) * max(|k|, 1e-12)):
+ *   out[j][0] = softplus(logsumexp_{r in N} dot_r + logsumexp_{r in P} -dot_r), exactly 0 when P or N is empty (stable: the
+ *               maxima are taken out first);
+ *   out[j][1] = sum_{r in A} (cos_r - [r in P])^2 / max(|A|, 1).
+ * An instance whose img is outside [0, images) or whose key_query is outside [0, key_rows) reads nothing, gets (0, 0) and
+ * contributes no gradient.
+ * Forward: ONE launch, a workgroup per instance; it also leaves what the backward needs: dot fp32 [instances][ref_rows],
+ * ref_norm fp32 [instances][ref_rows] (|ref_r|) and stats fp32 [instances][8] = {|k|, max_N, sum_N, max_P, sum_P, |A|,
+ * P and N both non-empty, 0} -- caller-owned, need not be zeroed; nothing of the embeddings' size.  instances == 0: no launch.
+ * Backward: TWO launches write every element of grad_ref [images][ref_rows][channels] and grad_key [images][key_rows][channels]
+ * (contiguous; zero where no instance reaches), grad_out fp32 [instances][2]; two instances that share a key row add, in list
+ * order.  The clamp of the norms is differentiated as a clamp_min.  No atomics, no memset: bit-identical run to run.  No
+ * allocation, no synchronisation: capturable in a hipGraph.  instances == 0 is valid: both gradients are zero.
+ * VNX_ERR_UNSUPPORTED, nothing launched: channels, key_rows or images < 1, ref_rows outside [1, VNX_REID_LOSS_MAX_ROWS].
+ * 16-byte loads where channels % 4 == 0 and bases and strides are 16-byte aligned; any channel count otherwise.
+ */
+#define VNX_REID_LOSS_MAX_ROWS 1024
+int vnx_reid_loss_forward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                          long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                          const void* key_query, const void* flags, int instances, void* out, void* dot, void* ref_norm,
+                          void* stats, void* hip_stream);
+int vnx_reid_loss_backward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                           long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                           const void* key_query, const void* flags, int instances, const void* dot, const void* ref_norm,
+                           const void* stats, const void* grad_out, void* grad_key, void* grad_ref, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

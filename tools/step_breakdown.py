@@ -1,12 +1,15 @@
 """Where a SeqFormer training step spends its wall time (synchronising between phases, so the sum
 exceeds the pipelined step).  python tools/step_breakdown.py [--graph] [--device-matching] [--fused-mask-loss]
-[--fused-set-loss]
+[--fused-set-loss] [--idol [--fused-reid-loss]]
 
 --device-matching: the same rows with SeqFormer's device-side matcher (train.enable_device_matching), so the "matching"
 row and the step can be read side by side with the host matcher's.
 --fused-mask-loss: the same rows with the criterion's mask losses from the fused kernel (train.enable_fused_mask_loss):
 the "full forward" and "backward" rows carry the difference.
---fused-set-loss: likewise with the criterion's class and box losses from the fused op (train.enable_fused_set_loss)."""
+--fused-set-loss: likewise with the criterion's class and box losses from the fused op (train.enable_fused_set_loss).
+--idol: the IDOL step instead (one 720 x 1280 pair, 8 objects: the bench's IDOL leg); its forward is one row, the trunk and
+the matching are not timed apart.
+--fused-reid-loss: with --idol, both reid losses from the fused op (train.enable_fused_reid_loss); SeqFormer has none."""
 import argparse
 import os
 import sys
@@ -17,19 +20,23 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import vnext_amd.models  # noqa: F401,E402
 from vnext_amd import train as T  # noqa: E402
-from vnext_amd.registry import build_model, get_seqformer_cfg  # noqa: E402
+from vnext_amd.registry import build_model, get_idol_cfg, get_seqformer_cfg  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--graph", action="store_true")
 ap.add_argument("--device-matching", action="store_true")
 ap.add_argument("--fused-mask-loss", action="store_true")
 ap.add_argument("--fused-set-loss", action="store_true")
+ap.add_argument("--fused-reid-loss", action="store_true")
+ap.add_argument("--idol", action="store_true")
 ap.add_argument("--steps", type=int, default=8)
 a = ap.parse_args()
 dev = "cuda:0"
 torch.manual_seed(0)
-model = build_model(get_seqformer_cfg(**{"MODEL.DEVICE": dev})).train()
+model = build_model((get_idol_cfg if a.idol else get_seqformer_cfg)(**{"MODEL.DEVICE": dev})).train()
 model.graph_training = a.graph
+if a.fused_reid_loss:
+    T.enable_fused_reid_loss(model)       # raises for SeqFormer: it has no reid losses
 if a.device_matching:
     T.enable_device_matching(model)
 if a.fused_mask_loss:
@@ -37,7 +44,8 @@ if a.fused_mask_loss:
 if a.fused_set_loss:
     T.enable_fused_set_loss(model)
 opt = T.build_optimizer(model)
-clips = T.synthetic_clips(1, 5, 360, 640, dev, seed=100, num_instances=4)
+clips = T.synthetic_clips(1, 2, 720, 1280, dev, seed=8, num_instances=8) if a.idol else \
+    T.synthetic_clips(1, 5, 360, 640, dev, seed=100, num_instances=4)
 for _ in range(3):
     T.train_step(model, opt, clips)
 
@@ -57,13 +65,18 @@ for _ in range(a.steps):
     targets = model.prepare_targets(clips)
     t = tick("prepare_targets", t)
     frames = [f for c in clips for f in c["image"]]
-    if a.graph:
+    if a.idol:
+        pass
+    elif a.graph:
         hs, logits, boxes, ref0, ref_rest, feats = model._graphed_train_trunk(torch.stack(frames))
     else:
         x, srcs, hs, memory, logits, boxes, refs = model._run(clips, want_refs=True)
         feats = model._mask_features(srcs, memory)
-    t = tick("trunk forward", t)
-    if a.device_matching:
+    if not a.idol:
+        t = tick("trunk forward", t)
+    if a.idol:
+        pass
+    elif a.device_matching:
         ind = model.criterion.matcher.match_all_layers_device(logits, boxes, targets)
         t = tick("matching (one kernel: cost + LSAP on the device)", t)
     else:

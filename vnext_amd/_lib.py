@@ -75,6 +75,8 @@ SIGNATURES = {
     "vnx_idol_match_max_targets": (_i, [_i]),
     "vnx_idol_match_out_words": (_i, [_i, _i]),
     "vnx_idol_match": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _i, _vp]),
+    "vnx_reid_loss_forward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 5),
+    "vnx_reid_loss_backward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 7),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -109,6 +111,9 @@ MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096      # VNX_MASK_LOSS_MAX_CLIPS, 
 
 
 SET_LOSS_PIECE, SET_LOSS_MAX_ROWS = 4096, 1024       # VNX_SET_LOSS_PIECE, VNX_SET_LOSS_MAX_ROWS
+
+
+REID_LOSS_MAX_ROWS = 1024                            # VNX_REID_LOSS_MAX_ROWS
 
 
 class MaskLossClips(ctypes.Structure):

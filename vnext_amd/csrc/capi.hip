@@ -857,6 +857,28 @@ int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_
                          valid_first, targets_max, (int32_t*)out, out_stride, (hipStream_t)hip_stream);
 }
 
+// ---- IDOL's reid losses, contrastive + cosine (reid_loss.hip: the argument checks live beside the kernels' addressing limits) ----
+int vnx_reid_loss_forward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                          long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                          const void* key_query, const void* flags, int instances, void* out, void* dot, void* ref_norm,
+                          void* stats, void* hip_stream) {
+  return vnx::reid_loss_forward((const float*)key, int64_t(key_image_stride), key_rows, (const float*)ref,
+                                int64_t(ref_image_stride), ref_rows, channels, images, (const int32_t*)img,
+                                (const int32_t*)key_query, (const uint8_t*)flags, instances, (float*)out, (float*)dot,
+                                (float*)ref_norm, (float*)stats, (hipStream_t)hip_stream);
+}
+
+int vnx_reid_loss_backward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                           long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                           const void* key_query, const void* flags, int instances, const void* dot, const void* ref_norm,
+                           const void* stats, const void* grad_out, void* grad_key, void* grad_ref, void* hip_stream) {
+  return vnx::reid_loss_backward((const float*)key, int64_t(key_image_stride), key_rows, (const float*)ref,
+                                 int64_t(ref_image_stride), ref_rows, channels, images, (const int32_t*)img,
+                                 (const int32_t*)key_query, (const uint8_t*)flags, instances, (const float*)dot,
+                                 (const float*)ref_norm, (const float*)stats, (const float*)grad_out, (float*)grad_key,
+                                 (float*)grad_ref, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"
 
 // ---- unit grid of the tile-fed grad_value kernel, seen from the host (include/vnext_hip_debug.h) -----------

@@ -150,6 +150,15 @@ int idol_match(const float* det_prob, const float* det_boxes, const float* ref_p
                int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
                int targets_max, int32_t* out, int out_stride, hipStream_t stream);
 
+// reid_loss.hip (IDOL's contrastive + cosine reid losses of every instance at once; argument checks there, C entry points in capi.hip)
+int reid_loss_forward(const float* key, int64_t key_stride, int key_rows, const float* ref, int64_t ref_stride, int ref_rows,
+                      int channels, int images, const int32_t* img, const int32_t* key_query, const uint8_t* flags,
+                      int instances, float* out, float* dot, float* ref_norm, float* stats, hipStream_t stream);
+int reid_loss_backward(const float* key, int64_t key_stride, int key_rows, const float* ref, int64_t ref_stride, int ref_rows,
+                       int channels, int images, const int32_t* img, const int32_t* key_query, const uint8_t* flags,
+                       int instances, const float* dot, const float* ref_norm, const float* stats, const float* grad_out,
+                       float* grad_key, float* grad_ref, hipStream_t stream);
+
 // Kernel-span stamps (measurement aid behind bench.py's roofline).  While a stamp buffer is armed
 // (vnx_debug_arm_stamps) every launch of a tuned MSDA kernel is handed a region of 2 x gridDim
 // 64-bit slots; each workgroup leaves {its start, its last wave's end} there in constant-rate

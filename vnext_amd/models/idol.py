@@ -31,7 +31,7 @@ from torch import nn
 from ..heads import dynamic_mask_head, loss_reid
 from ..registry import META_ARCH_REGISTRY
 from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
-from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, sample_aux_masks, select_pos_neg_masks
+from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, reid_terms_fused, sample_aux_masks, select_pos_neg_masks
 from .idol_transformer import DeformableTransformer
 from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
 from .seqformer_transformer import inverse_sigmoid
@@ -289,7 +289,10 @@ class IDOL(nn.Module):
             selections = select_pos_neg_masks(ref_last, ref_logits.sigmoid(), ref_t)
         else:                    # matched on the device above: the sampling loop alone
             selections = sample_aux_masks(pos_neg)
-        qd = reid_terms(embeds[0::2], embeds[1::2], matched, selections, loss_reid)
+        if self.criterion.fused_reid_loss and embeds.is_cuda:     # both reid losses of all images from one op
+            qd = reid_terms_fused(embeds[0::2], embeds[1::2], matched, selections)
+        else:
+            qd = reid_terms(embeds[0::2], embeds[1::2], matched, selections, loss_reid)
         if self.deep_supervision:   # every decoder layer's losses in one pass over stacked tensors
             loss = self.criterion.forward_all_layers(logits, boxes, masks, det_t, indices_list, qd)
         else:

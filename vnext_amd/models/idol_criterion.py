@@ -269,6 +269,9 @@ class IDOLCriterion(nn.Module):
         # class focal + box L1 / GIoU of `forward_all_layers` from the fused op (vnext_amd/ops/set_loss.py; opt-in:
         # train.enable_fused_set_loss).  CUDA tensors only -- there is no fallback behind the switch
         self.fused_set_loss = False
+        # both reid losses of every image from one op (`reid_terms_fused` below, vnext_amd/ops/reid_loss.py; opt-in:
+        # train.enable_fused_reid_loss).  Read by `IDOL.losses`, which takes that path for CUDA embeddings only
+        self.fused_reid_loss = False
 
     @staticmethod
     def _on_device(indices, device):
@@ -457,3 +460,58 @@ def reid_terms(key_embeds, ref_embeds, matched_ids, selections, loss_fn):
         c, a = loss_fn(ref_embeds[i], key_embeds[i, q], pos.to(dev), neg.to(dev), aux_mask.to(dev))
         contrast, aux, count = contrast + c, aux + a, count + len(inst)
     return {"contrast": contrast, "aux": aux, "count": count}
+
+
+def _pack_reid_buffer(matched_ids, selections):
+    """-> (one uint8 host buffer [8 J + J R]: img int32 [J] | key_query int32 [J] | flags uint8 [J, R], J, R, count).
+    Pinned where there is a device to copy to, so that the one upload does not block."""
+    imgs, queries, flag_rows = [], [], []
+    R = 0
+    with _one_thread():
+        for i, (inst, pos, neg, aux) in enumerate(selections):
+            R = max(R, int(pos.shape[0]))
+            if len(inst) == 0:
+                continue
+            imgs.append(torch.full((len(inst),), i, dtype=torch.int32))
+            queries.append(matched_ids[i][inst].to(torch.int32))
+            flag_rows.append((pos.to(torch.uint8) | (neg.to(torch.uint8) << 1) | (aux.to(torch.uint8) << 2)).t())
+        J = sum(len(q) for q in queries)
+        buf = torch.empty(8 * J + J * R, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        if J:
+            img, key_query, flags = _split_reid_buffer(buf, J, R)
+            torch.cat(imgs, out=img)
+            torch.cat(queries, out=key_query)
+            torch.cat(flag_rows, out=flags)
+    return buf, J, R, J
+
+
+def _split_reid_buffer(buf, J, R):
+    """views of the packed buffer, on whichever device it lives"""
+    return buf[:4 * J].view(torch.int32), buf[4 * J:8 * J].view(torch.int32), buf[8 * J:].view(J, R)
+
+
+def pack_reid_selections(matched_ids, selections):
+    """The per-image (inst, pos, neg, aux) of `sample_aux_masks` / `select_pos_neg_masks` and the matcher's best query per
+    box as the flat instance list of vnext_amd/ops/reid_loss.py, on the host: images in order, an image's instances in
+    `inst` order, an image without a valid instance contributes no rows.
+    -> (img int32 [J], key_query int32 [J], flags uint8 [J, R]: bit 0 positive, bit 1 negative, bit 2 aux sample, count):
+    three views of ONE staging buffer (pinned where a device exists), so that one copy takes all of them up."""
+    buf, J, R, count = _pack_reid_buffer(matched_ids, selections)
+    return _split_reid_buffer(buf, J, R) + (count,)
+
+
+def reid_terms_fused(key_embeds, ref_embeds, matched_ids, selections):
+    """`reid_terms(key_embeds, ref_embeds, matched_ids, selections, heads.loss_reid)` from ONE call of the fused op: one
+    packed non-blocking upload instead of four pageable ones per image, one launch forward and two backward whatever the
+    batch.  Same dict: {"contrast", "aux", "count"}.  Sizes outside the op's limits (checked here, on the host, before
+    anything is launched) go through `reid_terms`."""
+    from ..ops.reid_loss import reid_contrastive_losses, supported
+    buf, J, R, count = _pack_reid_buffer(matched_ids, selections)
+    if count == 0:
+        return {"contrast": 0, "aux": 0, "count": 0}
+    if R != ref_embeds.shape[1] or not supported(int(key_embeds.shape[1]), R, int(key_embeds.shape[2])):
+        from ..heads import loss_reid
+        return reid_terms(key_embeds, ref_embeds, matched_ids, selections, loss_reid)
+    img, key_query, flags = _split_reid_buffer(buf.to(key_embeds.device, non_blocking=True), J, R)
+    sums = reid_contrastive_losses(key_embeds, ref_embeds, img, key_query, flags).sum(0)
+    return {"contrast": sums[0], "aux": sums[1], "count": count}

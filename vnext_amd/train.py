@@ -334,6 +334,18 @@ def enable_fused_set_loss(model, on: bool = True) -> None:
     criterion.fused_set_loss = bool(on)
 
 
+def enable_fused_reid_loss(model, on: bool = True) -> None:
+    """Opt in to the fused reid losses (`criterion.fused_reid_loss`, vnext_amd/ops/reid_loss.py): IDOL's contrastive and
+    auxiliary cosine losses of every image of a step from one op -- one packed upload, one launch forward and two backward
+    whatever the batch, instead of a per-image loop of small launches.  Same loss names and numbers, the sums
+    reassociated; the negatives are still drawn by the host generator.  Taken for CUDA embeddings; on the CPU the per-image
+    path runs as before.  Raises for an object whose criterion has no such switch (SeqFormer has no reid losses)."""
+    criterion = getattr(model, "criterion", None)
+    if criterion is None or not hasattr(criterion, "fused_reid_loss"):
+        raise ValueError("enable_fused_reid_loss: %s has no criterion with a fused_reid_loss switch" % type(model).__name__)
+    criterion.fused_reid_loss = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
