@@ -460,6 +460,20 @@ int vnx_time_weighted_sum_backward(int dtype, const void* grad_out, const void* 
  * height, width, heads, window) bytes = batch * windows * heads * ((2 w - 1)^2 + 64) * 4, windows = ceil(height / w) *
  * ceil(width / w).  No atomics: the table and pad-bias gradients are per-workgroup partials reduced in a fixed order,
  * bit-identical run to run.  No allocation, no synchronisation: capturable in a hipGraph.
+ * dtype: VNX_F32 (all arrays fp32, as above), or VNX_BF16 (additive: a value that used to be refused; no symbol or signature
+ * changed, VNX_ABI_VERSION stays 17) -- the matrix-core instantiation (window_attn_mfma.hip) for the output of a bf16 qkv
+ * GEMM under autocast.  VNX_F16 and everything else: VNX_ERR_UNSUPPORTED before any launch.  With VNX_BF16:
+ *   - qkv, out, grad_out and grad_qkv are bf16; qkv_bias, bias_table, lse, grad_bias_table, grad_pad_bias and partial stay
+ *     fp32 (they are fp32 parameters under autocast); same shapes, same limits, same partial size;
+ *   - row_stride is in ELEMENTS and must be a multiple of 8 (16-byte rows; fp32: a multiple of 4), the same five pointers
+ *     16-byte aligned;
+ *   - bf16 rounding happens at the matrix-core operands -- q, k, v = bf16_rne(float(qkv) + qkv_bias), the probabilities p
+ *     for the p v product, dS for the grad_q product, grad_out as it arrives -- and at the final stores of out and
+ *     grad_qkv, nowhere else; for grad_v = p^T grad_out and grad_k = dS^T q, which sum over the (possibly few) real query
+ *     rows, p and dS enter as two bf16 terms each (the rounded value and the bf16 of what the rounding left): scale (applied to the fp32 score), the bias-table and mask adds,
+ *     max / sum / lse, D = rowsum(p o dP), dS = p (dP - D), every accumulator and the table / pad-bias partials are fp32.
+ *     The backward does not read `out` (D comes from its own p and dP); pass it all the same.
+ *   Forward and backward are bit-identical run to run; no atomics.
  */
 size_t vnx_window_attention_partial_bytes(int batch, int height, int width, int heads, int window);
 int vnx_window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out,

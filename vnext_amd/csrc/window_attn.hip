@@ -29,28 +29,20 @@
 //     over the query rows at that relative offset, fixed order), and the k / v gradients of the padded tokens summed in row
 //     order: [(2 w - 1)^2 + 64] partial floats per workgroup, reduced over the workgroups in a fixed order by a second
 //     launch.  No atomics anywhere: the table and pad-bias gradients are bit-identical run to run.
-#include "vnx_common.h"
+//
+// dtype VNX_BF16 at the two entry points below goes, after the same argument checks (row stride a multiple of 8 elements
+// instead of 4), to the matrix-core kernels of window_attn_mfma.hip, which leave the same partials for the reduction here.
+#include "window_attn.h"
 
 namespace vnx {
 
 typedef float wa_f4 __attribute__((ext_vector_type(4)));
 
-constexpr int kWaHd = 32;                    // channels per head
-constexpr int kWaMaxWin = 12;                // window sizes 1..12
-constexpr int kWaMaxN = kWaMaxWin * kWaMaxWin;
-constexpr int kWaMaxT = (2 * kWaMaxWin - 1) * (2 * kWaMaxWin - 1);
 constexpr int kWaThreads = 192;              // >= kWaMaxN, a multiple of 64
 constexpr int kWaSPad = kWaMaxN + 1;         // floats per dS row in LDS (odd: thread i reading row i hits bank 17 i mod 64)
 constexpr int kWaRedSlices = 16;             // workgroup slices of the partial reduction
-constexpr float kWaMask = -100.0f;
 
-struct WaArgs {
-  const float* qkv;      // [B * H * W][ld], q | k | v, no bias
-  const float* bias;     // [3 C] or null
-  const float* table;    // [(2 w - 1)^2][heads]
-  int B, H, W, heads, ld, w, s, Hp, Wp, nwx, nwin;     // nwin = windows per image
-  float scale;
-};
+// (WaArgs and the index helpers wa_token / wa_region / wa_rel: window_attn.h, shared with the bf16 matrix-core kernels)
 
 struct WaRow {
   wa_f4 v[8];
@@ -85,25 +77,6 @@ __device__ __forceinline__ void wa_axpy(WaRow& y, float a, const WaRow& x) {
   for (int i = 0; i < 8; ++i) y.v[i] += a * x.v[i];
 }
 
-// where window row `r` of window `win` (of image b) comes from: its token index in [B * H * W], or -1 for padding
-__device__ __forceinline__ int64_t wa_token(const WaArgs& a, int b, int win, int r) {
-  const int wy = win / a.nwx, wx = win - wy * a.nwx;
-  const int ry = r / a.w, rx = r - ry * a.w;
-  int pi = wy * a.w + ry + a.s, pj = wx * a.w + rx + a.s;
-  if (pi >= a.Hp) pi -= a.Hp;
-  if (pj >= a.Wp) pj -= a.Wp;
-  if (pi >= a.H || pj >= a.W) return -1;
-  return (int64_t(b) * a.H + pi) * a.W + pj;
-}
-// region label (0..8) of the shifted-grid position of window row `r` (only read when s > 0)
-__device__ __forceinline__ int wa_region(const WaArgs& a, int win, int r) {
-  const int wy = win / a.nwx, wx = win - wy * a.nwx;
-  const int ry = r / a.w, rx = r - ry * a.w;
-  const int i = wy * a.w + ry, j = wx * a.w + rx;
-  const int li = i < a.Hp - a.w ? 0 : (i < a.Hp - a.s ? 1 : 2);
-  const int lj = j < a.Wp - a.w ? 0 : (j < a.Wp - a.s ? 1 : 2);
-  return li * 3 + lj;
-}
 // the 32 channels of head h, section sec (0 q, 1 k, 2 v) of a token (bias added); padding = the bias alone
 __device__ __forceinline__ WaRow wa_global_row(const WaArgs& a, int64_t tok, int h, int sec) {
   WaRow o;
@@ -122,12 +95,6 @@ __device__ __forceinline__ WaRow wa_global_row(const WaArgs& a, int64_t tok, int
   }
   return o;
 }
-// relative-position table index of (query row ri, key row rj)
-__device__ __forceinline__ int wa_rel(int ri, int rj, int w) {
-  const int yi = ri / w, xi = ri - yi * w, yj = rj / w, xj = rj - yj * w;
-  return (yi - yj + w - 1) * (2 * w - 1) + (xi - xj + w - 1);
-}
-
 // grid: B * nwin * heads workgroups (head fastest: the workgroups of one window read the same token rows)
 __global__ void __launch_bounds__(kWaThreads) window_attn_fwd_kernel(WaArgs a, float* __restrict__ out,
                                                                      float* __restrict__ lse) {
@@ -334,8 +301,8 @@ __global__ void __launch_bounds__(kWaRedSlices * 64) window_attn_reduce_kernel(c
 
 static int wa_check(const char* fn, int dtype, int batch, int height, int width, int heads, int head_dim, int ld, int w,
                     int s) {
-  if (dtype != VNX_F32) {
-    set_error("%s: fp32 only (dtype %d)", fn, dtype);
+  if (dtype != VNX_F32 && dtype != VNX_BF16) {
+    set_error("%s: fp32 or bf16 only (dtype %d)", fn, dtype);
     return VNX_ERR_UNSUPPORTED;
   }
   if (head_dim != kWaHd) {
@@ -346,7 +313,8 @@ static int wa_check(const char* fn, int dtype, int batch, int height, int width,
     set_error("%s: window %d / heads %d outside 1..%d / 1..48", fn, w, heads, kWaMaxWin);
     return VNX_ERR_UNSUPPORTED;
   }
-  if (batch < 0 || height < 1 || width < 1 || s < 0 || s >= w || ld < 3 * heads * kWaHd || (ld & 3) != 0) {
+  if (batch < 0 || height < 1 || width < 1 || s < 0 || s >= w || ld < 3 * heads * kWaHd ||
+      (ld & (dtype == VNX_BF16 ? 7 : 3)) != 0) {                 // rows 16-byte aligned: 4 fp32 or 8 bf16 elements
     set_error("%s: bad sizes (batch %d, %d x %d, shift %d, row stride %d)", fn, batch, height, width, s, ld);
     return VNX_ERR_INVALID_ARGUMENT;
   }
@@ -397,6 +365,7 @@ int window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, c
     return VNX_ERR_INVALID_ARGUMENT;
   }
   const WaArgs a = wa_args(qkv, qkv_bias, bias_table, batch, height, width, heads, row_stride, window, shift, scale);
+  if (dtype == VNX_BF16) return window_attention_mfma_forward(a, out, lse, (hipStream_t)hip_stream);
   const int threads = (window * window + 63) / 64 * 64;
   hipLaunchKernelGGL(window_attn_fwd_kernel, dim3(uint32_t(int64_t(batch) * a.nwin * heads)), dim3(threads), 0,
                      (hipStream_t)hip_stream, a, (float*)out, (float*)lse);
@@ -427,10 +396,14 @@ int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, 
   const WaArgs a = wa_args(qkv, qkv_bias, bias_table, batch, height, width, heads, row_stride, window, shift, scale);
   const int threads = (window * window + 63) / 64 * 64;
   const int groups = batch * a.nwin;
-  hipLaunchKernelGGL(window_attn_bwd_kernel, dim3(uint32_t(int64_t(groups) * heads)), dim3(threads), 0,
-                     (hipStream_t)hip_stream, a, (const float*)out, (const float*)lse, (const float*)grad_out,
-                     (float*)grad_qkv, (float*)partial);
-  if (int st = check_launch("window_attn_bwd")) return st;
+  if (dtype == VNX_BF16) {                            // the matrix-core kernel leaves the same partials
+    if (int st = window_attention_mfma_backward(a, out, lse, grad_out, grad_qkv, partial, (hipStream_t)hip_stream)) return st;
+  } else {
+    hipLaunchKernelGGL(window_attn_bwd_kernel, dim3(uint32_t(int64_t(groups) * heads)), dim3(threads), 0,
+                       (hipStream_t)hip_stream, a, (const float*)out, (const float*)lse, (const float*)grad_out,
+                       (float*)grad_qkv, (float*)partial);
+    if (int st = check_launch("window_attn_bwd")) return st;
+  }
   const int T = (2 * window - 1) * (2 * window - 1);
   hipLaunchKernelGGL(window_attn_reduce_kernel, dim3(uint32_t((T + 64 + 63) / 64), uint32_t(heads)),
                      dim3(kWaRedSlices * 64), 0, (hipStream_t)hip_stream, (const float*)partial, groups, heads, T,

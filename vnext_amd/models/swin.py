@@ -85,6 +85,9 @@ class WindowAttention(nn.Module):
         self.attn_drop = nn.Dropout(attn_drop)
         self.proj = nn.Linear(dim, dim)
         self.proj_drop = nn.Dropout(proj_drop)
+        # opt-in (train.enable_bf16_window_attention): under torch.autocast(bfloat16) on CUDA the attention core takes the
+        # bf16 qkv rows as the GEMM left them and runs on the matrix cores; off = the fp32 core (custom_fwd casts up)
+        self.bf16_core = False
         nn.init.trunc_normal_(self.relative_position_bias_table, std=0.02, a=-2.0, b=2.0)
 
 

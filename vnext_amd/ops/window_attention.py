@@ -26,6 +26,12 @@ tensors, VNX_FUSED_WINDOW_ATTN=0 (the A/B switch), head_dim != 32, window > 12, 
 (`attn_drop > 0` while training: the kernel has no dropout; every reference config uses 0.0) -- the block IS the reference
 expression, evaluated by torch.  Under torch.autocast the qkv GEMM runs in the autocast dtype and the attention core in fp32
 (custom_fwd casts its inputs).
+
+Opt-in, `WindowAttention.bf16_core` (train.enable_bf16_window_attention): when the switch is on, the tensors are on CUDA,
+autocast is enabled with dtype bfloat16 and the qkv GEMM's output is bf16, the core is `_WindowAttentionBF16` instead --
+the same entry points with dtype VNX_BF16 (vnext_amd/csrc/window_attn_mfma.hip): bf16 qkv in as the GEMM left it, bf16
+context out for proj, every product on the matrix cores, scores / softmax / lse / accumulators fp32, no fp32 copy of qkv
+anywhere.  In every other case (fp32 input, fp16 autocast, CPU, the cases above) the switch changes nothing.
 """
 from __future__ import annotations
 
@@ -85,6 +91,51 @@ class _WindowAttention(torch.autograd.Function):
                 g_pad.data_ptr() if g_pad is not None else None, partial.data_ptr(), partial.numel() * 4,
                 B, H, W, heads, HEAD_DIM, 3 * C, window, shift, scale, _lib.current_stream(qkv)))
         g_bias = g.sum(0) + g_pad if qkv_bias is not None else None
+        return g, g_bias, g_table, None, None, None, None, None, None, None
+
+
+class _WindowAttentionBF16(torch.autograd.Function):
+    """The bf16 core: qkv bf16 [B * H * W, 3 C] as the qkv GEMM left it (no bias), qkv_bias / table fp32 -> the context
+    bf16 [B * H * W, C].  No cast_inputs: called under bf16 autocast, it keeps the types it is given."""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, table, B, H, W, heads, window, shift, scale):
+        lib = _lib.lib()
+        qkv = qkv.contiguous()
+        table = table.contiguous()
+        C = qkv.shape[1] // 3
+        out = torch.empty(qkv.shape[0], C, dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty(qkv.shape[0], heads, dtype=torch.float32, device=qkv.device)
+        with torch.cuda.device(qkv.device):
+            _lib.check(lib.vnx_window_attention_forward(
+                _lib.VNX_BF16, qkv.data_ptr(), qkv_bias.data_ptr() if qkv_bias is not None else None, table.data_ptr(),
+                out.data_ptr(), lse.data_ptr(), B, H, W, heads, HEAD_DIM, 3 * C, window, shift, float(scale),
+                _lib.current_stream(qkv)))
+        ctx.save_for_backward(qkv, qkv_bias, table, out, lse)
+        ctx.dims = (B, H, W, heads, window, shift, float(scale))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        lib = _lib.lib()
+        qkv, qkv_bias, table, out, lse = ctx.saved_tensors
+        B, H, W, heads, window, shift, scale = ctx.dims
+        grad_out = grad_out.to(torch.bfloat16).contiguous()
+        C = qkv.shape[1] // 3
+        g = torch.empty_like(qkv)
+        g_table = torch.empty_like(table)
+        g_pad = torch.empty(3 * C, dtype=torch.float32, device=qkv.device) if qkv_bias is not None else None
+        nbytes = lib.vnx_window_attention_partial_bytes(B, H, W, heads, window)
+        partial = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=qkv.device)
+        with torch.cuda.device(qkv.device):
+            _lib.check(lib.vnx_window_attention_backward(
+                _lib.VNX_BF16, qkv.data_ptr(), qkv_bias.data_ptr() if qkv_bias is not None else None, table.data_ptr(),
+                out.data_ptr(), lse.data_ptr(), grad_out.data_ptr(), g.data_ptr(), g_table.data_ptr(),
+                g_pad.data_ptr() if g_pad is not None else None, partial.data_ptr(), partial.numel() * 4,
+                B, H, W, heads, HEAD_DIM, 3 * C, window, shift, scale, _lib.current_stream(qkv)))
+        # the column sum in fp32: a bf16 sum over the tokens would lose the bias gradient
+        g_bias = g.sum(0, dtype=torch.float32) + g_pad if qkv_bias is not None else None
         return g, g_bias, g_table, None, None, None, None, None, None, None
 
 
@@ -176,6 +227,11 @@ def window_attention_block(x, H, W, attn, window, shift):
         return reference_block(x, H, W, attn, window, shift)
     B, L, C = x.shape
     qkv = F.linear(x.reshape(B * L, C), attn.qkv.weight)
+    if (getattr(attn, "bf16_core", False) and torch.is_autocast_enabled()
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16 and qkv.dtype == torch.bfloat16):
+        ctxt = _WindowAttentionBF16.apply(qkv, attn.qkv.bias, attn.relative_position_bias_table, B, H, W,
+                                          attn.num_heads, window, shift, attn.scale)
+        return attn.proj_drop(attn.proj(ctxt)).view(B, L, C)
     ctxt = _WindowAttention.apply(qkv, attn.qkv.bias, attn.relative_position_bias_table, B, H, W, attn.num_heads, window,
                                   shift, attn.scale)
     return attn.proj_drop(attn.proj(ctxt)).view(B, L, C)

@@ -346,6 +346,20 @@ def enable_fused_reid_loss(model, on: bool = True) -> None:
     criterion.fused_reid_loss = bool(on)
 
 
+def enable_bf16_window_attention(model, on: bool = True) -> None:
+    """Opt in to the bf16 window-attention core (`WindowAttention.bf16_core`, vnext_amd/ops/window_attention.py) on every
+    Swin block of the model: under `torch.autocast(bfloat16)` on CUDA the core reads the bf16 qkv rows as the qkv GEMM
+    left them, runs its products on the matrix cores and hands bf16 rows to proj -- no fp32 copy of qkv, no cast back.
+    Scores, softmax and accumulators stay fp32.  Without bf16 autocast (fp32 input, fp16 autocast, CPU) the switch
+    changes nothing.  Raises for a model without a WindowAttention (the ResNet trunks)."""
+    from .models.swin import WindowAttention
+    mods = [m for m in model.modules() if isinstance(m, WindowAttention)]
+    if not mods:
+        raise ValueError("enable_bf16_window_attention: %s has no WindowAttention" % type(model).__name__)
+    for m in mods:
+        m.bf16_core = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
