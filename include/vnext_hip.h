@@ -721,6 +721,55 @@ int vnx_reid_loss_backward(const void* key, long long key_image_stride, int key_
                            const void* key_query, const void* flags, int instances, const void* dot, const void* ref_norm,
                            const void* stats, const void* grad_out, void* grad_key, void* grad_ref, void* hip_stream);
 
+/*
+ * The element-wise glue of a Swin stage (swin_glue.hip): stochastic depth + residual add + the pre-norm LayerNorm of the
+ * next branch, and PatchMerging's pad + 2x2 gather + LayerNorm.  ADDITIVE: five symbols, no existing signature changed, so
+ * VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * Residual + LayerNorm.  Rows of `channels` values, contiguous; sample b owns rows [b, b + 1) * rows_per_sample:
+ *   y[r] = x[r] + scale[b] * a[r]                        scale fp32 [samples] on the device, or null = 1
+ *   n[r] = LayerNorm(y[r]; gamma, beta, eps)             stats fp32 [rows][2] = (mean, rstd), written with n
+ * a null: y = x and y is not written (pass y null): a plain LayerNorm.  gamma null: no n, no stats (pass beta, n, stats
+ * null): a plain scaled add.  Both null is an error.  A sample whose scale is 0 does not read its branch: its y equals x bit
+ * for bit, and the backward writes exactly 0 into its grad_a.
+ * Types (x_dtype names x, y, grad_y, grad_x; a_dtype a and grad_a; n_dtype n and grad_n): exactly
+ *   (VNX_F32, VNX_F32, VNX_F32), (VNX_F32, VNX_BF16, VNX_BF16), (VNX_BF16, VNX_BF16, VNX_BF16)
+ * -- what the library chain produces without autocast, under bf16 autocast on an fp32 stream, and on a bf16 stream.  Pass
+ * the triple also where a or n is null.  gamma, beta, scale, stats and all arithmetic are fp32; n is the LayerNorm of y as
+ * STORED (a bf16 stream: of the rounded y), which is what the backward recomputes xhat from.
+ * Backward: grad_y and grad_n may each be null (= zero; grad_n must be null where gamma is).  g = grad_y +
+ * LayerNormBackward(grad_n; y, stats, gamma);  grad_x = g;  grad_a = scale[b] * g (null: not wanted).  Every element of
+ * grad_x and grad_a is written -- no memset, no accumulation.  With gamma: grad_gamma and grad_beta fp32 [channels] leave
+ * as per-workgroup partial rows in `partial` (at least vnx_swin_glue_partial_bytes(rows, channels) bytes, sized by the
+ * launch and not by a maximum; need not be zeroed), which a finishing launch adds in a fixed order.  No atomics:
+ * bit-identical run to run.  rows == 0 is valid (the parameter gradients are zero).
+ *
+ * PatchMerging gather + LayerNorm.  x [batch][height][width][channels] (x_dtype), n [batch][ceil(height / 2) *
+ * ceil(width / 2)][4 * channels] (n_dtype): the row of output token (i, j) is x[2i][2j] | x[2i+1][2j] | x[2i][2j+1] |
+ * x[2i+1][2j+1], a position outside the grid contributing zeros (the reference's pad of an odd height or width), normalised
+ * over 4 * channels; stats fp32 [output rows][2].  No padded copy, no concatenated copy.  Types (x_dtype, n_dtype):
+ * (VNX_F32, VNX_F32), (VNX_F32, VNX_BF16), (VNX_BF16, VNX_BF16).  Backward: every element of grad_x (x's shape and type)
+ * is written by the one output row that owns it; grad_gamma / grad_beta fp32 [4 * channels] as above, `partial` at least
+ * vnx_swin_glue_partial_bytes(output rows, 4 * channels) bytes.
+ *
+ * VNX_ERR_UNSUPPORTED before any launch: another type triple; a row width (channels; 4 * channels of the merge) outside
+ * [32, 3072] or no multiple of 8; a pointer that is not 16-byte aligned.  All accesses are 16 bytes wide.  One launch
+ * forward; backward one launch, two with a LayerNorm.  No allocation, no synchronisation: capturable in a hipGraph.
+ */
+size_t vnx_swin_glue_partial_bytes(long long rows, int channels);
+int vnx_swin_residual_norm_forward(int x_dtype, int a_dtype, int n_dtype, const void* x, const void* a, const void* scale,
+                                   const void* gamma, const void* beta, void* y, void* n, void* stats, long long rows,
+                                   int channels, long long rows_per_sample, float eps, void* hip_stream);
+int vnx_swin_residual_norm_backward(int x_dtype, int a_dtype, int n_dtype, const void* grad_y, const void* grad_n,
+                                    const void* y, const void* stats, const void* gamma, const void* scale, void* grad_x,
+                                    void* grad_a, void* grad_gamma, void* grad_beta, void* partial, size_t partial_bytes,
+                                    long long rows, int channels, long long rows_per_sample, void* hip_stream);
+int vnx_swin_merge_norm_forward(int x_dtype, int n_dtype, const void* x, const void* gamma, const void* beta, void* n,
+                                void* stats, int batch, int height, int width, int channels, float eps, void* hip_stream);
+int vnx_swin_merge_norm_backward(int x_dtype, int n_dtype, const void* grad_n, const void* x, const void* stats,
+                                 const void* gamma, void* grad_x, void* grad_gamma, void* grad_beta, void* partial,
+                                 size_t partial_bytes, int batch, int height, int width, int channels, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

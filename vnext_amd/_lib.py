@@ -77,6 +77,11 @@ SIGNATURES = {
     "vnx_idol_match": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _i, _vp]),
     "vnx_reid_loss_forward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 5),
     "vnx_reid_loss_backward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 7),
+    "vnx_swin_glue_partial_bytes": (_sz, [_ll, _i]),
+    "vnx_swin_residual_norm_forward": (_i, [_i] * 3 + [_vp] * 8 + [_ll, _i, _ll, ctypes.c_float, _vp]),
+    "vnx_swin_residual_norm_backward": (_i, [_i] * 3 + [_vp] * 11 + [_sz, _ll, _i, _ll, _vp]),
+    "vnx_swin_merge_norm_forward": (_i, [_i] * 2 + [_vp] * 5 + [_i] * 4 + [ctypes.c_float, _vp]),
+    "vnx_swin_merge_norm_backward": (_i, [_i] * 2 + [_vp] * 8 + [_sz] + [_i] * 4 + [_vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

@@ -8,6 +8,9 @@ relative_position_index}, norm2, mlp.{fc1, fc2}}, layers.i.downsample.{norm, red
 
 The shifted-window attention of every block is vnext_amd/ops/window_attention.py (one HIP launch each way on the GPU;
 the reference expression by torch on CPU).  LayerNorm, the MLP, PatchMerging and the patch embedding are library ops.
+Opt-in (`BasicLayer.fused_glue` / `PatchMerging.fused_glue`, train.enable_fused_swin_glue): the stochastic depth, residual
+add and LayerNorm around the two branches of every block, and PatchMerging's pad + gather + LayerNorm, run through
+vnext_amd/ops/swin_glue.py (one HIP pass per site each way on the GPU; the same expression by torch elsewhere).
 
 Differences from the reference, all outside the numbers: APE (absolute position embedding) is rejected (no config enables
 it), USE_CHECKPOINT is rejected (activation checkpointing is not built), and timm's DropPath / trunc_normal_ are replaced by
@@ -19,6 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import swin_glue
 from ..ops.window_attention import window_attention_block
 
 
@@ -122,10 +126,13 @@ class PatchMerging(nn.Module):
         self.dim = dim
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
         self.norm = norm_layer(4 * dim)
+        self.fused_glue = False      # opt-in (train.enable_fused_swin_glue): pad + gather + norm in one pass (ops/swin_glue.py)
 
     def forward(self, x, H, W):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
+        if self.fused_glue:
+            return self.reduction(swin_glue.merge_norm(x, H, W, self.norm))
         x = x.view(B, H, W, C)
         if H % 2 == 1 or W % 2 == 1:
             x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
@@ -153,10 +160,31 @@ class BasicLayer(nn.Module):
                                  norm_layer=norm_layer)
             for i in range(depth)])
         self.downsample = downsample(dim=dim, norm_layer=norm_layer) if downsample is not None else None
+        # opt-in (train.enable_fused_swin_glue): every residual add (with its stochastic depth) is fused with the LayerNorm
+        # that follows it -- norm2 inside a block, the NEXT block's norm1 between blocks (ops/swin_glue.py)
+        self.fused_glue = False
+
+    def _blocks_fused(self, x, H, W):
+        """The blocks with (x, n) threaded through them: x the residual stream, n the LayerNorm of it the next branch reads.
+        The same function as the loop over blk(x, H, W); the stochastic-depth masks are drawn at the same points."""
+        assert x.shape[1] == H * W, "input feature has wrong size"
+        blocks = list(self.blocks)
+        _, n = swin_glue.residual_norm(x, None, None, blocks[0].norm1)
+        for i, blk in enumerate(blocks):
+            p = getattr(blk.drop_path, "drop_prob", 0.0)
+            a = window_attention_block(n, H, W, blk.attn, blk.window_size, blk.shift_size)
+            x, n = swin_glue.residual_norm(x, a, swin_glue.drop_scale(a, p, blk.drop_path.training), blk.norm2)
+            a = blk.mlp(n)
+            x, n = swin_glue.residual_norm(x, a, swin_glue.drop_scale(a, p, blk.drop_path.training),
+                                           blocks[i + 1].norm1 if i + 1 < len(blocks) else None)
+        return x
 
     def forward(self, x, H, W):
-        for blk in self.blocks:
-            x = blk(x, H, W)
+        if self.fused_glue and len(self.blocks) > 0:
+            x = self._blocks_fused(x, H, W)
+        else:
+            for blk in self.blocks:
+                x = blk(x, H, W)
         if self.downsample is not None:
             return x, H, W, self.downsample(x, H, W), (H + 1) // 2, (W + 1) // 2
         return x, H, W, x, H, W

@@ -360,6 +360,23 @@ def enable_bf16_window_attention(model, on: bool = True) -> None:
         m.bf16_core = bool(on)
 
 
+def enable_fused_swin_glue(model, on: bool = True) -> None:
+    """Opt in to the fused element-wise glue of the Swin stages (`BasicLayer.fused_glue`, `PatchMerging.fused_glue`,
+    vnext_amd/ops/swin_glue.py): each residual add, with its stochastic depth, and the LayerNorm that follows it are one
+    HIP pass each way -- the first block's norm1 a plain norm, each block's closing residual fused with the next block's
+    norm1, the stage's last one a plain scaled add -- and PatchMerging's pad, 2x2 gather and LayerNorm are one pass
+    without the padded and concatenated copies.  Under `torch.autocast(bfloat16)` the normalised rows leave as bf16, the
+    cast the next Linear would make.  Same modules and state-dict names, the same masks under the same seed, the sums
+    reassociated.  On the CPU, under fp16 autocast and for other types or widths the same expression runs through
+    torch.  Raises for a model without a Swin backbone (the ResNet trunks)."""
+    from .models.swin import BasicLayer, PatchMerging
+    mods = [m for m in model.modules() if isinstance(m, (BasicLayer, PatchMerging))]
+    if not mods:
+        raise ValueError("enable_fused_swin_glue: %s has no Swin stage" % type(model).__name__)
+    for m in mods:
+        m.fused_glue = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
