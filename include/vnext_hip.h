@@ -770,6 +770,42 @@ int vnx_swin_merge_norm_backward(int x_dtype, int n_dtype, const void* grad_n, c
                                  const void* gamma, void* grad_x, void* grad_gamma, void* grad_beta, void* partial,
                                  size_t partial_bytes, int batch, int height, int width, int channels, void* hip_stream);
 
+/*
+ * Detection selection of a batch of images (det_select.hip): best class per query, score threshold, class-aware greedy
+ * box NMS and the top-k over (kept query, class) -- IDOL's per-frame candidate selection and its COCO-pretrain inference.
+ * ADDITIVE: two symbols, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the
+ * symbols up.
+ *
+ * One launch, one workgroup (four wave64) per image.  logits fp32 [batch][queries][classes] (pre-sigmoid), boxes fp32
+ * [batch][queries][4] = (cx, cy, w, h), both contiguous, boxes 16-byte aligned.  Per image:
+ *   1. every query's label = the first argmax of its logits (equal maxima: the lowest class);
+ *   2. candidates = the queries with 1 / (1 + expf(-max logit)) > score_thr in fp32.  A negative score_thr admits every
+ *      query.  No candidate: the result is the single best query (the lowest index among equals) and no NMS runs;
+ *   3. the candidates in (max logit descending, query index ascending) order -- the logit, not its sigmoid;
+ *   4. greedy NMS in that order: a live candidate removes every later one with the same label and IoU > iou_thr; a removed
+ *      one removes nothing.  xyxy = c -+ 0.5 * wh, area = (x1 - x0) * (y1 - y0), IoU = inter / (area_a + area_b - inter)
+ *      with inter the product of the clamped overlaps: fp32, no contraction, IEEE division -- the comparison agrees bit for
+ *      bit with the same expression on the host; 0 / 0 compares false;
+ *   5. topk > 0: the min(topk, kept * classes) largest logits of the kept queries, in (logit descending, flat index
+ *      position_in_kept_order * classes + class ascending) order.
+ * Scores are not produced: a caller forms them from the logits it holds.  Integer LDS counters only, every global result a
+ * plain store: bit-identical run to run.  No workspace, no allocation, no synchronisation.  A call with more than 64 KB of
+ * LDS (queries above 720) raises the kernel's dynamic-LDS limit with hipFuncSetAttribute, once per device, the first time
+ * such a call is made there: make that call once outside a stream capture.
+ * out int32 [batch][out_stride], out_stride >= vnx_det_select_out_words(queries, topk) = 4 + 2 queries + 2 topk:
+ *   [0] status: 0 ok; 1 a non-finite logit or box in this image: nothing selected, [1] = [2] = 0, every list -1
+ *   [1] kept queries   [2] top-k entries   [3] 0
+ *   [4, 4 + queries) the kept queries in NMS order, then -1
+ *   [4 + queries, 4 + 2 queries) every query's label
+ *   then topk pairs (query, class), the unused ones -1.  Words of the stride beyond that are not written.
+ * batch == 0: VNX_OK, no launch.  VNX_ERR_UNSUPPORTED before any launch, the output untouched: queries above what the LDS
+ * of a CU holds (1280: 256 W (W + 1) + 40 queries + 8 W + 3136 bytes with W = ceil(queries / 64), against 163 840),
+ * classes above 4096, queries * classes >= 2^24, topk above 256, or a device that refuses the dynamic-LDS limit.
+ */
+int vnx_det_select_out_words(int queries, int topk);
+int vnx_det_select(const void* logits, const void* boxes, int batch, int queries, int classes, float score_thr,
+                   float iou_thr, int topk, void* out, int out_stride, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

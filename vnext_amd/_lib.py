@@ -75,6 +75,8 @@ SIGNATURES = {
     "vnx_idol_match_max_targets": (_i, [_i]),
     "vnx_idol_match_out_words": (_i, [_i, _i]),
     "vnx_idol_match": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _i, _vp]),
+    "vnx_det_select_out_words": (_i, [_i, _i]),
+    "vnx_det_select": (_i, [_vp, _vp, _i, _i, _i, ctypes.c_float, ctypes.c_float, _i, _vp, _i, _vp]),
     "vnx_reid_loss_forward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 5),
     "vnx_reid_loss_backward": (_i, [_vp, _ll, _i, _vp, _ll, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 7),
     "vnx_swin_glue_partial_bytes": (_sz, [_ll, _i]),

@@ -857,6 +857,17 @@ int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_
                          valid_first, targets_max, (int32_t*)out, out_stride, (hipStream_t)hip_stream);
 }
 
+// ---- detection selection: best class, score threshold, class-aware NMS, top-k (det_select.hip: the argument checks live beside the kernel's LDS layout) ----
+int vnx_det_select_out_words(int queries, int topk) {
+  return queries < 1 || topk < 0 ? 0 : vnx::det_select_out_words(queries, topk);
+}
+
+int vnx_det_select(const void* logits, const void* boxes, int batch, int queries, int classes, float score_thr,
+                   float iou_thr, int topk, void* out, int out_stride, void* hip_stream) {
+  return vnx::det_select((const float*)logits, (const float*)boxes, batch, queries, classes, score_thr, iou_thr, topk,
+                         (int32_t*)out, out_stride, (hipStream_t)hip_stream);
+}
+
 // ---- IDOL's reid losses, contrastive + cosine (reid_loss.hip: the argument checks live beside the kernels' addressing limits) ----
 int vnx_reid_loss_forward(const void* key, long long key_image_stride, int key_rows, const void* ref,
                           long long ref_image_stride, int ref_rows, int channels, int images, const void* img,

@@ -150,6 +150,12 @@ int idol_match(const float* det_prob, const float* det_boxes, const float* ref_p
                int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
                int targets_max, int32_t* out, int out_stride, hipStream_t stream);
 
+// det_select.hip (best class, score threshold, class-aware NMS and top-k of a batch of images, one workgroup per image; argument
+// checks there, C entry point in capi.hip)
+int det_select_out_words(int queries, int topk);                // int32 words of one image's output
+int det_select(const float* logits, const float* boxes, int batch, int queries, int classes, float score_thr, float iou_thr,
+               int topk, int32_t* out, int out_stride, hipStream_t stream);
+
 // reid_loss.hip (IDOL's contrastive + cosine reid losses of every instance at once; argument checks there, C entry points in capi.hip)
 int reid_loss_forward(const float* key, int64_t key_stride, int key_rows, const float* ref, int64_t ref_stride, int ref_rows,
                       int channels, int images, const int32_t* img, const int32_t* key_query, const uint8_t* flags,

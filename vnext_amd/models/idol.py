@@ -17,7 +17,10 @@ Mapping onto the machine (the arithmetic and the decisions are the reference's):
   * reid losses: one similarity launch per image on the matrix cores (heads.loss_reid);
   * inference: per-frame candidate selection for the whole chunk from one host copy, mask
     head only for the selected queries (the reference evaluates all 300 per frame, :296-318),
-    tracker with one mask-IoU matrix and one association matrix per frame (models/tracker.py).
+    tracker with one mask-IoU matrix and one association matrix per frame (models/tracker.py);
+  * COCO pre-training evaluation (INPUT.COCO_PRETRAIN, idol.py:235-248, 488-531): images in, per-image instances out;
+    NMS and the top 100 by one kernel for the whole batch (ops/det_select.py), the mask head for the picked queries
+    only (`coco_inference`, `coco_postprocess`, `coco_results`).
 """
 from __future__ import annotations
 
@@ -36,8 +39,11 @@ from .idol_transformer import DeformableTransformer
 from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
+from ..ops.det_select import DetSelectUnsupported, class_aware_nms, select_detections, select_detections_host  # noqa: F401 (class_aware_nms: the host NMS, re-exported)
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import rle_encode, ytvis_records
+
+COCO_NMS_THR, COCO_TOPK, VIDEO_NMS_THR = 0.7, 100, 0.9      # idol.py:502, 507, 340
 
 
 class CondInstSegmIDOL(nn.Module):
@@ -83,26 +89,6 @@ class _TrainTrunk(nn.Module):
         return o._train_trunk(x, mask)
 
 
-def class_aware_nms(boxes_xyxy, scores, classes, thr):
-    """torchvision.ops.batched_nms restated on host arrays (published algorithm: boxes of
-    different classes never suppress each other; greedy by descending score; returns the kept
-    indices in descending-score order)."""
-    order = np.argsort(-scores, kind="stable")
-    b = boxes_xyxy[order]
-    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
-    keep = np.ones(len(order), dtype=bool)
-    for i in range(len(order)):
-        if not keep[i]:
-            continue
-        lt = np.maximum(b[i, :2], b[i + 1:, :2])
-        rb = np.minimum(b[i, 2:], b[i + 1:, 2:])
-        wh = np.clip(rb - lt, 0, None)
-        inter = wh[:, 0] * wh[:, 1]
-        iou = inter / (area[i] + area[i + 1:] - inter)
-        keep[i + 1:] &= ~((iou > thr) & (classes[order[i + 1:]] == classes[order[i]]))
-    return order[keep]
-
-
 @META_ARCH_REGISTRY.register()
 class IDOL(nn.Module):
     def __init__(self, cfg):
@@ -117,6 +103,8 @@ class IDOL(nn.Module):
         self.inference_fw, self.inference_tw = m.INFERENCE_FW, m.INFERENCE_TW
         self.memory_len, self.nms_pre, self.add_new_score = m.MEMORY_LEN, m.NMS_PRE, m.ADD_NEW_SCORE
         self.batch_infer_len = m.BATCH_INFER_LEN
+        self.coco_pretrain = bool(cfg.INPUT.COCO_PRETRAIN)      # eval mode: image-level `coco_inference` (idol.py:235)
+        self.mask_on = bool(cfg.MODEL.MASK_ON)
         hidden = m.HIDDEN_DIM
         transformer = DeformableTransformer(
             d_model=hidden, nhead=m.NHEADS, num_encoder_layers=m.ENC_LAYERS, num_decoder_layers=m.DEC_LAYERS,
@@ -143,6 +131,9 @@ class IDOL(nn.Module):
         # simOTA matching and the contrastive sets by one kernel (vnext_amd/ops/ota_match.py) instead of on the host
         # (opt-in: train.enable_device_matching); CUDA tensors only, the host matcher otherwise
         self.device_matching = False
+        # per-frame candidate selection (score threshold + class-aware NMS) by one kernel for the whole chunk
+        # (vnext_amd/ops/det_select.py) instead of the host loop (opt-in: train.enable_device_selection); CUDA tensors only
+        self.device_selection = False
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -308,6 +299,8 @@ class IDOL(nn.Module):
     def forward(self, batched_inputs):
         if self.training:
             return self.losses(batched_inputs)
+        if self.coco_pretrain:
+            return self.coco_inference(batched_inputs)
         return self.inference_video(batched_inputs)
 
     @torch.no_grad()
@@ -322,7 +315,15 @@ class IDOL(nn.Module):
     def select_candidates(self, logits, boxes):
         """logits [F, Q, K], boxes [F, Q, 4] -> per frame the query indices that enter the tracker
         (idol.py:331-343): best class score above INFERENCE_SELECT_THRES (the top-1 query if none),
-        then class-aware box NMS at 0.9; one host copy for the whole chunk."""
+        then class-aware box NMS at 0.9; one host copy for the whole chunk.  With `device_selection` and CUDA tensors the
+        selection itself runs on the device (ops/det_select.py) and only the picked indices cross; a shape the kernel
+        refuses takes the host loop."""
+        if self.device_selection and logits.is_cuda:
+            try:
+                return list(select_detections(logits, boxes, iou_thr=VIDEO_NMS_THR,
+                                              score_thr=self.inference_select_thres).kept)
+            except DetSelectUnsupported:
+                pass
         best, label = logits.sigmoid().max(-1)
         host = torch.cat([best[..., None], label[..., None].to(best.dtype), box_cxcywh_to_xyxy(boxes)], -1).cpu().numpy()
         picks = []
@@ -332,9 +333,127 @@ class IDOL(nn.Module):
             if len(cand) == 0:
                 cand = np.array([int(np.argmax(score))])
             else:
-                cand = cand[class_aware_nms(bx[cand], score[cand], cls[cand], 0.9)]
+                cand = cand[class_aware_nms(bx[cand], score[cand], cls[cand], VIDEO_NMS_THR)]
             picks.append(cand)
         return picks
+
+    # ---- COCO pre-training evaluation ------------------------------------------------------------
+    @torch.no_grad()
+    def _coco_trunk(self, batched_inputs):
+        """-> logits, boxes, a `masks_of(image, queries)` callable (None with MASK_ON false), image sizes, output sizes"""
+        images = [x["image"].to(self.device, torch.float32) for x in batched_inputs]
+        image_sizes = [tuple(int(v) for v in im.shape[-2:]) for im in images]
+        out_sizes = [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, image_sizes)]
+        logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(images))
+        scale = torch.stack([scale_tensor([w, h], self.device) for h, w in image_sizes])      # [B, (w, h)]: each image's own
+
+        def masks_of(image, queries):
+            """image, queries int64 [n] on the device -> mask logits [n, H/4, W/4] of those queries"""
+            sel_hs = hs_last[image, queries]
+            points = ref_last[image, queries, :2].sigmoid() * scale[image]
+            return dynamic_mask_head(feats, points.float(), self.detr.controller(sel_hs).float(), image.to(torch.int32), 8)
+        return logits, boxes, masks_of if self.mask_on else None, image_sizes, out_sizes
+
+    @torch.no_grad()
+    def _coco_select(self, logits, boxes, masks_of, image_sizes, out_sizes):
+        """The part of `coco_inference` + `segmentation_postprocess` before the masks are formed: per image the output
+        boxes, scores, classes of the rows with a non-empty box, and (with masks) the stride-4 mask logits of those rows."""
+        try:
+            sel = select_detections(logits, boxes, iou_thr=COCO_NMS_THR, topk=COCO_TOPK)
+        except DetSelectUnsupported:      # more queries or classes than the kernel holds: the host expression
+            sel = select_detections_host(logits, boxes, iou_thr=COCO_NMS_THR, topk=COCO_TOPK)
+        dev = logits.device
+        counts = [len(p) for p in sel.topk]
+        image = torch.from_numpy(np.repeat(np.arange(len(counts)), counts)).to(dev)
+        pairs = torch.from_numpy(np.concatenate(sel.topk).reshape(-1, 2)).to(dev)
+        query, cls = pairs[:, 0], pairs[:, 1]
+        scores = logits[image, query, cls].sigmoid()                      # = prob[keep].view(-1)[topk]
+        xyxy = box_cxcywh_to_xyxy(boxes[image, query].float())
+        mask_logits = None
+        if masks_of is not None:     # the mask head once, for the distinct picked queries of all images
+            flat = image * logits.shape[1] + query
+            uniq, inverse = torch.unique(flat, return_inverse=True)
+            mask_logits = masks_of(torch.div(uniq, logits.shape[1], rounding_mode="floor"), uniq % logits.shape[1])[inverse]
+        out, start = [], 0
+        for b, n in enumerate(counts):
+            sl = slice(start, start + n)
+            start += n
+            (ih, iw), (oh, ow) = image_sizes[b], out_sizes[b]
+            bx = xyxy[sl] * scale_tensor([iw, ih, iw, ih], dev)           # Boxes.scale(image size)
+            sx, sy = ow / iw, oh / ih
+            bx = bx * scale_tensor([sx, sy, sx, sy], dev)                 # segmentation_postprocess: scale, clip, drop empty
+            bx = torch.stack([bx[:, 0].clamp(0, ow), bx[:, 1].clamp(0, oh), bx[:, 2].clamp(0, ow), bx[:, 3].clamp(0, oh)], 1)
+            keep = ((bx[:, 2] - bx[:, 0]) > 0) & ((bx[:, 3] - bx[:, 1]) > 0)
+            out.append({"pred_boxes": bx[keep], "scores": scores[sl][keep], "pred_classes": cls[sl][keep],
+                        "mask_logits": None if mask_logits is None else mask_logits[sl][keep]})
+        return out
+
+    @torch.no_grad()
+    def coco_postprocess(self, logits, boxes, masks_of, image_sizes, out_sizes):
+        """`coco_inference` (idol.py:488-531) + `segmentation_postprocess` (segmentation_condInst.py:748-788) on network
+        outputs: logits [B, Q, K], boxes [B, Q, 4] (cxcywh), `masks_of(image, queries) -> [n, H/4, W/4]` mask logits of
+        the named queries (None: no masks), the images' sizes (h, w) before padding and the sizes to report at.
+        -> per image {"instances": {"image_size", "pred_boxes" [n, 4], "scores", "pred_classes", "pred_masks" uint8
+        [n, height, width]}}: plain tensors under the reference's field names.  Selection: ops/det_select.py (the
+        kernel for CUDA tensors; the host expression for a shape it refuses).  Masks: bilinear x4, sigmoid > 0.5, crop to the image, nearest to the output size."""
+        results = []
+        for b, r in enumerate(self._coco_select(logits, boxes, masks_of, image_sizes, out_sizes)):
+            inst = {"image_size": tuple(out_sizes[b]), "pred_boxes": r["pred_boxes"], "scores": r["scores"],
+                    "pred_classes": r["pred_classes"]}
+            if r["mask_logits"] is not None:
+                m = r["mask_logits"][:, None].float()
+                h, w = m.shape[-2:]
+                ih, iw = image_sizes[b]
+                if m.shape[0]:
+                    m = F.interpolate(m, size=(h * 4, w * 4), mode="bilinear", align_corners=False).sigmoid() > 0.5
+                    m = F.interpolate(m[:, :, :ih, :iw].float(), size=tuple(out_sizes[b]), mode="nearest")[:, 0]
+                else:
+                    m = m.new_zeros((0,) + tuple(out_sizes[b]))
+                inst["pred_masks"] = m.to(torch.uint8)
+            results.append({"instances": inst})
+        return results
+
+    @torch.no_grad()
+    def coco_inference(self, batched_inputs):
+        """Eval mode with INPUT.COCO_PRETRAIN (idol.py:235-248): [{"image": [3, h, w], "height", "width"}, ...], one dict
+        per image (sizes may differ) -> [{"instances": {...}}, ...] as `coco_postprocess` forms them.  The mask head runs
+        once, for the distinct picked queries of all images (the reference runs it for all Q)."""
+        return self.coco_postprocess(*self._coco_trunk(batched_inputs))
+
+    @torch.no_grad()
+    def coco_results(self, batched_inputs):
+        """Images -> their COCO result records {"image_id", "category_id", "bbox" (xywh), "score", "segmentation" (RLE)}:
+        the counterpart of `ytvis_results`.  The RLE strings are encoded from the mask logits on the device
+        (ops/mask_rle.py), one call per distinct (image size, output size); no full-resolution mask is formed."""
+        logits, boxes, masks_of, image_sizes, out_sizes = self._coco_trunk(batched_inputs)
+        return self.coco_records(batched_inputs, self._coco_select(logits, boxes, masks_of, image_sizes, out_sizes),
+                                 image_sizes, out_sizes)
+
+    @staticmethod
+    def coco_records(batched_inputs, selected, image_sizes, out_sizes):
+        """`_coco_select`'s rows -> COCO result records, the masks as RLE of the stride-4 logits"""
+        rles = [None] * len(selected)
+        groups = {}
+        for b, r in enumerate(selected):
+            if r["mask_logits"] is not None:
+                groups.setdefault((tuple(image_sizes[b]), tuple(out_sizes[b])), []).append(b)
+        for (isz, osz), members in groups.items():
+            strings = encode_logits(torch.cat([selected[b]["mask_logits"] for b in members]), 4, isz, osz)
+            start = 0
+            for b in members:
+                n = selected[b]["mask_logits"].shape[0]
+                rles[b] = strings[start:start + n]
+                start += n
+        records = []
+        for b, (x, r) in enumerate(zip(batched_inputs, selected)):
+            bx = r["pred_boxes"].cpu()
+            xywh = torch.stack([bx[:, 0], bx[:, 1], bx[:, 2] - bx[:, 0], bx[:, 3] - bx[:, 1]], 1).tolist()
+            for i, (score, label) in enumerate(zip(r["scores"].tolist(), r["pred_classes"].tolist())):
+                rec = {"image_id": x.get("image_id", b), "category_id": int(label), "bbox": xywh[i], "score": float(score)}
+                if rles[b] is not None:
+                    rec["segmentation"] = rles[b][i]
+                records.append(rec)
+        return records
 
     def _chunk_trunk(self, x, mask):
         """Padded frames -> (logits [F,Q,K], boxes [F,Q,4], query states, pre-sigmoid reference of the

@@ -310,6 +310,19 @@ def enable_device_matching(model, on: bool = True) -> None:
     model.device_matching = bool(on)
 
 
+def enable_device_selection(model, on: bool = True) -> None:
+    """Opt in to candidate selection on the device (`IDOL.device_selection`, vnext_amd/ops/det_select.py): the per-frame
+    score threshold and class-aware box NMS of video inference by one kernel for the whole chunk, instead of a host copy
+    of [F, Q, 6] floats and a NumPy loop per frame.  Only the picked indices cross to the host -- one copy, which is the
+    one synchronisation that stays (the counts size the mask head's rows).  The same picks as the host loop wherever no
+    comparison is decided by fp32 rounding of a sigmoid at the threshold; a shape the kernel refuses takes the host loop.
+    The COCO pre-training branch (`IDOL.coco_inference`) uses the op whenever its tensors are CUDA, without this switch.
+    Raises for a model without the switch."""
+    if not hasattr(model, "device_selection"):
+        raise ValueError("enable_device_selection: %s has no device_selection switch" % type(model).__name__)
+    model.device_selection = bool(on)
+
+
 def enable_fused_mask_loss(model, on: bool = True) -> None:
     """Opt in to the fused mask losses (`criterion.fused_mask_loss`, vnext_amd/ops/mask_loss.py): focal + dice of the
     matched instances' mask logits in one kernel pass each way, the ground truth read in place at image resolution --
