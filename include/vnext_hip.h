@@ -806,6 +806,64 @@ int vnx_det_select_out_words(int queries, int topk);
 int vnx_det_select(const void* logits, const void* boxes, int batch, int queries, int classes, float score_thr,
                    float iou_thr, int topk, void* out, int out_stride, void* hip_stream);
 
+/*
+ * SeqFormer's clip matching with the video's state in device memory (clip_link.hip): what `Videos` of
+ * models/clip_matching.py does per clip -- sIoU of the incoming clip's masks against the stored clips on the shared frames,
+ * the mean over the clips that hold a track, threshold 0.01, assignment, new tracks for the unmatched, the running sums of
+ * the result -- in three launches on the caller's stream, with no copy to the host.  ADDITIVE: five symbols, no existing
+ * signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * vnx_clip_link_config describes one video's state; the same values go to every call on that state.
+ *   ring: stored clips kept = frames of a clip at most (the model's CLIP_LENGTH), 1..VNX_CLIP_LINK_MAX_FRAMES
+ *   max_instances: instances of a clip at most, 1..VNX_CLIP_LINK_MAX_INSTANCES     pixels: H * W of a mask
+ *   video_length: frames of the video     classes: columns of cls_probs
+ *   capacity: tracks the state has room for.  An instance that finds none gets id -1 and raises the second counter.
+ * Beyond the two limits: VNX_ERR_UNSUPPORTED (vnx_clip_link_state_bytes / _workspace_bytes: 0) with vnx_last_error naming
+ * them, nothing launched.
+ * state: vnx_clip_link_state_bytes(cfg) bytes of device memory, 16-byte aligned, zeroed by vnx_clip_link_reset (a memset
+ * on the stream).  Its first three int32 are counters: tracks opened, instances that found no free track, clips taken.
+ *
+ * vnx_clip_link_update: one clip.  mask_logits fp32 [num_instances][plan->frames][pixels], cls_probs fp32
+ * [num_instances][classes], ids_out int64 [num_instances] (the track of every instance, in input order), all on the
+ * device and contiguous.  The frame lists stay with the host, which owns them; vnx_clip_link_plan is read on the host
+ * during the call and travels to the kernels by value:
+ *   frames, frame_index[]: the incoming clip's frames in the video (distinct, inside video_length)
+ *   write_slot: the ring slot that stores the incoming clip
+ *   slots, slot[], pairs[], stored_pos[][], incoming_pos[][]: the stored clips that share a frame with the incoming one,
+ *     OLDEST FIRST (the order their scores are added in), and for each the shared frames as (position in the stored clip,
+ *     position in the incoming clip).  A listed slot that holds an empty clip does not count, as in `Videos.get_siou`.
+ * num_instances == 0 is legal: the clip is stored empty.  num_instances above max_instances or frames above ring:
+ * VNX_ERR_UNSUPPORTED before any launch, the state untouched.  workspace: vnx_clip_link_workspace_bytes(cfg) bytes,
+ * 16-byte aligned, scratch of this call.  No atomics and every sum in a fixed order: bit-identical run to run.
+ *
+ * vnx_clip_link_result: cls_out fp32 [num_tracks][classes] = cls / in_clips and logits_out fp32
+ * [num_tracks][video_length][pixels] = total / seen of the first num_tracks tracks; 0 / 0 = NaN where no clip of a track
+ * covers a frame, as in the reference.
+ */
+#define VNX_CLIP_LINK_MAX_INSTANCES 16
+#define VNX_CLIP_LINK_MAX_FRAMES 8
+typedef struct vnx_clip_link_config {
+  int ring, max_instances, pixels, video_length, classes, capacity;
+} vnx_clip_link_config;
+typedef struct vnx_clip_link_plan {
+  int frames;
+  int frame_index[VNX_CLIP_LINK_MAX_FRAMES];
+  int write_slot;
+  int slots;
+  int slot[VNX_CLIP_LINK_MAX_FRAMES];
+  int pairs[VNX_CLIP_LINK_MAX_FRAMES];
+  unsigned char stored_pos[VNX_CLIP_LINK_MAX_FRAMES][VNX_CLIP_LINK_MAX_FRAMES];
+  unsigned char incoming_pos[VNX_CLIP_LINK_MAX_FRAMES][VNX_CLIP_LINK_MAX_FRAMES];
+} vnx_clip_link_plan;
+size_t vnx_clip_link_state_bytes(const vnx_clip_link_config* cfg);
+size_t vnx_clip_link_workspace_bytes(const vnx_clip_link_config* cfg);
+int vnx_clip_link_reset(const vnx_clip_link_config* cfg, void* state, void* hip_stream);
+int vnx_clip_link_update(const vnx_clip_link_config* cfg, void* state, const void* mask_logits, const void* cls_probs,
+                         const vnx_clip_link_plan* plan, int num_instances, void* ids_out, void* workspace,
+                         size_t workspace_bytes, void* hip_stream);
+int vnx_clip_link_result(const vnx_clip_link_config* cfg, const void* state, int num_tracks, void* cls_out,
+                         void* logits_out, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -47,6 +47,15 @@ int vnx_debug_gvdirect_units(const int64_t* host_shapes, int levels, int num_que
                              int* units_used, int* units_bound, int* level_units, int* level_rows_per_unit,
                              int* level_group_shift);
 
+/* What launch 2 of vnx_clip_link_update (clip_link.hip) matched on, left at the head of the call's workspace: byte offsets
+ * of the row count (int32), of each row's track (int32 [rows_max]) and of the scores before the threshold (fp32
+ * [rows_max][row_stride]; row r, column j = the mean sIoU of track r's stored clips against incoming instance j; only
+ * the first `row count` rows and num_instances columns are written).  The kernel writes them on EVERY call, not on
+ * request: the workspace head is scratch the call owns anyway, and at most 128 x 16 floats from one workgroup cost less
+ * than a second instantiation would.  Host only, no GPU needed; 0 on success. */
+int vnx_debug_clip_link_score_layout(size_t* rows_offset, size_t* tracks_offset, size_t* scores_offset, int* rows_max,
+                                     int* row_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,11 @@ SIGNATURES = {
     "vnx_swin_residual_norm_backward": (_i, [_i] * 3 + [_vp] * 11 + [_sz, _ll, _i, _ll, _vp]),
     "vnx_swin_merge_norm_forward": (_i, [_i] * 2 + [_vp] * 5 + [_i] * 4 + [ctypes.c_float, _vp]),
     "vnx_swin_merge_norm_backward": (_i, [_i] * 2 + [_vp] * 8 + [_sz] + [_i] * 4 + [_vp]),
+    "vnx_clip_link_state_bytes": (_sz, [_vp]),
+    "vnx_clip_link_workspace_bytes": (_sz, [_vp]),
+    "vnx_clip_link_reset": (_i, [_vp, _vp, _vp]),
+    "vnx_clip_link_update": (_i, [_vp] * 5 + [_i, _vp, _vp, _sz, _vp]),
+    "vnx_clip_link_result": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -92,6 +97,7 @@ DEBUG_SIGNATURES = {
     "vnx_debug_gvtiles_units": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i),
                                     ctypes.POINTER(_ll), ctypes.POINTER(_ll)]),
     "vnx_debug_gvdirect_units": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), _vp, _vp, _vp]),
+    "vnx_debug_clip_link_score_layout": (_i, [ctypes.POINTER(_sz)] * 3 + [ctypes.POINTER(_i)] * 2),
 }
 # include/vnext_hip_dev.h: exported by the development library only
 DEV_SIGNATURES = {
@@ -121,6 +127,23 @@ SET_LOSS_PIECE, SET_LOSS_MAX_ROWS = 4096, 1024       # VNX_SET_LOSS_PIECE, VNX_S
 
 
 REID_LOSS_MAX_ROWS = 1024                            # VNX_REID_LOSS_MAX_ROWS
+
+
+CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_INSTANCES, VNX_CLIP_LINK_MAX_FRAMES
+
+
+class ClipLinkConfig(ctypes.Structure):
+    """`vnx_clip_link_config` of include/vnext_hip.h, field by field."""
+    _fields_ = [(k, _i) for k in ("ring", "max_instances", "pixels", "video_length", "classes", "capacity")]
+
+
+class ClipLinkPlan(ctypes.Structure):
+    """`vnx_clip_link_plan` of include/vnext_hip.h, field by field: read on the host during the call, handed to the
+    kernels by value."""
+    _fields_ = [("frames", _i), ("frame_index", _i * CLIP_LINK_MAX_FRAMES), ("write_slot", _i), ("slots", _i),
+                ("slot", _i * CLIP_LINK_MAX_FRAMES), ("pairs", _i * CLIP_LINK_MAX_FRAMES),
+                ("stored_pos", (ctypes.c_ubyte * CLIP_LINK_MAX_FRAMES) * CLIP_LINK_MAX_FRAMES),
+                ("incoming_pos", (ctypes.c_ubyte * CLIP_LINK_MAX_FRAMES) * CLIP_LINK_MAX_FRAMES)]
 
 
 class MaskLossClips(ctypes.Structure):

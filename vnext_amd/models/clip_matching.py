@@ -21,6 +21,7 @@ import torch
 from scipy.optimize import linear_sum_assignment
 
 from . import tracker as _trk      # shares the similarity entry point (tests swap it for torch.mm on CPU)
+from ..ops import clip_link
 
 
 class Clips:
@@ -107,3 +108,82 @@ class Videos:
             cls[ids] += cls_probs
             in_clips[ids] += 1
         return cls / in_clips[:, None], total / seen[..., None, None]
+
+
+class DeviceVideos:
+    """`Videos` with the video's state in device memory (vnext_amd/csrc/clip_link.hip, vnext_amd/ops/clip_link.py): the
+    last `num_frames` clips' mask probabilities, every track's running sums and the track counter live there, a clip
+    costs one call of three launches and nothing is copied to the host before `get_result`.  Same constructor as
+    `Videos` plus `capacity` (tracks the state has room for; the reference's num_max_inst), `max_instances`
+    (instances of a clip at most) and `num_clips` (when the caller knows it: with max_instances it bounds the tracks).
+
+    update_logits(frame_idx, cls_probs, mask_logits[, ids_out]) -> ids [n] int64 ON THE DEVICE, no synchronisation.
+    update(clip)      the same for a `Clips` object (its sigmoid copy is not used).
+    get_result()      -> (cls [N, K], logits [N, L, h, w]); one host copy, of the three counters.
+    Raises ClipLinkUnsupported -- link the video with `Videos` -- for a clip of more instances or frames than the kernels
+    take, and from get_result when an instance found no free track.  The same ids as `Videos` wherever no assignment and
+    no comparison with the threshold is decided by fp32 rounding of a score.
+    """
+    MAX_INSTANCES = clip_link.MAX_INSTANCES      # what the kernels take: a state is never built for more
+
+    def __init__(self, num_frames, video_length, num_classes, image_size, device, capacity=120, max_instances=16,
+                 num_clips=None):
+        self.num_frames, self.video_length, self.num_classes = int(num_frames), int(video_length), int(num_classes)
+        self.image_size, self.device = tuple(int(v) for v in image_size), device
+        self.max_instances = max(1, min(int(max_instances), self.MAX_INSTANCES))
+        # a clip opens at most max_instances tracks, and clips that start on distinct frames are at most video_length
+        clips = self.video_length if num_clips is None else max(1, int(num_clips))
+        self.capacity = max(1, min(int(capacity), self.max_instances * clips))
+        self.num_clip = 0
+        self.recent = []        # the ring as the host sees it: (slot, frame list) of the last num_frames clips, oldest first
+        self.cfg = self.state = self.workspace = None
+
+    def _start(self):
+        self.cfg = clip_link.config(self.num_frames, self.max_instances, self.image_size[0] * self.image_size[1],
+                                    self.video_length, self.num_classes, self.capacity)
+        self.state, self.workspace = clip_link.new_state(self.cfg, self.device)
+
+    def counters(self):
+        """(tracks opened, instances that found no free track, clips taken) -- one host copy."""
+        if self.state is None:
+            return 0, 0, 0
+        return tuple(self.state[:12].view(torch.int32).tolist())
+
+    @property
+    def num_inst(self):
+        return self.counters()[0]
+
+    def update_logits(self, frame_idx, cls_probs, mask_logits, ids_out=None):
+        if not mask_logits.is_cuda or not cls_probs.is_cuda:
+            raise RuntimeError("DeviceVideos: Not implemented on the CPU (Videos is the host form)")
+        if self.state is None:
+            self._start()
+        frame_idx = [int(f) for f in frame_idx]
+        n = mask_logits.shape[0]
+        logits = mask_logits.reshape(n, len(frame_idx), self.cfg.pixels).to(torch.float32).contiguous()
+        probs = cls_probs.reshape(n, self.num_classes).to(torch.float32).contiguous()
+        slot = self.num_clip % self.num_frames
+        # Videos.get_siou looks at the last len(frame_idx) clips
+        window = self.recent[max(len(self.recent) - len(frame_idx), 0):]
+        ids = clip_link.update(self.cfg, self.state, self.workspace, logits, probs,
+                               clip_link.plan(frame_idx, slot, window), ids_out)
+        self.recent = (self.recent + [(slot, frame_idx)])[-self.num_frames:]
+        self.num_clip += 1
+        return ids
+
+    def update(self, input_clip):
+        return self.update_logits(input_clip.frame_idx, input_clip.cls_probs, input_clip.mask_logits)
+
+    def get_result(self, cls_out=None, logits_out=None):
+        """-> (class probabilities [N, K], mask logits [N, video_length, h, w]), as `Videos.get_result`; written into
+        `cls_out` [N, K] / `logits_out` [N, video_length, h * w] when the caller brings them."""
+        h, w = self.image_size
+        if self.state is None:
+            return (torch.zeros(0, self.num_classes, device=self.device),
+                    torch.zeros(0, self.video_length, h, w, device=self.device))
+        opened, lost, _ = self.counters()
+        if lost:
+            raise clip_link.ClipLinkUnsupported(
+                f"DeviceVideos: {lost} instances found no free track (capacity {self.capacity})")
+        cls, logits = clip_link.result(self.cfg, self.state, opened, cls_out, logits_out)
+        return cls, logits.view(opened, self.video_length, h, w)

@@ -413,6 +413,7 @@ class SeqFormer(nn.Module):
         self.graph_inference = True     # replay the inference trunk from a hipGraph (per clip shape)
         self.graph_training = False     # capture the training trunk's forward and backward (opt-in)
         self.device_matching = False    # match queries to targets on the device: no host round trip in `losses` (opt-in)
+        self.device_clip_matching = False     # CLIP_MATCHING inference: link the clips on the device, no host copy per clip (opt-in)
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -698,6 +699,35 @@ class SeqFormer(nn.Module):
         the device (`_report(rle=True)`) instead of copied to the host as bool masks."""
         return ytvis_records(batched_inputs, self.inference(batched_inputs, rle=True))
 
+    def _linked_clips(self, frames, on_device):
+        """CLIP_MATCHING: the video's overlapping clips, linked into tracks -> (class probabilities [N, K], mask logits
+        [N, L, H/4, W/4]).  `on_device`: through `DeviceVideos`, whose per-clip call copies nothing to the host (and
+        needs neither `prob.max(-1)` nor the sigmoid copy a `Clips` object makes)."""
+        from types import SimpleNamespace
+        from .clip_matching import Clips, DeviceVideos, Videos
+        n_frames, merged, clips = len(frames), None, []
+        for start in range(0, n_frames, self.clip_stride):
+            end, last = start + self.clip_length, False
+            if end >= n_frames:
+                start, end, last = max(0, n_frames - self.clip_length), n_frames, True
+            clips.append(list(range(start, end)))
+            if last:
+                break
+        for idx in clips:
+            prob, mask_logits = self._top_instances([frames[i] for i in idx])
+            if merged is None and on_device:      # the clip count bounds the tracks the state needs room for
+                merged = DeviceVideos(self.clip_length, n_frames, self.num_classes, mask_logits.shape[-2:], self.device,
+                                      max_instances=prob.shape[0], num_clips=len(clips))
+            elif merged is None:
+                merged = Videos(self.clip_length, n_frames, self.num_classes, mask_logits.shape[-2:], self.device)
+            if on_device:
+                merged.update_logits(idx, prob, mask_logits)
+            else:
+                score, label = prob.max(-1)
+                merged.update(Clips(idx, SimpleNamespace(pred_classes=label, scores=score, cls_probs=prob,
+                                                         pred_masks=mask_logits)))
+        return merged.get_result()
+
     @torch.no_grad()
     def inference(self, batched_inputs, rle=False):
         """One video (seqformer.py:227-264).  Default: the whole video as one clip -- the 10 queries
@@ -713,21 +743,12 @@ class SeqFormer(nn.Module):
         if not self.clip_matching:
             prob, mask_logits = self._top_instances(frames)
             return self._report(prob, mask_logits, (ih, iw), out_size, rle)
-        from types import SimpleNamespace
-        from .clip_matching import Clips, Videos
-        n_frames, merged = len(frames), None
-        for start in range(0, n_frames, self.clip_stride):
-            end, last = start + self.clip_length, False
-            if end >= n_frames:
-                start, end, last = max(0, n_frames - self.clip_length), n_frames, True
-            idx = list(range(start, end))
-            prob, mask_logits = self._top_instances([frames[i] for i in idx])
-            if merged is None:
-                merged = Videos(self.clip_length, n_frames, self.num_classes, mask_logits.shape[-2:], self.device)
-            score, label = prob.max(-1)
-            merged.update(Clips(idx, SimpleNamespace(pred_classes=label, scores=score, cls_probs=prob,
-                                                     pred_masks=mask_logits)))
-            if last:
-                break
-        cls, mask_logits = merged.get_result()
+        if self.device_clip_matching and frames[0].is_cuda:
+            from ..ops.clip_link import ClipLinkUnsupported
+            try:
+                cls, mask_logits = self._linked_clips(frames, on_device=True)
+            except ClipLinkUnsupported:      # a clip beyond the kernels' limits, or more tracks than the state holds
+                cls, mask_logits = self._linked_clips(frames, on_device=False)
+        else:
+            cls, mask_logits = self._linked_clips(frames, on_device=False)
         return self._report(cls, mask_logits, (ih, iw), out_size, rle)

@@ -323,6 +323,19 @@ def enable_device_selection(model, on: bool = True) -> None:
     model.device_selection = bool(on)
 
 
+def enable_device_clip_matching(model, on: bool = True) -> None:
+    """Opt in to clip matching on the device (`SeqFormer.device_clip_matching`, vnext_amd/ops/clip_link.py): with
+    `MODEL.SEQFORMER.CLIP_MATCHING` the clips of a long video are linked into tracks by three launches per clip on a state
+    that stays in device memory -- mask sIoU against the stored clips, the assignment, new tracks, the running sums -- instead
+    of a loop of small launches, two copies to the host and a scipy call per clip; the host no longer waits for the device
+    between clips.  The same tracks as the host path wherever no assignment is decided by fp32 rounding of a score; a
+    video beyond the kernels' limits (instances or frames of a clip, tracks of a video) is redone on the host path.
+    Raises for a model without the switch (IDOL tracks frame by frame: `DeviceTracker`)."""
+    if not hasattr(model, "device_clip_matching"):
+        raise ValueError("enable_device_clip_matching: %s has no device_clip_matching switch" % type(model).__name__)
+    model.device_clip_matching = bool(on)
+
+
 def enable_fused_mask_loss(model, on: bool = True) -> None:
     """Opt in to the fused mask losses (`criterion.fused_mask_loss`, vnext_amd/ops/mask_loss.py): focal + dice of the
     matched instances' mask logits in one kernel pass each way, the ground truth read in place at image resolution --
