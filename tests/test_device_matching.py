@@ -16,7 +16,7 @@ import torch
 from scipy.optimize import linear_sum_assignment
 
 from conftest import GOLDEN_DIR, ROOT
-from vnext_amd.models.criterion import DeviceMatch, HungarianMatcher, SetCriterion
+from vnext_amd.models.criterion import DeviceMatch, HungarianMatcher, SetCriterion, flat_pairs
 
 NAMES = ("vnx_seqformer_match", "vnx_lsap_solve")
 WEIGHTS = dict(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0)      # the fixture's (and the model's) matcher weights
@@ -38,15 +38,57 @@ def _fixture(device="cpu"):
     return g, targets, logits, boxes, masks, (bs, nf, Q, K, layers)
 
 
-def _hand_built_match(g, bs, layers, sizes, device):
-    """the DeviceMatch of the fixture's own indices"""
+def _hand_built_match(g, bs, layers, sizes, device, keys=("src", "tgt")):
+    """the DeviceMatch of the fixture's own indices; `keys`: the fixture's names of a pair's two halves (the first half of
+    criterion_idol.npz, `sel`, is a bool selection over the queries: its set positions are the queries)"""
     start = np.concatenate([[0], np.cumsum(sizes)])
     lay, clip, qry, tgt = [], [], [], []
     for l in range(layers):
         for i in range(bs):
-            q, t = g[f"l{l}.src{i}"], g[f"l{l}.tgt{i}"]
+            q, t = g[f"l{l}.{keys[0]}{i}"], g[f"l{l}.{keys[1]}{i}"]
+            if q.dtype == np.bool_:
+                q = np.nonzero(q)[0]
             lay.append(np.full_like(q, l)); clip.append(np.full_like(q, i)); qry.append(q); tgt.append(t + start[i])
     return DeviceMatch(*(torch.from_numpy(np.concatenate(a).astype(np.int64)).to(device) for a in (lay, clip, qry, tgt)))
+
+
+@pytest.mark.parametrize("fixture, keys, labels, layers_at", [("criterion_seqformer", ("src", "tgt"), "t{}.labels", 6),
+                                                             ("criterion_idol", ("sel", "gt"), "det{}.labels", 5)])
+def test_flat_pairs_equals_the_hand_built_vectors(fixture, keys, labels, layers_at):
+    """The one constructor of the pair list against the vectors built by hand here, for both forms the matchers return
+    ((query idx, target idx) and (selected [Q] bool, target idx)): the fixture as it is, then with an image without
+    targets put between its images and, for the bool form, with a layer in which nothing is selected."""
+    g = dict(np.load(os.path.join(GOLDEN_DIR, fixture + ".npz")))
+    bs, layers = int(g["cfg"][0]), int(g["cfg"][layers_at])
+    assert bs >= 2 and layers >= 2
+    sizes = [len(g[labels.format(i)]) for i in range(bs)]
+
+    def both(g, bs, sizes):
+        ind = [[tuple(torch.from_numpy(g[f"l{l}.{k}{i}"]) for k in keys) for i in range(bs)] for l in range(layers)]
+        got, want = flat_pairs(ind, sizes, "cpu"), _hand_built_match(g, bs, layers, sizes, "cpu", keys)
+        assert isinstance(got, DeviceMatch)
+        for name, a, b in zip(DeviceMatch._fields, got, want):
+            assert a.dtype == torch.int64 and torch.equal(a, b), name
+        return got
+    whole = both(g, bs, sizes)
+    assert len(whole.qry) >= layers * sum(sizes) > 0      # every target in every layer, at least once
+    # an image without targets in second place: the images after it move up one, the targets' offsets stay
+    first = g[f"l0.{keys[0]}0"]
+    wider = {}
+    for l in range(layers):
+        for i in range(bs):
+            for k in keys:
+                wider[f"l{l}.{k}{i + (i > 0)}"] = g[f"l{l}.{k}{i}"]
+        wider[f"l{l}.{keys[0]}1"] = np.zeros_like(first) if first.dtype == np.bool_ else np.zeros(0, dtype=first.dtype)
+        wider[f"l{l}.{keys[1]}1"] = np.zeros(0, dtype=np.int64)
+    if first.dtype == np.bool_:                  # ... and nothing selected in layer 0
+        for i in range(bs + 1):
+            wider[f"l0.{keys[0]}{i}"], wider[f"l0.{keys[1]}{i}"] = np.zeros_like(first), np.zeros(0, dtype=np.int64)
+    got = both(wider, bs + 1, sizes[:1] + [0] + sizes[1:])
+    assert not bool((got.clip == 1).any()) and int(got.clip.max()) == bs
+    assert torch.equal(got.tgt[got.lay == layers - 1], whole.tgt[whole.lay == layers - 1])
+    if first.dtype == np.bool_:
+        assert not bool((got.lay == 0).any()) and bool((got.lay == 1).any())
 
 
 def _gap(cost64, maximize=False):
@@ -468,8 +510,7 @@ def test_model_step_is_the_same_with_device_matching(seqformer):
         for x, y in zip(a, b):
             assert torch.equal(x, y)                      # two device-path runs: bit-identical indices
         assert int(a.qry.min()) >= 0
-        host = HungarianMatcher._upload(m.match_all_layers(logits, boxes, targets), [len(t["labels"]) for t in targets],
-                                        logits.device)
+        host = flat_pairs(m.match_all_layers(logits, boxes, targets), [len(t["labels"]) for t in targets], logits.device)
         for x, y in zip(a, host):
             assert torch.equal(x, y)                      # ... and the host matcher's
     model.device_matching = False
@@ -492,3 +533,67 @@ def test_model_step_is_the_same_with_device_matching(seqformer):
         check("loss", k, loss_d[k], loss_h1[k], loss_h2[k])
     for k in grad_h1:
         check("grad", k, grad_d[k], grad_h1[k], grad_h2[k])
+
+
+# ---- 7. one pair list per training step ----------------------------------------------------------------------------
+def count_flat_pairs(monkeypatch):
+    """Put a counting wrapper in place of `flat_pairs` under every name the models package holds it by.
+    -> the list of what the calls returned."""
+    import vnext_amd.models.criterion as criterion
+    import vnext_amd.models.idol as idol
+    import vnext_amd.models.idol_criterion as idol_criterion
+    import vnext_amd.models.seqformer as seqformer
+    made = []
+
+    def counting(*args, **kw):
+        made.append(flat_pairs(*args, **kw))
+        return made[-1]
+    held = [mod for mod in (criterion, idol_criterion, seqformer, idol) if hasattr(mod, "flat_pairs")]
+    assert criterion in held
+    for mod in held:
+        monkeypatch.setattr(mod, "flat_pairs", counting)
+    return made
+
+
+def record_calls(monkeypatch, owner, name):
+    """-> the list of (args, kwargs) `owner.name` is called with from now on; the calls go through"""
+    real, calls = getattr(owner, name), []
+
+    def recording(*args, **kw):
+        calls.append((args, kw))
+        return real(*args, **kw)
+    monkeypatch.setattr(owner, name, recording)
+    return calls
+
+
+@pytest.mark.gpu
+def test_the_pair_list_is_built_once_per_step_on_the_host_matching_path(monkeypatch):
+    """Host matching, deep supervision: one `flat_pairs` call per `model(clips)`, and the `DeviceMatch` it returned is
+    both what orders the mask head's rows and, the same object, what the criterion is given.  Two decoder layers and two
+    clips of 1 and 3 instances: the smallest batch in which a second, differently ordered list would show."""
+    import vnext_amd.models  # noqa: F401
+    import vnext_amd.models.seqformer as seqformer
+    from vnext_amd import train
+    from vnext_amd.registry import build_model, get_seqformer_cfg
+    dev = "cuda:0"
+    tiny = {"MODEL.SeqFormer.ENC_LAYERS": 1, "MODEL.SeqFormer.DEC_LAYERS": 2, "MODEL.SeqFormer.NUM_OBJECT_QUERIES": 12,
+            "MODEL.SeqFormer.DIM_FEEDFORWARD": 64, "MODEL.SeqFormer.DROPOUT": 0.0, "INPUT.SAMPLING_FRAME_NUM": 2}
+    torch.manual_seed(0)
+    model = build_model(get_seqformer_cfg(**{"MODEL.DEVICE": dev, **tiny})).train()
+    assert model.device_matching is False and model.deep_supervision
+    T = 2
+    clips = (train.synthetic_clips(1, T, 128, 192, dev, seed=3, num_instances=1) +
+             train.synthetic_clips(1, T, 128, 192, dev, seed=4, num_instances=3))
+    made = count_flat_pairs(monkeypatch)
+    head = record_calls(monkeypatch, seqformer, "dynamic_mask_head")
+    given = record_calls(monkeypatch, model.criterion, "forward_all_layers")
+    losses = model(clips)
+    assert len(made) == 1
+    match = made[0]
+    assert len(given) == 1 and given[0][0][4] is match                       # the criterion's `indices_list` argument
+    assert len(match.qry) == 2 * (1 + 3) and all(x.is_cuda for x in match)
+    assert match.clip.tolist() == [0, 1, 1, 1] * 2 and match.lay.tolist() == [0] * 4 + [1] * 4
+    assert len(head) == 1
+    image = head[0][0][3]                                                    # the frame each mask-head row reads
+    assert torch.equal(image, ((match.clip * T)[:, None] + torch.arange(T, device=dev)[None, :]).flatten().to(torch.int32))
+    assert all(bool(torch.isfinite(v)) for v in losses.values())

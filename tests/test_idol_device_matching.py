@@ -788,3 +788,36 @@ def test_model_step_is_the_same_with_device_matching():
             if not dev_diff <= allowed:
                 failures.append((kind, k, dev_diff, allowed))
     assert not failures, failures
+
+
+@pytest.mark.gpu
+def test_the_pair_list_is_built_once_per_step(monkeypatch):
+    """test_device_matching.py's test of the same name, for IDOL (whose two matching paths both return host structures):
+    one `flat_pairs` call per `model(pairs)`; the `DeviceMatch` it returned orders the mask head's rows and is, the same
+    object, what the criterion is given, with the per-layer counts as host integers beside it."""
+    import vnext_amd.models  # noqa: F401
+    import vnext_amd.models.idol as idol
+    from test_device_matching import count_flat_pairs, record_calls
+    from vnext_amd import train
+    from vnext_amd.registry import build_model, get_idol_cfg
+    tiny = {"MODEL.IDOL.ENC_LAYERS": 1, "MODEL.IDOL.DEC_LAYERS": 2, "MODEL.IDOL.NUM_OBJECT_QUERIES": 110,
+            "MODEL.IDOL.DIM_FEEDFORWARD": 64, "MODEL.IDOL.DROPOUT": 0.0}
+    torch.manual_seed(11)
+    model = build_model(get_idol_cfg(**{"MODEL.DEVICE": DEV, **tiny})).train()
+    assert model.device_matching is False and model.deep_supervision
+    pairs = (train.synthetic_clips(1, 2, 128, 192, DEV, seed=3, num_instances=1) +
+             train.synthetic_clips(1, 2, 128, 192, DEV, seed=4, num_instances=3))
+    made = count_flat_pairs(monkeypatch)
+    head = record_calls(monkeypatch, idol, "dynamic_mask_head")
+    given = record_calls(monkeypatch, model.criterion, "forward_all_layers")
+    losses = model(pairs)
+    assert len(made) == 1
+    match = made[0]
+    assert len(given) == 1 and given[0][0][4] is match                       # the criterion's `indices_list` argument
+    counts = given[0][1]["counts"]
+    assert all(type(c) is int for c in counts) and len(counts) == 2 and sum(counts) == len(match.qry)
+    assert counts == [int((match.lay == l).sum()) for l in range(2)] and min(counts) >= 1 + 3
+    assert all(x.is_cuda for x in match) and set(match.clip.tolist()) == {0, 1}
+    assert len(head) == 1
+    assert torch.equal(head[0][0][3], match.clip.to(torch.int32))            # the key frame each mask-head row reads
+    assert all(bool(torch.isfinite(v)) for v in losses.values())

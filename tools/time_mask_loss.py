@@ -25,7 +25,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
 
 SHAPES = [  # (R, F, h, w, clips, stride): Ld = 6 layers x 4 instances of one 360p clip; 6 x 20 instances over two 720p clips
     (24, 5, 90, 160, 1, 4),
@@ -53,20 +52,13 @@ def make_case(R, frames, h, w, clips, stride, dev, layers=6, seed=0):
 
 
 def aten_rows(logits, gts, row_gt, stride, alpha=0.25, gamma=2.0):
-    """the criteria's expression, from t["masks"] to the per-row focal mean and dice"""
+    """the criteria's expression (their own term functions), from t["masks"] to the per-row focal mean and dice"""
+    from vnext_amd.models.criterion import dice_term, focal_term, gt_canvas
     h, w = logits.shape[-2:]
-    gt = []
-    for m in gts:
-        m = m[..., stride // 2::stride, stride // 2::stride]
-        gt.append(F.pad(m.to(logits.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
-    gt = torch.cat(gt)[row_gt].flatten(1)
+    gt = gt_canvas(gts, stride, h, w, logits.dtype)[row_gt].flatten(1)
     src = logits.flatten(1)
     pm = src.sigmoid()
-    ce = F.binary_cross_entropy_with_logits(src, gt, reduction="none")
-    pt = pm * gt + (1 - pm) * (1 - gt)
-    fm = (alpha * gt + (1 - alpha) * (1 - gt)) * ce * (1 - pt) ** gamma
-    dice = 1 - (2 * (pm * gt).sum(1) + 1) / (pm.sum(1) + gt.sum(1) + 1)
-    return fm.mean(1), dice
+    return focal_term(src, gt, alpha, gamma, p=pm).mean(1), dice_term(pm, gt)
 
 
 def fused_rows(logits, gts, row_gt, stride):

@@ -28,7 +28,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
 
 SHAPES = [  # (name, Ld, N, T, Q, K, targets per clip, IDOL-shaped): the bench's two legs, then ten clips
     ("seqformer", 6, 2, 5, 300, 40, (2, 2), False),
@@ -61,27 +60,20 @@ def make_case(Ld, N, T, Q, K, sizes, idol, dev, seed=0):
 
 
 def aten_sums(logits, boxes, lay, clip, qry, tgt, labels, tgt_boxes, idol, alpha=0.25):
-    """the criteria's expression, from the logits to the per-layer sums [Ld, 4]"""
-    from vnext_amd.models.criterion import box_cxcywh_to_xyxy, giou_loss
+    """the criteria's expression (their own term functions), from the logits to the per-layer sums [Ld, 4]"""
+    from vnext_amd.models.criterion import box_terms, focal_term
     Ld, T = logits.shape[0], boxes.shape[2]
     onehot = torch.zeros_like(logits)
     onehot[lay, clip, qry, labels[tgt]] = torch.ones((), dtype=logits.dtype, device=logits.device)
-    p = logits.sigmoid()
-    ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
-    p_t = p * onehot + (1 - p) * (1 - onehot)
-    focal = (alpha * onehot + (1 - alpha) * (1 - onehot)) * (ce * (1 - p_t) ** 2.0)
-    loss_ce = focal.mean(2).sum((1, 2)) * logits.shape[2]
-    pred = boxes.transpose(2, 3)[lay, clip, qry]
-    want = tgt_boxes[tgt]
+    loss_ce = focal_term(logits, onehot, alpha).mean(2).sum((1, 2)) * logits.shape[2]
+    l1, g = box_terms(boxes.transpose(2, 3)[lay, clip, qry], tgt_boxes[tgt])          # [R], [R, T]
     with torch.no_grad():
         hit = (logits[lay, clip, qry].argmax(-1) == labels[tgt]).float()
-    g = giou_loss(box_cxcywh_to_xyxy(pred.flatten(0, 1)), box_cxcywh_to_xyxy(want.flatten(0, 1)))
     if idol:
         seg = lambda v: torch.zeros(Ld, dtype=v.dtype, device=v.device).index_add_(0, lay, v)      # noqa: E731
-        return torch.stack([loss_ce, seg((pred - want).abs().flatten(1).sum(1)), seg(g), seg(hit)], 1)
+        return torch.stack([loss_ce, seg(l1), seg(g.flatten()), seg(hit)], 1)
     n = len(lay) // Ld
-    return torch.stack([loss_ce, (pred - want).abs().flatten(1).sum(1).view(Ld, n).sum(1), g.view(Ld, n * T).sum(1),
-                        hit.view(Ld, n).sum(1)], 1)
+    return torch.stack([loss_ce, l1.view(Ld, n).sum(1), g.view(Ld, n * T).sum(1), hit.view(Ld, n).sum(1)], 1)
 
 
 def fused_sums(logits, boxes, lay, clip, qry, tgt, labels, tgt_boxes, idol):

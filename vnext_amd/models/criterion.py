@@ -18,10 +18,20 @@ mask head runs for), not a kernel.  Differences in *how*, not in *what*:
     the ground truth read in place -- no sliced / padded / gathered float copy, nothing [R, M]-sized kept for the backward.
   * opt-in (`fused_set_loss`): the class focal loss, the boxes' L1 and GIoU losses and `class_error` of every decoder layer
     from one op (vnext_amd/csrc/set_loss.hip): no one-hot target, no gathers, two launches forward and one backward.
+Shared with IDOL's criterion (idol_criterion.py, whose `IDOLCriterion` derives from `SetCriterion`), and written once:
+  * the flat pair list `DeviceMatch(lay, clip, qry, tgt)` every all-layers expression and fused op consumes.  On the
+    device-matching path the matcher returns it; everywhere else `flat_pairs` makes it from the host `indices_list` of
+    either matcher.  The models call it once per step and pass the object on, so the rows of the mask head and the rows
+    of the losses cannot fall out of step; `layer_counts` gives the host integers that go with it.
+  * the loss terms before their reductions: `focal_term`, `dice_term`, `gt_canvas` (the ground truth as the mask logits
+    see it), `box_terms`, `layer_suffixes`.  The reductions stay with each criterion: SeqFormer sums `view(Ld, n)`,
+    IDOL segment-sums over unequal layer counts.  tools/time_set_loss.py and tools/time_mask_loss.py time these same
+    functions as the ATen baseline of the fused ops.
 """
 from __future__ import annotations
 
 from collections import namedtuple
+from itertools import accumulate
 
 import torch
 import torch.nn as nn
@@ -65,29 +75,93 @@ def giou_loss(a, b, eps=1e-7):
     return 1 - (inter / (union + eps) - (hull - union) / (hull + eps))
 
 
-def sigmoid_focal_loss(logits, targets, num_boxes, alpha=0.25, gamma=2.0):
-    """segmentation_condInst.py:698-723: mean over the last axis, summed, / num_boxes"""
-    p = logits.sigmoid()
+def focal_term(logits, targets, alpha=0.25, gamma=2.0, p=None):
+    """element-wise sigmoid focal term of logits against a 0/1 target (segmentation_condInst.py:698-720), before any
+    reduction.  `p`: logits.sigmoid() where the caller holds it already (the mask branch shares it with `dice_term`)."""
+    if p is None:
+        p = logits.sigmoid()
     ce = F.binary_cross_entropy_with_logits(logits, targets, reduction="none")
     p_t = p * targets + (1 - p) * (1 - targets)
     loss = ce * (1 - p_t) ** gamma
     if alpha >= 0:
         loss = (alpha * targets + (1 - alpha) * (1 - targets)) * loss
-    return loss.mean(1).sum() / num_boxes
+    return loss
+
+
+def sigmoid_focal_loss(logits, targets, num_boxes, alpha=0.25, gamma=2.0):
+    """segmentation_condInst.py:698-723: mean over the last axis, summed, / num_boxes"""
+    return focal_term(logits, targets, alpha, gamma).mean(1).sum() / num_boxes
+
+
+def dice_term(p, targets):
+    """per-row dice term of probabilities p [R, M] (the mask logits' sigmoid) against targets [R, M] -> [R]"""
+    num = 2 * (p * targets).sum(1)
+    den = p.sum(-1) + targets.sum(-1)
+    return 1 - (num + 1) / (den + 1)
 
 
 def dice_loss(logits, targets, num_boxes):
     """segmentation_condInst.py:680-695"""
-    p = logits.sigmoid().flatten(1)
-    num = 2 * (p * targets).sum(1)
-    den = p.sum(-1) + targets.sum(-1)
-    return (1 - (num + 1) / (den + 1)).sum() / num_boxes
+    return dice_term(logits.sigmoid().flatten(1), targets).sum() / num_boxes
+
+
+def gt_canvas(masks, stride, h, w, dtype):
+    """Ground-truth masks as the mask logits see them (deformable_detr.py:353-362): per entry of `masks` ([..., H_i, W_i],
+    one per clip or image) sampled at the centre of each stride-`stride` cell, cast, zero-padded to the /32-padded canvas
+    (h, w), then concatenated along the first axis."""
+    out = []
+    for m in masks:
+        m = m[..., stride // 2::stride, stride // 2::stride]
+        assert m.shape[-2] <= h and m.shape[-1] <= w
+        out.append(F.pad(m.to(dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
+    return torch.cat(out)
+
+
+def box_terms(pred, want):
+    """gathered pairs pred / want [R, ..., 4] (cxcywh) -> (L1 per pair [R], 1 - GIoU per box [R, ...])"""
+    return (pred - want).abs().flatten(1).sum(1), giou_loss(box_cxcywh_to_xyxy(pred), box_cxcywh_to_xyxy(want))
+
+
+def layer_suffixes(layers):
+    """loss-name suffixes of deep supervision: `_0 ... _{Ld-2}` for the auxiliary layers, none for the last"""
+    return [f"_{l}" for l in range(layers - 1)] + [""]
 
 
 # What `HungarianMatcher.match_all_layers_device` returns and `SetCriterion.forward_all_layers` accepts in place of the host
 # `indices_list`: int64 device tensors [Ld * n] each (n = all targets of the batch), layer-major, clips in order, a clip's
 # pairs by ascending query.  lay / clip / qry index logits [Ld, N, Q, K]; tgt indexes the batch's concatenated targets.
 DeviceMatch = namedtuple("DeviceMatch", ["lay", "clip", "qry", "tgt"])
+
+
+def _target_offsets(sizes):
+    """[0, n_0, n_0 + n_1, ...]: where each clip's targets begin among the batch's targets laid back to back"""
+    return list(accumulate(sizes, initial=0))
+
+
+def flat_pairs(indices_list, sizes, device=None, non_blocking=False):
+    """host indices_list[layer][clip] -> DeviceMatch: THE place that lays the pairs out (everything that gathers by them
+    -- controller, mask head rows, every loss -- takes its order from one call of this).  A clip's entry is either
+    (query idx, target idx) (`HungarianMatcher`) or (selected [Q] bool, target idx of each selected query, ascending)
+    (`OTAMatcher`); `sizes` are the clips' target counts.  One `cat` per field on the host, one transfer per field
+    (`device` None: the vectors stay where the indices are)."""
+    start = _target_offsets(sizes)
+    lay, clip, qry, tgt = [], [], [], []
+    for l, ind in enumerate(indices_list):
+        for i, (q, j) in enumerate(ind):
+            if q.dtype == torch.bool:
+                q = torch.nonzero(q).flatten()
+            lay.append(torch.full_like(q, l))
+            clip.append(torch.full_like(q, i))
+            qry.append(q)
+            tgt.append(j.long() + start[i])                 # into the concatenated targets
+    if not qry:                                             # no layer or no clip at all
+        lay = clip = qry = tgt = [torch.zeros(0, dtype=torch.int64)]
+    return DeviceMatch(*(torch.cat(v).to(device, non_blocking=non_blocking) for v in (lay, clip, qry, tgt)))
+
+
+def layer_counts(indices_list):
+    """pairs per layer of a host indices_list (either form), as host integers"""
+    return [sum(len(j) for _, j in ind) for ind in indices_list]
 
 _MATCH_CONSTANTS = {}
 
@@ -102,9 +176,7 @@ def _match_constants(sizes, layers, device):
     if c is None:
         if len(_MATCH_CONSTANTS) > 256:
             _MATCH_CONSTANTS.clear()
-        start = [0]
-        for n in sizes:
-            start.append(start[-1] + n)
+        start = _target_offsets(sizes)
         offsets = torch.cat([torch.full((1,), v, dtype=torch.int32, device=device) for v in start])
         clip = torch.cat([torch.full((n,), i, dtype=torch.int64, device=device) for i, n in enumerate(sizes)])
         first = torch.cat([torch.full((n,), start[i], dtype=torch.int64, device=device) for i, n in enumerate(sizes)])
@@ -193,20 +265,8 @@ class HungarianMatcher(nn.Module):
             qry, tgt = seqformer_match(logits, boxes, labels, tgt_boxes, offsets,
                                        (self.cost_class, self.cost_bbox, self.cost_giou), max_targets=max(sizes))
         except LsapUnsupported:
-            return self._upload(self.match_all_layers(logits, boxes, targets), sizes, dev)
+            return flat_pairs(self.match_all_layers(logits, boxes, targets), sizes, dev)
         return DeviceMatch(lay, clip, qry.flatten(), (tgt + first).flatten())
-
-    @staticmethod
-    def _upload(indices_list, sizes, device):
-        """host indices_list -> DeviceMatch (the stacked index tensors, one transfer each)"""
-        start = [0]
-        for n in sizes:
-            start.append(start[-1] + n)
-        lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind])
-        clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)])
-        qry = torch.cat([q for ind in indices_list for q, _ in ind])
-        tgt = torch.cat([j + start[i] for ind in indices_list for i, (_, j) in enumerate(ind)])   # into the concatenated targets
-        return DeviceMatch(lay.to(device), clip.to(device), qry.to(device), tgt.to(device))
 
 
 class SetCriterion(nn.Module):
@@ -270,15 +330,8 @@ class SetCriterion(nn.Module):
         s = self.mask_out_stride
         if self.fused_mask_loss:
             return self._loss_masks_fused(src, targets, indices, num_boxes)
-        picked = []
-        for t, (_, j) in zip(targets, indices):
-            m = t["masks"][j.to(t["masks"].device)]                           # [n_i, nf, H_i, W_i]
-            # ground truth sampled at the centre of each stride-4 cell of the /32-padded canvas
-            # (deformable_detr.py:353-362): zero-pad to the canvas, then [s//2::s]
-            m = m[..., s // 2::s, s // 2::s]
-            assert m.shape[-2] <= h and m.shape[-1] <= w
-            picked.append(F.pad(m.to(src.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
-        tgt = torch.cat(picked) if picked else src.new_zeros((0, nf, h, w))
+        picked = [t["masks"][j.to(t["masks"].device)] for t, (_, j) in zip(targets, indices)]   # [n_i, nf, H_i, W_i] each
+        tgt = gt_canvas(picked, s, h, w, src.dtype) if picked else src.new_zeros((0, nf, h, w))
         if tgt.shape[0] == 0:
             zero = (src * 0).sum()
             return {"loss_mask": zero, "loss_dice": zero}
@@ -287,13 +340,9 @@ class SetCriterion(nn.Module):
 
     def _loss_masks_fused(self, src, targets, indices, num_boxes):
         """`loss_masks` through the fused kernel: the matched targets are named by index (into the clips' targets laid
-        back to back) instead of gathered."""
+        back to back: `flat_pairs` of the one layer) instead of gathered."""
         from ..ops.mask_loss import mask_focal_dice
-        start, row_gt = 0, []
-        for t, (_, j) in zip(targets, indices):
-            row_gt.append(j.to(torch.int64) + start)
-            start += len(t["labels"])
-        row_gt = torch.cat(row_gt) if row_gt else torch.zeros(0, dtype=torch.int64)
+        row_gt = flat_pairs([indices], [len(t["labels"]) for t in targets]).tgt
         if row_gt.numel() == 0:
             zero = (src * 0).sum()
             return {"loss_mask": zero, "loss_dice": zero}
@@ -326,9 +375,9 @@ class SetCriterion(nn.Module):
         if isinstance(indices_list, DeviceMatch):      # matched on the device: the index tensors are there already
             lay, clip, qry, tgt = indices_list
         else:                                          # stacked index tensors, built on the host, one transfer each
-            lay, clip, qry, tgt = HungarianMatcher._upload(indices_list, [len(t["labels"]) for t in targets], dev)
+            lay, clip, qry, tgt = flat_pairs(indices_list, [len(t["labels"]) for t in targets], dev)
         n = len(qry) // Ld
-        names = [f"_{l}" for l in range(Ld - 1)] + [""]
+        names = layer_suffixes(Ld)
         out = {}
         # labels (focal): mean over Q * Q = sum over Q
         all_labels = torch.cat([t["labels"] for t in targets]).to(dev)
@@ -343,13 +392,7 @@ class SetCriterion(nn.Module):
         else:
             onehot = torch.zeros_like(logits)
             onehot[lay, clip, qry, all_labels[tgt]] = torch.ones((), dtype=logits.dtype, device=dev)   # a Python 1 is uploaded
-            p = logits.sigmoid()
-            ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
-            p_t = p * onehot + (1 - p) * (1 - onehot)
-            focal = ce * (1 - p_t) ** 2.0
-            if self.focal_alpha >= 0:
-                focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
-            loss_ce = focal.mean(2).sum((1, 2)) / num_boxes * Q
+            loss_ce = focal_term(logits, onehot, self.focal_alpha).mean(2).sum((1, 2)) / num_boxes * Q
             with torch.no_grad():
                 if n:
                     sel = logits[-1][clip[-n:], qry[-n:]]
@@ -359,9 +402,8 @@ class SetCriterion(nn.Module):
             # boxes (L1 + GIoU over the clip's frames)
             pred = boxes.transpose(2, 3)[lay, clip, qry]                                   # [Ld*n, T, 4]
             all_boxes = torch.cat([t["boxes"].reshape(-1, T, 4) for t in targets]).to(pred)
-            want = all_boxes[tgt]
-            l1 = (pred - want).abs().flatten(1).sum(1).view(Ld, n).sum(1) / T / num_boxes
-            g = giou_loss(box_cxcywh_to_xyxy(pred.flatten(0, 1)), box_cxcywh_to_xyxy(want.flatten(0, 1)))
+            l1, g = box_terms(pred, all_boxes[tgt])                                        # [Ld*n], [Ld*n, T]
+            l1 = l1.view(Ld, n).sum(1) / T / num_boxes
             g = g.view(Ld, n * T).sum(1) / T / num_boxes
         # masks (focal + dice)
         if n and self.fused_mask_loss:
@@ -371,20 +413,12 @@ class SetCriterion(nn.Module):
             loss_dice = dice.view(Ld, n).sum(1) / num_boxes
         elif n:
             h, w = masks.shape[-2:]
-            s_ = self.mask_out_stride
-            gt = []
-            for t in targets:
-                m = t["masks"][..., s_ // 2::s_, s_ // 2::s_]
-                gt.append(F.pad(m.to(masks.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
-            gt = torch.cat(gt).to(dev)[tgt].flatten(1)                                 # [Ld*n, T*h*w]
+            gt = gt_canvas([t["masks"] for t in targets], self.mask_out_stride, h, w, masks.dtype)
+            gt = gt.to(dev)[tgt].flatten(1)                                            # [Ld*n, T*h*w]
             src = masks.flatten(1)
-            pm = src.sigmoid()
-            ce_m = F.binary_cross_entropy_with_logits(src, gt, reduction="none")
-            pt_m = pm * gt + (1 - pm) * (1 - gt)
-            fm = (0.25 * gt + 0.75 * (1 - gt)) * ce_m * (1 - pt_m) ** 2.0
-            loss_mask = fm.mean(1).view(Ld, n).sum(1) / num_boxes
-            dice = 1 - (2 * (pm * gt).sum(1) + 1) / (pm.sum(1) + gt.sum(1) + 1)
-            loss_dice = dice.view(Ld, n).sum(1) / num_boxes
+            pm = src.sigmoid()                                                         # one sigmoid for both terms
+            loss_mask = focal_term(src, gt, p=pm).mean(1).view(Ld, n).sum(1) / num_boxes
+            loss_dice = dice_term(pm, gt).view(Ld, n).sum(1) / num_boxes
         else:
             loss_mask = loss_dice = (masks * 0).sum() + torch.zeros(Ld, device=dev)
         for kind, per_layer in (("loss_ce", loss_ce), ("loss_bbox", l1), ("loss_giou", g), ("loss_mask", loss_mask),

@@ -33,7 +33,7 @@ from torch import nn
 
 from ..heads import dynamic_mask_head, loss_reid
 from ..registry import META_ARCH_REGISTRY
-from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh
+from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, reid_terms_fused, sample_aux_masks, select_pos_neg_masks
 from .idol_transformer import DeformableTransformer
 from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
@@ -263,10 +263,9 @@ class IDOL(nn.Module):
             indices_list, matched = self.criterion.matcher.match_all_layers(logits, boxes, det_t)
         # the selected queries of every decoder layer on every key frame: one gather, one controller
         # call, one mask-head launch
-        q_host = [[torch.nonzero(sel).flatten() for sel, _ in ind] for ind in indices_list]
-        lay = torch.cat([torch.full_like(q, l) for l, layer in enumerate(q_host) for q in layer]).to(self.device, non_blocking=True)
-        img = torch.cat([torch.full_like(q, i) for layer in q_host for i, q in enumerate(layer)]).to(self.device, non_blocking=True)
-        qry = torch.cat([q for layer in q_host for q in layer]).to(self.device, non_blocking=True)
+        counts = layer_counts(indices_list)
+        match = flat_pairs(indices_list, [len(t["labels"]) for t in det_t], self.device, non_blocking=True)
+        lay, img, qry = match.lay, match.clip, match.qry          # the one pair list: these rows are the criterion's rows
         key_hs = hs[:, 0::2]                                                            # [Ld, bz, Q, C]
         scale = torch.stack([scale_tensor([sizes[i][1], sizes[i][0]], self.device) for i in range(bz)])   # [bz, (w, h)]
         params = self.detr.controller(key_hs[lay, img, qry])
@@ -285,9 +284,9 @@ class IDOL(nn.Module):
         else:
             qd = reid_terms(embeds[0::2], embeds[1::2], matched, selections, loss_reid)
         if self.deep_supervision:   # every decoder layer's losses in one pass over stacked tensors
-            loss = self.criterion.forward_all_layers(logits, boxes, masks, det_t, indices_list, qd)
+            loss = self.criterion.forward_all_layers(logits, boxes, masks, det_t, match, qd, counts=counts)
         else:
-            n_last = sum(len(q) for q in q_host[-1])
+            n_last = counts[-1]
             outputs = {"pred_logits": logits[-1], "pred_boxes": boxes[-1], "pred_masks": masks[masks.shape[0] - n_last:],
                        "pred_qd": qd}
             loss = self.criterion(outputs, det_t, ref_t, indices_list)

@@ -18,6 +18,10 @@ Two quirks of the reference are kept on purpose, because they change results: th
 "matched to several boxes" mask in the repair loop is the one computed BEFORE the loop
 (matcher.py:156-158 reuses `anchor_matching_gt`), and the k=10 / k=100 selections of
 pos_neg_select share one cost matrix, so repairs made by the first are seen by the second.
+`IDOLCriterion` derives from SeqFormer's `SetCriterion` (criterion.py): constructor, `fused_mask_loss` / `fused_set_loss`
+switches, the flat pair list (`flat_pairs`) and the loss terms (`focal_term`, `dice_term`, `gt_canvas`, `box_terms`) are
+that module's; what is IDOL's own here is the `ref_targets` signatures, the normalisation by the selected queries of
+each layer, the segment sums of `forward_all_layers` and the reid losses.
 `OTAMatcher.match_all_layers_device` is the same matching by one kernel (vnext_amd/csrc/ota_match.hip; opt-in through
 `IDOL.device_matching`): the host forms here stay the yardstick it is tested against, and what runs when it declines.
 """
@@ -29,7 +33,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .criterion import box_cxcywh_to_xyxy, dice_loss, giou_loss, pairwise_giou, sigmoid_focal_loss
+from .criterion import (DeviceMatch, SetCriterion, box_cxcywh_to_xyxy, box_terms, dice_loss, dice_term, flat_pairs, focal_term,
+                        giou_loss, gt_canvas, layer_counts, layer_suffixes, pairwise_giou, sigmoid_focal_loss)
 
 
 class _one_thread:
@@ -255,20 +260,13 @@ def select_pos_neg_masks(ref_boxes, ref_prob, ref_targets, rng=_random):
     return sample_aux_masks(pos_neg_masks(ref_boxes, ref_prob, ref_targets), rng)
 
 
-class IDOLCriterion(nn.Module):
+class IDOLCriterion(SetCriterion):
     """labels / boxes / masks on the key frame with simOTA indices + the reid losses between
-    key and reference frame (deformable_detr.py:236-494)."""
+    key and reference frame (deformable_detr.py:236-494).  The constructor, the `fused_mask_loss` / `fused_set_loss`
+    switches and the shared terms are `SetCriterion`'s; the loss methods take `ref_targets` as the reference's do."""
 
     def __init__(self, num_classes, matcher, weight_dict, losses, focal_alpha=0.25, mask_out_stride=4, num_frames=1):
-        super().__init__()
-        self.num_classes, self.matcher, self.weight_dict, self.losses = num_classes, matcher, weight_dict, losses
-        self.focal_alpha, self.mask_out_stride, self.num_frames = focal_alpha, mask_out_stride, num_frames
-        # mask losses from the fused kernel (vnext_amd/ops/mask_loss.py): the ground truth read in place, one pass each
-        # way (opt-in: train.enable_fused_mask_loss).  CUDA tensors only -- there is no fallback behind the switch
-        self.fused_mask_loss = False
-        # class focal + box L1 / GIoU of `forward_all_layers` from the fused op (vnext_amd/ops/set_loss.py; opt-in:
-        # train.enable_fused_set_loss).  CUDA tensors only -- there is no fallback behind the switch
-        self.fused_set_loss = False
+        super().__init__(num_classes, matcher, weight_dict, losses, focal_alpha, mask_out_stride, num_frames)
         # both reid losses of every image from one op (`reid_terms_fused` below, vnext_amd/ops/reid_loss.py; opt-in:
         # train.enable_fused_reid_loss).  Read by `IDOL.losses`, which takes that path for CUDA embeddings only
         self.fused_reid_loss = False
@@ -310,39 +308,18 @@ class IDOLCriterion(nn.Module):
             src = torch.cat(list(src), 1)[0]
         h, w = src.shape[-2:]
         s = self.mask_out_stride
-        if self.fused_mask_loss:
-            return self._loss_masks_fused(src, targets, indices)
-        picked = []
-        for i, (_, gt) in enumerate(indices):
-            if len(gt):
-                m = targets[i]["masks"][gt.to(targets[i]["masks"].device)][..., s // 2::s, s // 2::s]
-                picked.append(F.pad(m.to(src.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2]))[:, None])
+        if self.fused_mask_loss:                 # normalised by the rows, as below
+            assert src.shape[1] == 1
+            return self._loss_masks_fused(src, targets, indices, src.shape[0])
+        picked = [targets[i]["masks"][gt.to(targets[i]["masks"].device)] for i, (_, gt) in enumerate(indices) if len(gt)]
         if not picked:
             zero = (src * 0).sum()
             return {"loss_mask": zero, "loss_dice": zero}
-        tgt = torch.cat(picked)
+        tgt = gt_canvas(picked, s, h, w, src.dtype)[:, None]
         n = src.shape[0]
         assert src.shape == tgt.shape
         return {"loss_mask": sigmoid_focal_loss(src.flatten(1), tgt.flatten(1), n),
                 "loss_dice": dice_loss(src.flatten(1), tgt.flatten(1), n)}
-
-    def _loss_masks_fused(self, src, targets, indices):
-        """`loss_masks` through the fused kernel: the selected targets are named by index (into the images' targets laid
-        back to back) instead of gathered."""
-        from ..ops.mask_loss import mask_focal_dice
-        start, row_gt = 0, []
-        for i, (_, gt) in enumerate(indices):
-            if len(gt):
-                row_gt.append(gt.to(src.device, torch.int64) + start)
-            start += len(targets[i]["labels"])
-        if not row_gt:
-            zero = (src * 0).sum()
-            return {"loss_mask": zero, "loss_dice": zero}
-        row_gt = torch.cat(row_gt)
-        n = src.shape[0]
-        assert n == len(row_gt) and src.shape[1] == 1
-        focal, dice = mask_focal_dice(src, [t["masks"] for t in targets], row_gt, self.mask_out_stride)
-        return {"loss_mask": focal.sum() / n, "loss_dice": dice.sum() / n}
 
     def loss_reid(self, outputs, targets, ref_targets, indices, num_boxes):
         """outputs['pred_qd'] = {"contrast": sum over instances, "aux": sum over instances,
@@ -354,23 +331,22 @@ class IDOLCriterion(nn.Module):
         return {"loss_reid": qd["contrast"] / qd["count"], "loss_reid_aux": qd["aux"] / qd["count"]}
 
     # ---- all decoder layers in one pass ------------------------------------------------------
-    def forward_all_layers(self, logits, boxes, masks, targets, indices_list, pred_qd):
+    def forward_all_layers(self, logits, boxes, masks, targets, indices_list, pred_qd, counts=None):
         """`forward` for every decoder layer at once: logits [Ld, bz, Q, K], boxes [Ld, bz, Q, 4], masks
         [sum over layers of n_l, 1, h, w] (layer-major, images in order, queries ascending -- what the
-        fused mask head returns), indices_list[layer][image] = (selected [Q] bool, gt idx).  simOTA
+        fused mask head returns), indices_list[layer][image] = (selected [Q] bool, gt idx) on the host, or the
+        `DeviceMatch` made of it (`flat_pairs`) together with `counts`, the pairs per layer as host integers
+        (`layer_counts`): the device vectors are not read back for them.  simOTA
         selects a different number of queries per layer, so per-layer sums are segment sums over one
         flat list.  Same names and numbers as `forward` with deep supervision."""
         Ld, bz, Q, K = logits.shape
         dev = logits.device
-        q_host = [[torch.nonzero(sel).flatten() for sel, _ in ind] for ind in indices_list]
-        counts = [sum(len(q) for q in layer) for layer in q_host]
-        lay = torch.cat([torch.full_like(q, l) for l, layer in enumerate(q_host) for q in layer]).to(dev, non_blocking=True)
-        img = torch.cat([torch.full_like(q, i) for layer in q_host for i, q in enumerate(layer)]).to(dev, non_blocking=True)
-        qry = torch.cat([q for layer in q_host for q in layer]).to(dev, non_blocking=True)
-        start = [0]
-        for t in targets:
-            start.append(start[-1] + len(t["labels"]))
-        tgt = torch.cat([gt.long() + start[i] for ind in indices_list for i, (_, gt) in enumerate(ind)]).to(dev, non_blocking=True)
+        if isinstance(indices_list, DeviceMatch):
+            assert counts is not None and len(counts) == Ld, "a DeviceMatch comes with the host's per-layer counts"
+            lay, img, qry, tgt = indices_list
+        else:
+            counts = layer_counts(indices_list)
+            lay, img, qry, tgt = flat_pairs(indices_list, [len(t["labels"]) for t in targets], dev, non_blocking=True)
         denom = torch.tensor([max(c, 1) for c in counts], dtype=logits.dtype, device=dev)
         present = torch.tensor([1.0 if c else 0.0 for c in counts], dtype=logits.dtype, device=dev)
 
@@ -388,42 +364,30 @@ class IDOLCriterion(nn.Module):
         else:
             onehot = torch.zeros_like(logits)
             onehot[lay, img, qry, all_labels[tgt]] = 1
-            p = logits.sigmoid()
-            ce = F.binary_cross_entropy_with_logits(logits, onehot, reduction="none")
-            focal = ce * (1 - (p * onehot + (1 - p) * (1 - onehot))) ** 2.0
-            if self.focal_alpha >= 0:
-                focal = (self.focal_alpha * onehot + (1 - self.focal_alpha) * (1 - onehot)) * focal
-            loss_ce = focal.mean(2).sum((1, 2)) / denom * Q
+            loss_ce = focal_term(logits, onehot, self.focal_alpha).mean(2).sum((1, 2)) / denom * Q
             # boxes
             pred = boxes[lay, img, qry]
-            want = torch.cat([t["boxes"].reshape(-1, 4) for t in targets]).to(pred)[tgt]
-            l1 = per_layer((pred - want).abs().sum(1)) / denom * present
-            giou = per_layer(giou_loss(box_cxcywh_to_xyxy(pred), box_cxcywh_to_xyxy(want))) / denom * present
+            l1, giou = box_terms(pred, torch.cat([t["boxes"].reshape(-1, 4) for t in targets]).to(pred)[tgt])
+            l1 = per_layer(l1) / denom * present
+            giou = per_layer(giou) / denom * present
         # masks
-        h, w = masks.shape[-2:]
-        s_ = self.mask_out_stride
-        gt_masks = []
-        for t in (() if self.fused_mask_loss else targets):       # the fused kernel reads t["masks"] in place
-            m = t["masks"][..., s_ // 2::s_, s_ // 2::s_]
-            gt_masks.append(F.pad(m.to(masks.dtype), (0, w - m.shape[-1], 0, h - m.shape[-2])))
-        if sum(counts) and self.fused_mask_loss:
+        if sum(counts) and self.fused_mask_loss:                  # the fused kernel reads t["masks"] in place
             from ..ops.mask_loss import mask_focal_dice
             fm, dice = mask_focal_dice(masks, [t["masks"] for t in targets], tgt, self.mask_out_stride)   # [sum n_l] each
             loss_mask = per_layer(fm) / denom * present
             loss_dice = per_layer(dice) / denom * present
         elif sum(counts):
-            gt_m = torch.cat(gt_masks).to(dev)[tgt].flatten(1)
+            h, w = masks.shape[-2:]
+            gt_m = gt_canvas([t["masks"] for t in targets], self.mask_out_stride, h, w, masks.dtype)
+            gt_m = gt_m.to(dev)[tgt].flatten(1)
             src = masks.flatten(1)
-            pm = src.sigmoid()
-            ce_m = F.binary_cross_entropy_with_logits(src, gt_m, reduction="none")
-            fm = (0.25 * gt_m + 0.75 * (1 - gt_m)) * ce_m * (1 - (pm * gt_m + (1 - pm) * (1 - gt_m))) ** 2.0
-            loss_mask = per_layer(fm.mean(1)) / denom * present
-            dice = 1 - (2 * (pm * gt_m).sum(1) + 1) / (pm.sum(1) + gt_m.sum(1) + 1)
-            loss_dice = per_layer(dice) / denom * present
+            pm = src.sigmoid()                                    # one sigmoid for both terms
+            loss_mask = per_layer(focal_term(src, gt_m, p=pm).mean(1)) / denom * present
+            loss_dice = per_layer(dice_term(pm, gt_m)) / denom * present
         else:
             loss_mask = loss_dice = (masks * 0).sum() + torch.zeros(Ld, dtype=logits.dtype, device=dev)
         out = self.loss_reid({"pred_qd": pred_qd, "pred_logits": logits[-1]}, None, None, None, None)
-        for l, suffix in enumerate([f"_{l}" for l in range(Ld - 1)] + [""]):
+        for l, suffix in enumerate(layer_suffixes(Ld)):
             out["loss_ce" + suffix], out["loss_bbox" + suffix], out["loss_giou" + suffix] = loss_ce[l], l1[l], giou[l]
             out["loss_mask" + suffix], out["loss_dice" + suffix] = loss_mask[l], loss_dice[l]
         return out

@@ -30,7 +30,7 @@ from torch import nn
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
-from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh
+from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from ..registry import META_ARCH_REGISTRY
 from .seqformer_transformer import DeformableTransformer, inverse_sigmoid
 
@@ -552,13 +552,11 @@ class SeqFormer(nn.Module):
         Ld, N, T = boxes.shape[:3]
         if self.device_matching and self.deep_supervision and logits.is_cuda:
             # cost + assignment of every (layer, clip) in one kernel; the indices stay on the device
-            indices_list = self.criterion.matcher.match_all_layers_device(logits, boxes, targets)
-            lay, clip, qry = indices_list.lay, indices_list.clip, indices_list.qry
+            match = self.criterion.matcher.match_all_layers_device(logits, boxes, targets)
         else:
             indices_list = self.criterion.matcher.match_all_layers(logits, boxes, targets)
-            lay = torch.cat([torch.full_like(q, l) for l, ind in enumerate(indices_list) for q, _ in ind]).to(self.device)
-            clip = torch.cat([torch.full_like(q, i) for ind in indices_list for i, (q, _) in enumerate(ind)]).to(self.device)
-            qry = torch.cat([q for ind in indices_list for q, _ in ind]).to(self.device)
+            match = flat_pairs(indices_list, [len(t["labels"]) for t in targets], self.device)
+        lay, clip, qry = match.lay, match.clip, match.qry         # the one pair list: these rows are the criterion's rows
         # the matched instances of every decoder layer, on every frame of their clip: one gather, one
         # controller call, one mask-head launch (the reference: a Python loop over layers x clips x frames)
         params = self.detr.controller(hs[lay, clip, qry])                         # [Ld*n, 169]
@@ -574,9 +572,9 @@ class SeqFormer(nn.Module):
         if masks.shape[0] == 0:  # nothing matched anywhere: keep the mask branch in the autograd graph
             masks = masks + 0 * (feats.sum() + sum(p.sum() for p in self.detr.controller.parameters()))
         if self.deep_supervision:   # every decoder layer's losses in one pass over stacked tensors
-            return self.criterion.forward_all_layers(logits, boxes, masks, targets, indices_list, weighted=True)
-        else:
-            n_last = sum(len(q) for q, _ in indices_list[-1])
+            return self.criterion.forward_all_layers(logits, boxes, masks, targets, match, weighted=True)
+        else:                       # (matched on the host: the device matching is for deep supervision only)
+            n_last = layer_counts(indices_list)[-1]
             outputs = {"pred_logits": logits[-1], "pred_boxes": boxes[-1], "pred_masks": masks[masks.shape[0] - n_last:]}
             loss = self.criterion(outputs, targets, indices_list)
         w = self.criterion.weight_dict
