@@ -226,6 +226,23 @@ class IDOL_Tracker(object):
 METRICS = {"bisoftmax": 0, "softmax": 1, "cosine": 2}
 
 
+def state_layout(capacity, channels, memory_len):
+    """The device state blob of `trk_views` (vnext_amd/csrc/tracker.hip), as plain arithmetic:
+    -> ({name: (byte offset, numpy dtype, shape)}, total bytes).  A 64-byte header of int32 counters, five
+    int32[capacity] arrays, then embed, memo, long_embed, long_score in fp32; every array starts on a 16-byte
+    boundary.  The total equals `vnx_tracker_state_bytes` (tests/test_tracker_state.py)."""
+    cap, C, mem = int(capacity), int(channels), int(memory_len)
+    fields = [("hdr", np.int32, (16,))] + \
+        [(k, np.int32, (cap,)) for k in ("slot_id", "last_frame", "exist", "label", "long_len")] + \
+        [("embed", np.float32, (cap, C)), ("memo", np.float32, (cap, C)),
+         ("long_embed", np.float32, (cap, mem, C)), ("long_score", np.float32, (cap, mem))]
+    layout, offset = {}, 0
+    for name, dtype, shape in fields:
+        layout[name] = (offset, dtype, shape)
+        offset += (int(np.prod(shape)) * 4 + 15) & ~15
+    return layout, offset
+
+
 class DeviceTracker(object):
     """IDOL_Tracker with the tracklets in device memory (vnext_amd/csrc/tracker.hip; reference
     projects/IDOL/idol/models/tracker.py:50-298).  Same constructor arguments plus `capacity`
@@ -288,6 +305,26 @@ class DeviceTracker(object):
     @property
     def num_tracklets(self):
         return self.counters()[0]
+
+    def tracklets(self):
+        """The live tracklets as the host class keeps them, read from the device with ONE copy of the state blob:
+        {id: dict(slot, embed [C], memo [C], long_embed [len, C], long_score [len], label, last_frame, exist_frame)},
+        numpy fp32 arrays, oldest remembered frame first.  For debugging and tests; nothing on the product path
+        calls it."""
+        if self.state is None:
+            return {}
+        blob = self.state.cpu().numpy()
+        layout, total = state_layout(self.cfg.capacity, self.cfg.channels, self.cfg.memory_len)
+        assert total == blob.size, f"state_layout says {total} bytes, the device blob has {blob.size}"
+        a = {k: blob[o:o + int(np.prod(shape)) * 4].view(dtype).reshape(shape) for k, (o, dtype, shape) in layout.items()}
+        out = {}
+        for s in np.nonzero(a["slot_id"] >= 0)[0].tolist():
+            n = int(a["long_len"][s])
+            out[int(a["slot_id"][s])] = dict(
+                slot=s, embed=a["embed"][s].copy(), memo=a["memo"][s].copy(), long_embed=a["long_embed"][s, :n].copy(),
+                long_score=a["long_score"][s, :n].copy(), label=int(a["label"][s]), last_frame=int(a["last_frame"][s]),
+                exist_frame=int(a["exist"][s]))
+        return out
 
     def match_device(self, bboxes, labels, masks, track_feats, frame_id):
         from .. import _lib

@@ -183,15 +183,16 @@ def set_rank_affinity(local_rank: int, local_world: int):
         except Exception:
             return []
 
-    node = node_of(local_rank) if torch.cuda.is_available() else -1
-    pool, share, slot = [], local_world, local_rank
-    if node >= 0:
-        pool = cpus_of(node)
-        mates = [r for r in range(local_world) if node_of(r) == node]
-        if pool and local_rank in mates:
-            share, slot = len(mates), mates.index(local_rank)
-    if not pool:
-        pool, node = allowed, -1
+    # one layout for all ranks: the NUMA pools only when EVERY rank's GPU and its node's cores can be read.  A rank
+    # that fell back to the even split while another took its whole node overlapped it (a host that shows this process
+    # fewer GPUs than ranks: tests/test_model_ddp.py::test_rank_affinity_partitions_the_allowed_cores).
+    nodes = [node_of(r) for r in range(local_world)] if torch.cuda.is_available() else [-1]
+    pools = {nd: cpus_of(nd) for nd in set(nodes) if nd >= 0}
+    pool, node, share, slot = allowed, -1, local_world, local_rank
+    if min(nodes) >= 0 and all(pools.values()) and local_rank < len(nodes):
+        node = nodes[local_rank]
+        mates = [r for r in range(local_world) if nodes[r] == node]
+        pool, share, slot = pools[node], len(mates), mates.index(local_rank)
     per = max(1, len(pool) // max(1, share))
     mine = pool[slot * per:(slot + 1) * per] or pool
     try:
