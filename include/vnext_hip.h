@@ -660,7 +660,7 @@ int vnx_set_loss_backward(const void* logits, const void* boxes, const void* lay
  * lower index.  No atomics, fixed evaluation order: bit-identical run to run.  No workspace, no allocation, no
  * synchronisation.  A call that needs more than 64 KB of LDS (41 targets or more at 300 queries) raises the kernel's
  * dynamic-LDS limit with hipFuncSetAttribute, once per device, the first time such a call is made there: make that call
- * once outside a stream capture.  (Capture itself is not exercised by this library's tests.)
+ * once outside a stream capture.
  * out int32 [det_problems + ref_problems][out_stride], out_stride >= vnx_idol_match_out_words(targets_max, queries):
  *   [0] status: 0 solved; 1 a non-finite cost or IoU; 2 the repair loop reached its bound (count + 8 rounds); 3 a label
  *       outside [0, classes) or a (first, count) outside the arrays / above targets_max.  Not 0: no result, match on the host.
