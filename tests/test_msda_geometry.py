@@ -86,7 +86,7 @@ def scale(x):
 
 def boundary_mask(loc, sh, eps=1e-4):
     """samples not within eps pixels of a pixel line: there the bilinear gradient jumps, and fp32 and fp64 may disagree
-    on the side"""
+    on the side.  The lines themselves are tested in test_msda_lattice.py, on power-of-two maps where the two agree."""
     wh = torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
     px = loc.double() * wh - 0.5
     return ((px - px.round()).abs() > eps).all(-1, keepdim=True).numpy()

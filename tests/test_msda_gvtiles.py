@@ -81,7 +81,9 @@ def oracle(case, vdt=torch.float32, ldt=torch.float32):
 
 
 def boundary_mask(loc, sh, eps=1e-4):
-    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
+    """samples not within eps pixels of a pixel line (test_msda_geometry.boundary_mask).  The lines themselves are tested in
+    test_msda_lattice.py, on power-of-two maps where fp32 and fp64 agree on the side."""
+    wh =torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
     px = loc.double() * wh - 0.5
     return ((px - px.round()).abs() > eps).all(-1, keepdim=True).numpy()
 

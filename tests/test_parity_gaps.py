@@ -46,7 +46,8 @@ def off_the_pixel_grid(loc, sh, eps=1e-4):
     """[B,Lq,M,L,P,1] mask of samples whose pixel coordinates are at least `eps` away from an integer.  The
     gradient with respect to the location is discontinuous across a pixel boundary (another pair of taps takes
     over), so a sample that fp32 and fp64 arithmetic put on different sides has no common reference value
-    there; everything else the op produces is continuous in the location."""
+    there; everything else the op produces is continuous in the location.  The lines themselves are tested in
+    test_msda_lattice.py, on power-of-two maps where fp32 and fp64 agree on the side."""
     wh = torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
     px = loc.double() * wh - 0.5
     return ((px - px.round()).abs() > eps).all(-1, keepdim=True).numpy()

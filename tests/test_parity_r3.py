@@ -59,7 +59,9 @@ def scale(x):
 
 
 def off_the_pixel_grid(loc, sh, eps=1e-4):
-    wh = torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
+    """samples at least eps pixels away from every pixel line (test_parity_gaps.off_the_pixel_grid).  The lines themselves are
+    tested in test_msda_lattice.py, on power-of-two maps where fp32 and fp64 agree on the side."""
+    wh =torch.stack([sh[:, 1], sh[:, 0]], -1).double().view(1, 1, 1, -1, 1, 2)
     px = loc.double() * wh - 0.5
     return ((px - px.round()).abs() > eps).all(-1, keepdim=True).numpy()
 
