@@ -28,7 +28,7 @@ int vnx_debug_wall_clock_khz(void);
 int vnx_debug_row_gather_probe(const void* rows, size_t n_rows, const uint32_t* idx, size_t n_idx, int in_flight,
                                float* sink, void* hip_stream);
 
-/* Host-side view of the unit grid of the tile-fed grad_value kernel (vnext_amd/csrc/vnx_common.h: gv_level_grid;
+/* Host-side view of the unit grid of the tile-fed grad_value kernel (vnext_amd/csrc/msda_units.h: gv_level_grid;
  * msda_d32_gvtiles.hip): the launcher sizes the grid from the pixel count alone, the kernel derives the units from the
  * level shapes on the device -- the sum of the latter must never pass the former, or a unit's rows would be lost.
  * host_shapes: [levels][2] = (H, W) in HOST memory.  Writes the workgroups per (batch, head) the kernel will use and
@@ -39,7 +39,7 @@ int vnx_debug_gvtiles_units(const int64_t* host_shapes, int levels, int num_quer
                             int* units_used, int* units_bound, long long* partial_rows_used, long long* partial_rows_bound);
 
 /* The same check for the self-decoding grad_value kernel of calls below 1 024 queries (msda_d32_gvdirect.hip;
- * gvd_level_split in vnx_common.h; batch_heads = batch x heads decides whether small levels are cut in two).  Writes, per
+ * gvd_level_split in msda_units.h; batch_heads = batch x heads decides whether small levels are cut in two).  Writes, per
  * (batch, head), the workgroups the kernel's level table yields and the
  * launcher's bound; per level (any of the three arrays may be null; `levels` entries each) the units, the rows per unit
  * and log2 of the 8-lane groups that share a row.  0 on success.  No GPU needed (tests/test_gvdirect_model.py). */

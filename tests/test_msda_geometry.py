@@ -1,7 +1,7 @@
 """MSDA backward at geometries other than the default models' 4 levels x 4 points: the self-decoding grad_value kernel
 (vnext_amd/csrc/msda_d32_gvdirect.hip) with 5 to 64 points, one to eight levels, query counts around a pass
 (min(304, 1216 / P) queries) and batch x heads on both sides of gvd_units_min's switch -- the geometries where a unit's
-rows may need more slots than the walk's 768 (gvd_level_split, vnx_common.h; the host side of it: test_gvdirect_model.py).
+rows may need more slots than the walk's 768 (gvd_level_split, msda_units.h; the host side of it: test_gvdirect_model.py).
 
 Everything through the C ABI (vnx_msda_backward, and vnx_msda_fused_backward where L * P == 16) into buffers prefilled
 with NaN between guard words: every element must be written, finite and next to the fp64 C oracle, and no guard word may

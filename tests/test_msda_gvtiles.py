@@ -116,7 +116,7 @@ def test_ragged_query_counts(Lq):
 def test_units_min_variants_on_small_levels(units_min, shapes):
     """variants 200 + x set the minimum number of units per level: the grad_loc kernel (which zeroes the rows of
     query-split levels), the grad_value kernel (which adds onto them) and the tile words must use ONE split
-    (gv_level_split, vnx_common.h).  Lq >= 1281 puts 16-pixel levels on both sides of the threshold."""
+    (gv_level_split, msda_units.h).  Lq >= 1281 puts 16-pixel levels on both sides of the threshold."""
     case = pixel_queries(shapes, 2, 1300, seed=units_min)
     check(run(case, 200 + units_min), oracle(case), case)
 
@@ -199,7 +199,7 @@ def test_fused_backward_records_path_and_tiles_path_agree(vdt):
     assert np.array_equal(res[430][1], res[0][1]) and np.array_equal(res[430][2], res[0][2])   # same kernel, same order
 
 
-# the unit grid of gv_level_grid (vnx_common.h): levels from 128 pixels of width up are cut into blocks of about
+# the unit grid of gv_level_grid (msda_units.h): levels from 128 pixels of width up are cut into blocks of about
 # 32 x 8 pixels, flat wide levels (H < 8) into wider blocks, narrow levels into bands of whole image rows
 WIDE = [(20, 130), (10, 65), (5, 33), (3, 17)]           # S = 3466: level 0 in blocks of 26 x 9 (5 x 3 of them)
 FLAT = [(5, 300), (3, 150), (2, 75), (1, 38)]            # S = 2138: levels 0 and 1 in flat blocks, H < 8

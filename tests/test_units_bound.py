@@ -1,5 +1,5 @@
 """The launcher of the tile-fed grad_value kernel sizes its grid from the pixel count S alone; the kernel derives its
-units from the level shapes on the device (gv_level_grid, vnx_common.h).  A unit past the grid would silently lose its
+units from the level shapes on the device (gv_level_grid, msda_units.h).  A unit past the grid would silently lose its
 rows, so the kernel's count is held to the launcher's bound here, on the host, through the debug ABI -- no GPU needed."""
 import ctypes
 import random

@@ -1,5 +1,5 @@
 """Exhaustive check behind the grid bound of the tile-fed grad_value kernel (msda_d32_gvtiles.hip, gvtiles_units_bound):
-a level of H x W pixels is cut by gv_level_grid (vnx_common.h; restated here with numpy) into at most
+a level of H x W pixels is cut by gv_level_grid (msda_units.h; restated here with numpy) into at most
 3 * H * W / 256 + units_min units.  Every H <= 1 200 (and a few larger) x W <= 20 000, units_min in {1, 2, 16}."""
 import numpy as np
 

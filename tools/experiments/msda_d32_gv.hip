@@ -37,7 +37,7 @@
 // them (deformable_transformer.py:97-106).  Every workgroup re-derives that
 // predicate; when it fails the kernel does nothing and the general path (atomics
 // into a zero-filled image) does the work -- see vnx_msda_backward in capi.hip.
-#include "vnx_common.h"
+#include "msda_units.h"
 
 namespace vnx {
 

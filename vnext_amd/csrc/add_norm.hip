@@ -30,34 +30,6 @@ constexpr int kAnMaxBlocks = 1024;   // workgroups of the backward = rows of the
 constexpr int kAnParts = 3;          // partial rows per workgroup: gamma, beta, and the bias folded into r (ABI 11)
 static_assert(kAnParts <= kAnWaves, "one wave per partial row");
 
-// murmur3-style mix of (element index, 64-bit seed) -> 32 uniform bits
-__device__ __forceinline__ uint32_t an_hash(uint32_t idx, uint32_t seed_lo, uint32_t seed_hi) {
-  uint32_t h = idx ^ seed_lo;
-  h *= 0xcc9e2d51u; h = (h << 15) | (h >> 17); h *= 0x1b873593u;
-  h ^= seed_hi;
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-
-// Effective seed of a launch: the host's 64 bits, mixed with a 64-bit word read from DEVICE memory when the caller
-// passes one.  A host integer is baked into a captured hipGraph -- every replay of a captured training step would drop
-// the same elements -- whereas a device word bumped once per step (by a captured `add_`) gives every replay
-// fresh masks; forward and backward of one step read the same word, so the backward still recomputes the mask.
-__device__ __forceinline__ void an_effective_seed(uint32_t& lo, uint32_t& hi, const unsigned long long* seed_device) {
-  if (seed_device == nullptr) return;
-  const unsigned long long s = *seed_device;                       // wave-uniform (scalar load)
-  uint32_t a = uint32_t(s) * 0x9E3779B1u, b = (uint32_t(s >> 32) + 0x7F4A7C15u) * 0x85EBCA77u;
-  a ^= a >> 15; b ^= b >> 13;
-  lo ^= a * 0xC2B2AE3Du;
-  hi ^= b * 0x27D4EB2Fu + a;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // z = x + keep * r * scale for this lane's four channels of `row`
 __device__ __forceinline__ float4_t an_residual(float4_t x, float4_t r, int64_t row, int lane, uint32_t threshold,
                                                 float scale, uint32_t seed_lo, uint32_t seed_hi) {
@@ -65,10 +37,10 @@ __device__ __forceinline__ float4_t an_residual(float4_t x, float4_t r, int64_t 
   const uint32_t base = uint32_t(row) * uint32_t(kAnC) + uint32_t(lane) * 4u;
   const uint32_t hi = seed_hi ^ uint32_t(uint64_t(row) >> 24);     // rows beyond 2^24 (4 G elements) still differ
   float4_t z = x;
-  if (an_hash(base + 0u, seed_lo, hi) >= threshold) z.x += r.x * scale;
-  if (an_hash(base + 1u, seed_lo, hi) >= threshold) z.y += r.y * scale;
-  if (an_hash(base + 2u, seed_lo, hi) >= threshold) z.z += r.z * scale;
-  if (an_hash(base + 3u, seed_lo, hi) >= threshold) z.w += r.w * scale;
+  if (dropout_hash(base + 0u, seed_lo, hi) >= threshold) z.x += r.x * scale;
+  if (dropout_hash(base + 1u, seed_lo, hi) >= threshold) z.y += r.y * scale;
+  if (dropout_hash(base + 2u, seed_lo, hi) >= threshold) z.z += r.z * scale;
+  if (dropout_hash(base + 3u, seed_lo, hi) >= threshold) z.w += r.w * scale;
   return z;
 }
 
@@ -82,7 +54,7 @@ add_dropout_layernorm_fwd_kernel(const float* __restrict__ x, const TR* __restri
   const int lane = threadIdx.x & 63;
   const int64_t row = int64_t(blockIdx.x) * kAnWaves + (threadIdx.x >> 6);
   if (row >= rows) return;
-  if (threshold != 0u) an_effective_seed(seed_lo, seed_hi, seed_device);
+  if (threshold != 0u) dropout_effective_seed(seed_lo, seed_hi, seed_device);
   const int64_t at = row * kAnC + lane * 4;
   const float4_t xv = *reinterpret_cast<const float4_t*>(x + at);
   float4_t rv = row4_load<TR>(r + at);
@@ -109,7 +81,7 @@ add_dropout_layernorm_bwd_kernel(const float* __restrict__ grad_y, const float* 
                                  int64_t rows, uint32_t threshold, float scale, uint32_t seed_lo, uint32_t seed_hi,
                                  const unsigned long long* __restrict__ seed_device) {
   __shared__ float4_t red[kAnParts][kAnWaves][64];
-  if (threshold != 0u) an_effective_seed(seed_lo, seed_hi, seed_device);
+  if (threshold != 0u) dropout_effective_seed(seed_lo, seed_hi, seed_device);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float4_t g = *reinterpret_cast<const float4_t*>(gamma + lane * 4);
   float4_t dg = {0.f, 0.f, 0.f, 0.f}, db = dg, dbias = dg;
@@ -130,10 +102,10 @@ add_dropout_layernorm_bwd_kernel(const float* __restrict__ grad_y, const float* 
     if (threshold != 0u) {
       const uint32_t base = uint32_t(row) * uint32_t(kAnC) + uint32_t(lane) * 4u;
       const uint32_t hi = seed_hi ^ uint32_t(uint64_t(row) >> 24);
-      dr.x = an_hash(base + 0u, seed_lo, hi) >= threshold ? dz.x * scale : 0.f;
-      dr.y = an_hash(base + 1u, seed_lo, hi) >= threshold ? dz.y * scale : 0.f;
-      dr.z = an_hash(base + 2u, seed_lo, hi) >= threshold ? dz.z * scale : 0.f;
-      dr.w = an_hash(base + 3u, seed_lo, hi) >= threshold ? dz.w * scale : 0.f;
+      dr.x = dropout_hash(base + 0u, seed_lo, hi) >= threshold ? dz.x * scale : 0.f;
+      dr.y = dropout_hash(base + 1u, seed_lo, hi) >= threshold ? dz.y * scale : 0.f;
+      dr.z = dropout_hash(base + 2u, seed_lo, hi) >= threshold ? dz.z * scale : 0.f;
+      dr.w = dropout_hash(base + 3u, seed_lo, hi) >= threshold ? dz.w * scale : 0.f;
     }
     dbias += dr;
     row4_store_nt<TR>(grad_r + at, dr);
@@ -194,11 +166,6 @@ static int an_check(const char* who, int dtype, int64_t rows, int channels, floa
   return VNX_OK;
 }
 
-static uint32_t an_threshold(float p) {      // keep iff hash >= threshold:  P(drop) = threshold / 2^32
-  const double t = double(p) * 4294967296.0;
-  return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 0xffffffffu : uint32_t(t + 0.5));
-}
-
 }  // namespace vnx
 
 using namespace vnx;
@@ -219,7 +186,7 @@ extern "C" int vnx_add_dropout_layernorm_forward(int dtype, const void* x, const
 #define VNX_AN_FWD(TR)                                                                                                   \
   hipLaunchKernelGGL(add_dropout_layernorm_fwd_kernel<TR>, dim3(uint32_t(blocks)), dim3(64 * kAnWaves), 0,               \
                      (hipStream_t)hip_stream, (const float*)x, (const TR*)r, (const float*)r_bias, (const float*)gamma,  \
-                     (const float*)beta, (float*)y, (float*)z, (float*)stats, int64_t(rows), an_threshold(p),           \
+                     (const float*)beta, (float*)y, (float*)z, (float*)stats, int64_t(rows), dropout_threshold(p),      \
                      1.f / (1.f - p), eps, uint32_t(seed), uint32_t(seed >> 32), seed_device)
   if (dtype == VNX_BF16) VNX_AN_FWD(bf16_t); else if (dtype == VNX_F16) VNX_AN_FWD(f16_t); else VNX_AN_FWD(float);
 #undef VNX_AN_FWD
@@ -246,7 +213,7 @@ extern "C" int vnx_add_dropout_layernorm_backward(int dtype, const void* grad_y,
 #define VNX_AN_BWD(TR)                                                                                                   \
     hipLaunchKernelGGL(add_dropout_layernorm_bwd_kernel<TR>, dim3(uint32_t(blocks)), dim3(64 * kAnWaves), 0, stream,       \
                        (const float*)grad_y, (const float*)z, (const float*)stats, (const float*)gamma, (float*)grad_x,   \
-                       (TR*)grad_r, (float*)partial, int64_t(rows), an_threshold(p), 1.f / (1.f - p), uint32_t(seed),     \
+                       (TR*)grad_r, (float*)partial, int64_t(rows), dropout_threshold(p), 1.f / (1.f - p), uint32_t(seed),\
                        uint32_t(seed >> 32), seed_device)
     if (dtype == VNX_BF16) VNX_AN_BWD(bf16_t); else if (dtype == VNX_F16) VNX_AN_BWD(f16_t); else VNX_AN_BWD(float);
 #undef VNX_AN_BWD

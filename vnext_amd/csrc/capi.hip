@@ -1,6 +1,7 @@
-// capi.hip -- the extern "C" surface of libvnext_hip.so (include/vnext_hip.h).
-// Argument validation, kernel selection and error reporting live here; the
-// kernels themselves are in msda_generic.hip / msda_d32.hip.
+// capi.hip -- the library-wide part of the extern "C" surface of libvnext_hip.so (include/vnext_hip.h: ABI version,
+// status strings, last error, the development build's variant knob, stamps), the MSDA entry points and the vnx_debug_*
+// MSDA aids.  MSDA argument validation, kernel selection (plan_backward) and error reporting live here; the MSDA kernels
+// themselves are in msda_generic.hip / msda_d32*.hip.  Every other op defines its entry points beside its kernels.
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -648,246 +649,6 @@ int vnx_msda_fused_backward(int value_dtype, int query_dtype, const void* value,
     return msda_split_levels_convert(value_dtype, spatial_shapes, level_start_index, split_image, grad_value, d,
                                      tiles, kv.gv_units, stream);
   return VNX_OK;
-}
-
-// ---- the Swin block's shifted-window attention (window_attn.hip) -------------------------------------------------
-size_t vnx_window_attention_partial_bytes(int batch, int height, int width, int heads, int window) {
-  return vnx::window_attention_partial_bytes(batch, height, width, heads, window);
-}
-
-int vnx_window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out,
-                                 void* lse, int batch, int height, int width, int heads, int head_dim, int row_stride,
-                                 int window, int shift, float scale, void* hip_stream) {
-  return vnx::window_attention_forward(dtype, qkv, qkv_bias, bias_table, out, lse, batch, height, width, heads, head_dim,
-                                       row_stride, window, shift, scale, hip_stream);
-}
-
-int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table,
-                                  const void* out, const void* lse, const void* grad_out, void* grad_qkv,
-                                  void* grad_bias_table, void* grad_pad_bias, void* partial, size_t partial_bytes,
-                                  int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
-                                  int shift, float scale, void* hip_stream) {
-  return vnx::window_attention_backward(dtype, qkv, qkv_bias, bias_table, out, lse, grad_out, grad_qkv, grad_bias_table,
-                                        grad_pad_bias, partial, partial_bytes, batch, height, width, heads, head_dim,
-                                        row_stride, window, shift, scale, hip_stream);
-}
-
-// ---- COCO RLE strings of a batch of masks (mask_rle.hip) ---------------------------------------------------------
-static int mask_rle_check(const char* fn, int mode, const void* input, int masks, int height, int width, int stride,
-                          int image_height, int image_width, int out_height, int out_width) {
-  if (mode != VNX_MASK_RLE_LOGITS && mode != VNX_MASK_RLE_BINARY) {
-    vnx::set_error("%s: unknown mode %d", fn, mode);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (masks < 0 || out_height < 1 || out_width < 1) {
-    vnx::set_error("%s: bad sizes (masks %d, out %d x %d)", fn, masks, out_height, out_width);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (int64_t(out_height) * out_width >= (int64_t(1) << 31)) {
-    vnx::set_error("%s: out %d x %d has 2^31 pixels or more (int32 counts)", fn, out_height, out_width);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  if (mode == VNX_MASK_RLE_LOGITS) {
-    if (height < 1 || width < 1 || stride < 1 || image_height < 1 || image_width < 1 ||
-        int64_t(image_height) > int64_t(height) * stride || int64_t(image_width) > int64_t(width) * stride) {
-      vnx::set_error("%s: bad sizes (map %d x %d, stride %d, image %d x %d)", fn, height, width, stride, image_height,
-                     image_width);
-      return VNX_ERR_INVALID_ARGUMENT;
-    }
-    if (int64_t(height) * width >= (int64_t(1) << 31)) {
-      vnx::set_error("%s: map %d x %d has 2^31 elements or more", fn, height, width);
-      return VNX_ERR_UNSUPPORTED;
-    }
-    if (masks > 0 && (reinterpret_cast<uintptr_t>(input) & 3) != 0) {
-      vnx::set_error("%s: logits must be 4-byte aligned", fn);
-      return VNX_ERR_INVALID_ARGUMENT;
-    }
-  }
-  if (masks > 0 && !input) {
-    vnx::set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  return VNX_OK;
-}
-
-int vnx_mask_rle_measure(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
-                         int image_width, int out_height, int out_width, void* lengths, void* hip_stream) {
-  const char* fn = "vnx_mask_rle_measure";
-  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
-                              out_width))
-    return st;
-  if (masks == 0) return VNX_OK;
-  if (!lengths) {
-    vnx::set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  return vnx::mask_rle_launch(false, mode, input, masks, height, width, stride, image_height, image_width, out_height,
-                              out_width, (int64_t*)lengths, nullptr, nullptr, 0, (hipStream_t)hip_stream);
-}
-
-int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int width, int stride, int image_height,
-                       int image_width, int out_height, int out_width, const void* offsets, void* arena,
-                       long long arena_bytes, void* hip_stream) {
-  const char* fn = "vnx_mask_rle_write";
-  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
-                              out_width))
-    return st;
-  if (arena_bytes < 0) {
-    vnx::set_error("%s: arena_bytes %lld < 0", fn, arena_bytes);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (masks == 0) return VNX_OK;
-  if (!offsets || !arena) {
-    vnx::set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  return vnx::mask_rle_launch(true, mode, input, masks, height, width, stride, image_height, image_width, out_height,
-                              out_width, nullptr, (const int64_t*)offsets, arena, int64_t(arena_bytes),
-                              (hipStream_t)hip_stream);
-}
-
-// ---- linear sum assignment on the device (lsap.hip) --------------------------------------------------------------------
-int vnx_seqformer_match(const void* logits, const void* boxes, const void* labels, const void* target_boxes,
-                        const void* offsets, int layers, int clips, int frames, int queries, int classes,
-                        int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
-                        void* query_index, void* target_index, void* cost_out, void* hip_stream) {
-  const char* fn = "vnx_seqformer_match";
-  if (layers < 0 || clips < 0 || frames < 1 || queries < 1 || classes < 1 || targets_total < 0 || targets_max < 0 ||
-      targets_max > targets_total) {
-    vnx::set_error("%s: bad sizes (layers %d, clips %d, frames %d, queries %d, classes %d, targets %d, largest clip %d)", fn,
-                   layers, clips, frames, queries, classes, targets_total, targets_max);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (layers == 0 || clips == 0 || targets_total == 0) return VNX_OK;
-  if (targets_max > queries || !vnx::lsap_fits(targets_max, queries)) {
-    vnx::set_error("%s: %d targets of one clip against %d queries: more targets than queries, or more than the LDS of a "
-                   "CU holds", fn, targets_max, queries);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  if (int64_t(layers) * clips >= (int64_t(1) << 31) ||
-      int64_t(layers) * clips * queries * (int64_t(classes) > int64_t(frames) * 4 ? classes : frames * 4) >= (int64_t(1) << 40)) {
-    vnx::set_error("%s: %d x %d problems are outside what the kernel addresses", fn, layers, clips);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  if (!logits || !boxes || !labels || !target_boxes || !offsets || !query_index || !target_index) {
-    vnx::set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  return vnx::seqformer_match_launch((const float*)logits, (const float*)boxes, (const int64_t*)labels,
-                                     (const float*)target_boxes, (const int32_t*)offsets, layers, clips, frames, queries,
-                                     classes, targets_total, targets_max, cost_class, cost_bbox, cost_giou,
-                                     (int64_t*)query_index, (int64_t*)target_index, (float*)cost_out,
-                                     (hipStream_t)hip_stream);
-}
-
-int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long batch_stride, long long row_stride,
-                   long long col_stride, int maximize, void* row_index, void* col_index, void* hip_stream) {
-  const char* fn = "vnx_lsap_solve";
-  if (batch < 0 || rows < 0 || cols < 0) {
-    vnx::set_error("%s: bad sizes (batch %d, %d x %d)", fn, batch, rows, cols);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (batch == 0 || rows == 0 || cols == 0) return VNX_OK;
-  if (!vnx::lsap_fits(rows < cols ? rows : cols, rows < cols ? cols : rows)) {
-    vnx::set_error("%s: a %d x %d problem does not fit the LDS of a CU", fn, rows, cols);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  if (!cost || !row_index || !col_index) {
-    vnx::set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  return vnx::lsap_solve_launch((const float*)cost, batch, rows, cols, int64_t(batch_stride), int64_t(row_stride),
-                                int64_t(col_stride), maximize != 0, (int64_t*)row_index, (int64_t*)col_index,
-                                (hipStream_t)hip_stream);
-}
-
-// ---- mask losses, focal + dice (mask_loss.hip: the argument checks live beside the kernels' addressing limits) --------------
-int vnx_mask_loss_forward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
-                          int height, int width, int stride, float alpha, float gamma, void* partial,
-                          size_t partial_bytes, void* focal, void* dice, void* row_sums, void* hip_stream) {
-  return vnx::mask_loss_forward((const float*)logits, clips, (const int64_t*)row_gt, rows, frames, height, width, stride,
-                                alpha, gamma, (float*)partial, partial_bytes, (float*)focal, (float*)dice,
-                                (float*)row_sums, (hipStream_t)hip_stream);
-}
-
-int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows, int frames,
-                           int height, int width, int stride, float alpha, float gamma, const void* row_sums,
-                           const void* grad_focal, const void* grad_dice, void* grad_logits, void* hip_stream) {
-  return vnx::mask_loss_backward((const float*)logits, clips, (const int64_t*)row_gt, rows, frames, height, width, stride,
-                                 alpha, gamma, (const float*)row_sums, (const float*)grad_focal, (const float*)grad_dice,
-                                 (float*)grad_logits, (hipStream_t)hip_stream);
-}
-
-// ---- class and box losses of every decoder layer (set_loss.hip: the argument checks live beside the kernels' addressing limits) ----
-int vnx_set_loss_forward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
-                         const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
-                         int queries, int classes, int pairs, int targets_total, float alpha, void* partial,
-                         size_t partial_bytes, void* out, void* hip_stream) {
-  return vnx::set_loss_forward((const float*)logits, (const float*)boxes, (const int64_t*)lay, (const int64_t*)clip,
-                               (const int64_t*)qry, (const int64_t*)tgt, (const int64_t*)labels, (const float*)target_boxes,
-                               layers, clips, frames, queries, classes, pairs, targets_total, alpha, (float*)partial,
-                               partial_bytes, (float*)out, (hipStream_t)hip_stream);
-}
-
-int vnx_set_loss_backward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
-                          const void* tgt, const void* labels, const void* target_boxes, int layers, int clips, int frames,
-                          int queries, int classes, int pairs, int targets_total, float alpha, const void* grad_out,
-                          void* grad_logits, void* grad_boxes, void* hip_stream) {
-  return vnx::set_loss_backward((const float*)logits, (const float*)boxes, (const int64_t*)lay, (const int64_t*)clip,
-                                (const int64_t*)qry, (const int64_t*)tgt, (const int64_t*)labels,
-                                (const float*)target_boxes, layers, clips, frames, queries, classes, pairs, targets_total,
-                                alpha, (const float*)grad_out, (float*)grad_logits, (float*)grad_boxes,
-                                (hipStream_t)hip_stream);
-}
-
-// ---- IDOL's simOTA matching and contrastive sets (ota_match.hip: the argument checks live beside the kernel's LDS layout) ----
-int vnx_idol_match_max_targets(int queries) { return queries < 1 ? 0 : vnx::idol_match_cap(queries); }
-
-int vnx_idol_match_out_words(int targets_max, int queries) {
-  return targets_max < 0 || queries < 1 ? 0 : vnx::idol_match_out_words(targets_max, queries);
-}
-
-int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_prob, const void* ref_boxes,
-                   const void* target_boxes, const void* labels, const void* valid, const void* problems,
-                   int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
-                   int targets_max, void* out, int out_stride, void* hip_stream) {
-  return vnx::idol_match((const float*)det_prob, (const float*)det_boxes, (const float*)ref_prob, (const float*)ref_boxes,
-                         (const float*)target_boxes, (const int64_t*)labels, (const uint8_t*)valid,
-                         (const int32_t*)problems, det_problems, ref_problems, queries, classes, targets_total,
-                         valid_first, targets_max, (int32_t*)out, out_stride, (hipStream_t)hip_stream);
-}
-
-// ---- detection selection: best class, score threshold, class-aware NMS, top-k (det_select.hip: the argument checks live beside the kernel's LDS layout) ----
-int vnx_det_select_out_words(int queries, int topk) {
-  return queries < 1 || topk < 0 ? 0 : vnx::det_select_out_words(queries, topk);
-}
-
-int vnx_det_select(const void* logits, const void* boxes, int batch, int queries, int classes, float score_thr,
-                   float iou_thr, int topk, void* out, int out_stride, void* hip_stream) {
-  return vnx::det_select((const float*)logits, (const float*)boxes, batch, queries, classes, score_thr, iou_thr, topk,
-                         (int32_t*)out, out_stride, (hipStream_t)hip_stream);
-}
-
-// ---- IDOL's reid losses, contrastive + cosine (reid_loss.hip: the argument checks live beside the kernels' addressing limits) ----
-int vnx_reid_loss_forward(const void* key, long long key_image_stride, int key_rows, const void* ref,
-                          long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
-                          const void* key_query, const void* flags, int instances, void* out, void* dot, void* ref_norm,
-                          void* stats, void* hip_stream) {
-  return vnx::reid_loss_forward((const float*)key, int64_t(key_image_stride), key_rows, (const float*)ref,
-                                int64_t(ref_image_stride), ref_rows, channels, images, (const int32_t*)img,
-                                (const int32_t*)key_query, (const uint8_t*)flags, instances, (float*)out, (float*)dot,
-                                (float*)ref_norm, (float*)stats, (hipStream_t)hip_stream);
-}
-
-int vnx_reid_loss_backward(const void* key, long long key_image_stride, int key_rows, const void* ref,
-                           long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
-                           const void* key_query, const void* flags, int instances, const void* dot, const void* ref_norm,
-                           const void* stats, const void* grad_out, void* grad_key, void* grad_ref, void* hip_stream) {
-  return vnx::reid_loss_backward((const float*)key, int64_t(key_image_stride), key_rows, (const float*)ref,
-                                 int64_t(ref_image_stride), ref_rows, channels, images, (const int32_t*)img,
-                                 (const int32_t*)key_query, (const uint8_t*)flags, instances, (const float*)dot,
-                                 (const float*)ref_norm, (const float*)stats, (const float*)grad_out, (float*)grad_key,
-                                 (float*)grad_ref, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

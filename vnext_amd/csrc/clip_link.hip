@@ -104,11 +104,6 @@ template <bool VEC> __device__ __forceinline__ void cl_store4(float* row, int px
   }
 }
 
-__device__ __forceinline__ float cl_wave_sum(float v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // ---- launch 1: products and row sums of one (stored clip, shared frame pair, pixel chunk) ---------------------------------
 template <bool VEC>
 __global__ __launch_bounds__(kClThreads) void clip_link_siou_kernel(
@@ -178,13 +173,13 @@ __global__ __launch_bounds__(kClThreads) void clip_link_siou_kernel(
   for (int r = 0; r < 4; ++r) {
 #pragma unroll
     for (int j = 0; j < kClInst; j += 4) {
-      const vnx_f4 v = {cl_wave_sum(acc[r][j]), cl_wave_sum(acc[r][j + 1]), cl_wave_sum(acc[r][j + 2]),
-                        cl_wave_sum(acc[r][j + 3])};
+      const vnx_f4 v = {wave_sum(acc[r][j]), wave_sum(acc[r][j + 1]), wave_sum(acc[r][j + 2]),
+                        wave_sum(acc[r][j + 3])};
       if (lane == 0) *reinterpret_cast<vnx_f4*>(out + (4 * wave + r) * kClInst + j) = v;
     }
   }
-  const vnx_f4 sa = {cl_wave_sum(asum[0]), cl_wave_sum(asum[1]), cl_wave_sum(asum[2]), cl_wave_sum(asum[3])};
-  const vnx_f4 sbm = {cl_wave_sum(bsum[0]), cl_wave_sum(bsum[1]), cl_wave_sum(bsum[2]), cl_wave_sum(bsum[3])};
+  const vnx_f4 sa = {wave_sum(asum[0]), wave_sum(asum[1]), wave_sum(asum[2]), wave_sum(asum[3])};
+  const vnx_f4 sbm = {wave_sum(bsum[0]), wave_sum(bsum[1]), wave_sum(bsum[2]), wave_sum(bsum[3])};
   if (lane == 0) {
     *reinterpret_cast<vnx_f4*>(out + kClInst * kClInst + 4 * wave) = sa;
     *reinterpret_cast<vnx_f4*>(out + kClInst * kClInst + kClInst + 4 * wave) = sbm;

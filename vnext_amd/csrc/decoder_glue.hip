@@ -68,12 +68,6 @@ refine_boxes_bwd_kernel(const float* __restrict__ grad_out, const float* __restr
 // ---- 2. temporal weighting: one wave per (clip, query), lane = channels 4 lane .. 4 lane + 3 of each 256-channel slab --------
 constexpr int kTwMaxFrames = 16;
 
-__device__ __forceinline__ float dg_wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // (the frame loops run to the compile-time maximum under a `t < T` guard: fully unrolled, so the per-frame values stay in
 //  registers instead of an indexed scratch array)
 #define VNX_TW_FRAMES(t) _Pragma("unroll") for (int t = 0; t < kTwMaxFrames; ++t) if (t < T)
@@ -122,7 +116,7 @@ time_weighted_sum_bwd_kernel(const float* __restrict__ grad_out, const float* __
     }
   }
   float dot = 0.f;
-  VNX_TW_FRAMES(t) { dw[t] = dg_wave_sum(dw[t]); dot += wt[t] * dw[t]; }
+  VNX_TW_FRAMES(t) { dw[t] = wave_sum(dw[t]); dot += wt[t] * dw[t]; }
   if (lane == 0) {
     VNX_TW_FRAMES(t) grad_z[(int64_t(n) * T + t) * Q + q] = wt[t] * (dw[t] - dot);
   }

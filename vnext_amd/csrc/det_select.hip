@@ -58,7 +58,6 @@ constexpr size_t kDetLdsBytes = 160 * 1024;       // LDS of a gfx950 CU
 typedef unsigned long long u64;
 typedef int det_i4 __attribute__((ext_vector_type(4)));
 
-__host__ __device__ inline int det_qpad(int Q) { return (Q + 3) & ~3; }
 __host__ __device__ inline int det_words(int n) { return (n + 63) >> 6; }
 // rows of block b (64 rows) hold the words b .. W-1: the first word of row i
 __host__ __device__ inline int det_row_offset(int i, int W) {
@@ -66,7 +65,7 @@ __host__ __device__ inline int det_row_offset(int i, int W) {
   return 64 * (b * W - b * (b - 1) / 2) + (i & 63) * (W - b);
 }
 __host__ __device__ inline size_t det_lds_bytes(int Q) {
-  const size_t Qp = det_qpad(Q), W = det_words(Q);
+  const size_t Qp = pad4(Q), W = det_words(Q);
   return 8 * (64 * W * (W + 1) / 2) + 8 * ((W + 1) & ~size_t(1)) + 16 * Qp + 6 * 4 * Qp + 8 * kDetTopMax + 4 * 256 + 64;
 }
 __host__ __device__ inline int det_out_words(int Q, int topk) { return 4 + 2 * Q + 2 * topk; }
@@ -95,7 +94,7 @@ struct DetLds {
 };
 
 __device__ __forceinline__ DetLds det_carve(unsigned char* smem, int Q) {
-  const size_t Qp = det_qpad(Q), W = det_words(Q);
+  const size_t Qp = pad4(Q), W = det_words(Q);
   DetLds s;
   s.mat = reinterpret_cast<u64*>(smem);
   s.rem = s.mat + 64 * W * (W + 1) / 2;
@@ -110,12 +109,6 @@ __device__ __forceinline__ DetLds det_carve(unsigned char* smem, int Q) {
   s.hist = reinterpret_cast<int*>(s.sel + kDetTopMax);
   s.misc = s.hist + 256;
   return s;
-}
-
-// a float as an integer with the same order (-0 = +0); INT_MIN only for a NaN payload, which never gets here
-__device__ __forceinline__ int det_order_key(float x) {
-  const int b = __float_as_int(x + 0.f);
-  return b ^ ((b >> 31) & 0x7fffffff);
 }
 
 __device__ __forceinline__ int det_wave_sum(int v) {
@@ -153,14 +146,14 @@ __device__ __forceinline__ u64 det_wave_or(u64 v) {
 __device__ __forceinline__ u64 det_topk_key(const DetLds& s, const float* __restrict__ logits, int K, int i) {
   const int p = int(unsigned(i) / unsigned(K)), c = i - p * K;
   const float v = logits[size_t(s.kq[p]) * K + c];
-  const unsigned uk = unsigned(det_order_key(v)) ^ 0x80000000u;
+  const unsigned uk = unsigned(order_key(v)) ^ 0x80000000u;
   return (u64(uk) << kDetFlatBits) | u64(((1u << kDetFlatBits) - 1u) - unsigned(i));
 }
 
 __global__ __launch_bounds__(kDetThreads) void det_select_kernel(DetArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int Q = a.Q, K = a.K, Qp = det_qpad(Q);
+  const int Q = a.Q, K = a.K, Qp = pad4(Q);
   const DetLds s = det_carve(smem, Q);
   const float* logits = a.logits + size_t(blockIdx.x) * Q * K;
   const float* boxes = a.boxes + size_t(blockIdx.x) * Q * 4;
@@ -191,7 +184,7 @@ __global__ __launch_bounds__(kDetThreads) void det_select_kernel(DetArgs a) {
     }
     if (q < Q && g == 0) {
       const bool cand = 1.f / (1.f + expf(-best)) > a.score_thr;
-      s.key[q] = det_order_key(best);
+      s.key[q] = order_key(best);
       s.label[q] = bc;
       s.kq[q] = cand;
       mine += cand;
@@ -372,10 +365,16 @@ __global__ __launch_bounds__(kDetThreads) void det_select_kernel(DetArgs a) {
 
 }  // namespace
 
-int det_select_out_words(int queries, int topk) { return det_out_words(queries, topk); }
+}  // namespace vnx
 
-int det_select(const float* logits, const float* boxes, int batch, int queries, int classes, float score_thr, float iou_thr,
-               int topk, int32_t* out, int out_stride, hipStream_t stream) {
+using namespace vnx;
+
+extern "C" int vnx_det_select_out_words(int queries, int topk) {      // int32 words of one image's output
+  return queries < 1 || topk < 0 ? 0 : det_out_words(queries, topk);
+}
+
+extern "C" int vnx_det_select(const void* logits, const void* boxes, int batch, int queries, int classes, float score_thr,
+                              float iou_thr, int topk, void* out, int out_stride, void* hip_stream) {
   const char* fn = "vnx_det_select";
   if (batch < 0 || queries < 1 || classes < 1 || topk < 0) {
     set_error("%s: bad sizes (batch %d, queries %d, classes %d, topk %d)", fn, batch, queries, classes, topk);
@@ -425,9 +424,8 @@ int det_select(const float* logits, const float* boxes, int batch, int queries, 
       if (device >= 0 && device < kDevices) asked[device].store(true, std::memory_order_release);
     }
   }
-  const DetArgs a{logits, boxes, out, queries, classes, topk, out_stride, score_thr, iou_thr};
-  hipLaunchKernelGGL(det_select_kernel, dim3(unsigned(batch)), dim3(kDetThreads), lds, stream, a);
+  const DetArgs a{(const float*)logits, (const float*)boxes, (int32_t*)out, queries, classes, topk, out_stride, score_thr,
+                  iou_thr};
+  hipLaunchKernelGGL(det_select_kernel, dim3(unsigned(batch)), dim3(kDetThreads), lds, (hipStream_t)hip_stream, a);
   return check_launch(fn);
 }
-
-}  // namespace vnx

@@ -26,22 +26,6 @@ typedef float ffn_f4 __attribute__((ext_vector_type(4)));
 constexpr int kFaMaxBlocks = 2048;     // workgroups of the backward = partial rows of the bias gradient (8 waves per SIMD at 1 024 columns)
 constexpr int kFaMaxCols = 4096;       // columns (d_ffn) at most: one float4 per thread, 1 024 threads
 
-__device__ __forceinline__ uint32_t fa_hash(uint32_t idx, uint32_t seed_lo, uint32_t seed_hi) {      // = an_hash (add_norm.hip)
-  uint32_t h = idx ^ seed_lo;
-  h *= 0xcc9e2d51u; h = (h << 15) | (h >> 17); h *= 0x1b873593u;
-  h ^= seed_hi;
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ void fa_effective_seed(uint32_t& lo, uint32_t& hi, const unsigned long long* seed_device) {
-  if (seed_device == nullptr) return;                                  // = an_effective_seed (add_norm.hip)
-  const unsigned long long s = *seed_device;
-  uint32_t a = uint32_t(s) * 0x9E3779B1u, b = (uint32_t(s >> 32) + 0x7F4A7C15u) * 0x85EBCA77u;
-  a ^= a >> 15; b ^= b >> 13;
-  lo ^= a * 0xC2B2AE3Du;
-  hi ^= b * 0x27D4EB2Fu + a;
-}
-
 // in place over h [rows, cols]; thread = 4 consecutive columns (blockIdx.x * 256 + threadIdx.x), rows blockIdx.y,
 // blockIdx.y + gridDim.y, ...: no division anywhere, the bias quad is loaded once per thread
 template <typename T>
@@ -51,7 +35,7 @@ bias_relu_dropout_fwd_kernel(T* __restrict__ h, const float* __restrict__ bias, 
                              uint32_t seed_hi, const unsigned long long* __restrict__ seed_device) {
   const int c4 = int(blockIdx.x) * 256 + int(threadIdx.x);
   if (c4 >= cols4) return;
-  if (threshold != 0u) fa_effective_seed(seed_lo, seed_hi, seed_device);
+  if (threshold != 0u) dropout_effective_seed(seed_lo, seed_hi, seed_device);
   const ffn_f4 b = bias != nullptr ? *reinterpret_cast<const ffn_f4*>(bias + c4 * 4) : ffn_f4{0.f, 0.f, 0.f, 0.f};
   for (int64_t row = blockIdx.y; row < rows; row += gridDim.y) {
     const int64_t i = row * cols4 + c4;                                // float4 index
@@ -65,10 +49,10 @@ bias_relu_dropout_fwd_kernel(T* __restrict__ h, const float* __restrict__ bias, 
     if (threshold != 0u) {
       const uint32_t base = uint32_t(i) * 4u;                          // element index mod 2^32 ...
       const uint32_t hi = seed_hi ^ uint32_t(uint64_t(i) >> 30);       // ... and what lies above it
-      v.x = fa_hash(base + 0u, seed_lo, hi) >= threshold ? v.x * scale : 0.f;
-      v.y = fa_hash(base + 1u, seed_lo, hi) >= threshold ? v.y * scale : 0.f;
-      v.z = fa_hash(base + 2u, seed_lo, hi) >= threshold ? v.z * scale : 0.f;
-      v.w = fa_hash(base + 3u, seed_lo, hi) >= threshold ? v.w * scale : 0.f;
+      v.x = dropout_hash(base + 0u, seed_lo, hi) >= threshold ? v.x * scale : 0.f;
+      v.y = dropout_hash(base + 1u, seed_lo, hi) >= threshold ? v.y * scale : 0.f;
+      v.z = dropout_hash(base + 2u, seed_lo, hi) >= threshold ? v.z * scale : 0.f;
+      v.w = dropout_hash(base + 3u, seed_lo, hi) >= threshold ? v.w * scale : 0.f;
     }
     row4_store<T>(h + i * 4, v);
   }
@@ -138,11 +122,6 @@ static int fa_check(const char* who, int dtype, int64_t rows, int cols, float p)
   return VNX_OK;
 }
 
-static uint32_t fa_threshold(float p) {      // keep iff hash >= threshold:  P(drop) = threshold / 2^32
-  const double t = double(p) * 4294967296.0;
-  return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 0xffffffffu : uint32_t(t + 0.5));
-}
-
 }  // namespace vnx
 
 using namespace vnx;
@@ -168,7 +147,7 @@ extern "C" int vnx_bias_relu_dropout_forward(int dtype, void* h, const void* bia
   const dim3 grid(uint32_t((cols4 + 255) / 256), uint32_t(std::min<int64_t>(rows, 16384)));
 #define VNX_FA_FWD(T)                                                                                                  \
   hipLaunchKernelGGL(bias_relu_dropout_fwd_kernel<T>, grid, dim3(256), 0, (hipStream_t)hip_stream, (T*)h,              \
-                     (const float*)bias, (const uint8_t*)row_zero, int64_t(rows), channels / 4, relu, fa_threshold(p), \
+                     (const float*)bias, (const uint8_t*)row_zero, int64_t(rows), channels / 4, relu, dropout_threshold(p), \
                      1.f / (1.f - p), uint32_t(seed), uint32_t(seed >> 32), seed_device)
   if (dtype == VNX_BF16) VNX_FA_FWD(bf16_t); else if (dtype == VNX_F16) VNX_FA_FWD(f16_t); else VNX_FA_FWD(float);
 #undef VNX_FA_FWD

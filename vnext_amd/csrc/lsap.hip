@@ -17,7 +17,7 @@
 // Q = 300: 8.4 KB + n x 1212 B, n <= 128 in the 160 KB of a gfx950 CU.
 //
 // vnx_seqformer_match computes its cost block in the kernel (HungarianMatcher.cost, reference matcher.py:53-96);
-// vnx_lsap_solve takes cost matrices from device memory through strides.  C entry points and argument checks: capi.hip.
+// vnx_lsap_solve takes cost matrices from device memory through strides.
 // The solver of one wave itself (LsapLds, carve, wave_sync, lsap_lds_bytes, lsap_solve_wave) lives in lsap_wave.h, which
 // clip_link.hip includes too.
 #include "lsap_wave.h"
@@ -158,33 +158,75 @@ template <typename Kernel> int allow_full_lds(Kernel kernel, std::atomic<bool>& 
   return VNX_OK;
 }
 
-}  // namespace
-
+// the problem's state fits the LDS of a CU
 bool lsap_fits(int n_short, int n_long) { return lsap_lds_bytes(n_short, n_long) <= kLdsBytes; }
 
-int seqformer_match_launch(const float* logits, const float* boxes, const int64_t* labels, const float* tgt_boxes,
-                           const int32_t* offsets, int layers, int clips, int frames, int queries, int classes,
-                           int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
-                           int64_t* query_index, int64_t* target_index, float* cost_out, hipStream_t stream) {
+}  // namespace
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" int vnx_seqformer_match(const void* logits, const void* boxes, const void* labels, const void* target_boxes,
+                                   const void* offsets, int layers, int clips, int frames, int queries, int classes,
+                                   int targets_total, int targets_max, float cost_class, float cost_bbox, float cost_giou,
+                                   void* query_index, void* target_index, void* cost_out, void* hip_stream) {
+  const char* fn = "vnx_seqformer_match";
+  if (layers < 0 || clips < 0 || frames < 1 || queries < 1 || classes < 1 || targets_total < 0 || targets_max < 0 ||
+      targets_max > targets_total) {
+    set_error("%s: bad sizes (layers %d, clips %d, frames %d, queries %d, classes %d, targets %d, largest clip %d)", fn,
+              layers, clips, frames, queries, classes, targets_total, targets_max);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (layers == 0 || clips == 0 || targets_total == 0) return VNX_OK;
+  if (targets_max > queries || !lsap_fits(targets_max, queries)) {
+    set_error("%s: %d targets of one clip against %d queries: more targets than queries, or more than the LDS of a "
+              "CU holds", fn, targets_max, queries);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (int64_t(layers) * clips >= (int64_t(1) << 31) ||
+      int64_t(layers) * clips * queries * (int64_t(classes) > int64_t(frames) * 4 ? classes : frames * 4) >= (int64_t(1) << 40)) {
+    set_error("%s: %d x %d problems are outside what the kernel addresses", fn, layers, clips);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (!logits || !boxes || !labels || !target_boxes || !offsets || !query_index || !target_index) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  hipStream_t stream = (hipStream_t)hip_stream;
   static std::atomic<bool> asked{false};
   const size_t lds = lsap_lds_bytes(targets_max, queries);
   if (lds > 64 * 1024)
     if (int st = allow_full_lds(seqformer_match_kernel, asked)) return st;
-  hipLaunchKernelGGL(seqformer_match_kernel, dim3(layers * clips), dim3(kWave), lds, stream, logits, boxes, labels,
-                     tgt_boxes, offsets, clips, frames, queries, classes, targets_total, targets_max, cost_class, cost_bbox,
-                     cost_giou, query_index, target_index, cost_out);
-  return check_launch("vnx_seqformer_match");
+  hipLaunchKernelGGL(seqformer_match_kernel, dim3(layers * clips), dim3(kWave), lds, stream, (const float*)logits,
+                     (const float*)boxes, (const int64_t*)labels, (const float*)target_boxes, (const int32_t*)offsets, clips,
+                     frames, queries, classes, targets_total, targets_max, cost_class, cost_bbox, cost_giou,
+                     (int64_t*)query_index, (int64_t*)target_index, (float*)cost_out);
+  return check_launch(fn);
 }
 
-int lsap_solve_launch(const float* cost, int batch, int rows, int cols, int64_t batch_stride, int64_t row_stride,
-                      int64_t col_stride, int maximize, int64_t* row_index, int64_t* col_index, hipStream_t stream) {
+extern "C" int vnx_lsap_solve(const void* cost, int batch, int rows, int cols, long long batch_stride, long long row_stride,
+                              long long col_stride, int maximize, void* row_index, void* col_index, void* hip_stream) {
+  const char* fn = "vnx_lsap_solve";
+  if (batch < 0 || rows < 0 || cols < 0) {
+    set_error("%s: bad sizes (batch %d, %d x %d)", fn, batch, rows, cols);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (batch == 0 || rows == 0 || cols == 0) return VNX_OK;
+  if (!lsap_fits(rows < cols ? rows : cols, rows < cols ? cols : rows)) {
+    set_error("%s: a %d x %d problem does not fit the LDS of a CU", fn, rows, cols);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (!cost || !row_index || !col_index) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  hipStream_t stream = (hipStream_t)hip_stream;
   static std::atomic<bool> asked{false};
   const size_t lds = lsap_lds_bytes(rows < cols ? rows : cols, rows < cols ? cols : rows);
   if (lds > 64 * 1024)
     if (int st = allow_full_lds(lsap_solve_kernel, asked)) return st;
-  hipLaunchKernelGGL(lsap_solve_kernel, dim3(batch), dim3(kWave), lds, stream, cost, rows, cols, batch_stride, row_stride,
-                     col_stride, maximize, row_index, col_index);
-  return check_launch("vnx_lsap_solve");
+  hipLaunchKernelGGL(lsap_solve_kernel, dim3(batch), dim3(kWave), lds, stream, (const float*)cost, rows, cols,
+                     int64_t(batch_stride), int64_t(row_stride), int64_t(col_stride), int(maximize != 0), (int64_t*)row_index,
+                     (int64_t*)col_index);
+  return check_launch(fn);
 }
-
-}  // namespace vnx

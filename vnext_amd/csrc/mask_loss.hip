@@ -34,7 +34,7 @@
 // and the ground truth -- the forward saves nothing of [R, M] size -- and stores grad_logits 16 bytes per lane.
 //
 // A row whose row_gt is outside [0, total) has no ground truth: its target is 0 everywhere (the kernels never read
-// outside a clip's tensor).  C entry points: capi.hip.
+// outside a clip's tensor).
 #include "vnx_common.h"
 
 namespace vnx {
@@ -129,12 +129,6 @@ __device__ __forceinline__ void ml_accumulate(MlSums& a, float x, bool t, float 
   a.t += t ? 1.f : 0.f;
 }
 
-__device__ __forceinline__ float ml_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 }  // namespace
 
 // grid: R * pieces workgroups; partial [R][pieces][4] = {sum focal, sum p t, sum p, sum t} of the piece
@@ -172,10 +166,10 @@ __global__ void __launch_bounds__(kMlThreads) mask_loss_fwd_kernel(const float* 
       }
     }
   }
-  a.focal = ml_wave_sum(a.focal);
-  a.pt = ml_wave_sum(a.pt);
-  a.p = ml_wave_sum(a.p);
-  a.t = ml_wave_sum(a.t);
+  a.focal = wave_sum(a.focal);
+  a.pt = wave_sum(a.pt);
+  a.p = wave_sum(a.p);
+  a.t = wave_sum(a.t);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
     s_part[wave][0] = a.focal; s_part[wave][1] = a.pt; s_part[wave][2] = a.p; s_part[wave][3] = a.t;
@@ -200,10 +194,10 @@ __global__ void __launch_bounds__(64) mask_loss_finish_kernel(const float* __res
   const vnx_f4* p = reinterpret_cast<const vnx_f4*>(partial) + int64_t(r) * pieces;
   vnx_f4 a = {0.f, 0.f, 0.f, 0.f};
   for (int k = lane; k < pieces; k += 64) a += p[k];
-  a.x = ml_wave_sum(a.x);
-  a.y = ml_wave_sum(a.y);
-  a.z = ml_wave_sum(a.z);
-  a.w = ml_wave_sum(a.w);
+  a.x = wave_sum(a.x);
+  a.y = wave_sum(a.y);
+  a.z = wave_sum(a.z);
+  a.w = wave_sum(a.w);
   if (lane == 0) {
     focal[r] = a.x / float(M);
     dice[r] = 1.f - (2.f * a.y + 1.f) / (a.z + a.w + 1.f);
@@ -305,9 +299,13 @@ static int ml_dims(const char* fn, const void* logits, const vnx_mask_loss_clips
   return VNX_OK;
 }
 
-int mask_loss_forward(const float* logits, const vnx_mask_loss_clips* clips, const int64_t* row_gt, int rows, int frames,
-                      int height, int width, int stride, float alpha, float gamma, float* partial, size_t partial_bytes,
-                      float* focal, float* dice, float* row_sums, hipStream_t stream) {
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" int vnx_mask_loss_forward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows,
+                                     int frames, int height, int width, int stride, float alpha, float gamma, void* partial,
+                                     size_t partial_bytes, void* focal, void* dice, void* row_sums, void* hip_stream) {
   const char* fn = "vnx_mask_loss_forward";
   MlDims d;
   if (int st = ml_dims(fn, logits, clips, rows, frames, height, width, stride, alpha, gamma, &d)) return st;
@@ -321,17 +319,19 @@ int mask_loss_forward(const float* logits, const vnx_mask_loss_clips* clips, con
     set_error("%s: partial buffer of %zu bytes, %zu needed (16-byte aligned)", fn, partial_bytes, need);
     return VNX_ERR_WORKSPACE;
   }
-  hipLaunchKernelGGL(mask_loss_fwd_kernel, dim3(uint32_t(rows) * uint32_t(d.pieces)), dim3(kMlThreads), 0, stream, logits,
-                     *clips, row_gt, d, partial);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(mask_loss_fwd_kernel, dim3(uint32_t(rows) * uint32_t(d.pieces)), dim3(kMlThreads), 0, stream,
+                     (const float*)logits, *clips, (const int64_t*)row_gt, d, (float*)partial);
   if (int st = check_launch("mask_loss_fwd")) return st;
   hipLaunchKernelGGL(mask_loss_finish_kernel, dim3(uint32_t(rows)), dim3(64), 0, stream, (const float*)partial, d.pieces,
-                     d.M, focal, dice, row_sums);
+                     d.M, (float*)focal, (float*)dice, (float*)row_sums);
   return check_launch("mask_loss_finish");
 }
 
-int mask_loss_backward(const float* logits, const vnx_mask_loss_clips* clips, const int64_t* row_gt, int rows, int frames,
-                       int height, int width, int stride, float alpha, float gamma, const float* row_sums,
-                       const float* grad_focal, const float* grad_dice, float* grad_logits, hipStream_t stream) {
+extern "C" int vnx_mask_loss_backward(const void* logits, const vnx_mask_loss_clips* clips, const void* row_gt, int rows,
+                                      int frames, int height, int width, int stride, float alpha, float gamma,
+                                      const void* row_sums, const void* grad_focal, const void* grad_dice,
+                                      void* grad_logits, void* hip_stream) {
   const char* fn = "vnx_mask_loss_backward";
   MlDims d;
   if (int st = ml_dims(fn, logits, clips, rows, frames, height, width, stride, alpha, gamma, &d)) return st;
@@ -341,9 +341,8 @@ int mask_loss_backward(const float* logits, const vnx_mask_loss_clips* clips, co
     return VNX_ERR_INVALID_ARGUMENT;
   }
   d.vec = d.vec && (reinterpret_cast<uintptr_t>(grad_logits) & 15) == 0;
-  hipLaunchKernelGGL(mask_loss_bwd_kernel, dim3(uint32_t(rows) * uint32_t(d.pieces)), dim3(kMlThreads), 0, stream, logits,
-                     *clips, row_gt, d, row_sums, grad_focal, grad_dice, grad_logits);
+  hipLaunchKernelGGL(mask_loss_bwd_kernel, dim3(uint32_t(rows) * uint32_t(d.pieces)), dim3(kMlThreads), 0,
+                     (hipStream_t)hip_stream, (const float*)logits, *clips, (const int64_t*)row_gt, d, (const float*)row_sums,
+                     (const float*)grad_focal, (const float*)grad_dice, (float*)grad_logits);
   return check_launch("mask_loss_bwd");
 }
-
-}  // namespace vnx

@@ -178,9 +178,9 @@ __global__ void __launch_bounds__(kRleThreads) mask_rle_kernel(RleArgs a, int64_
   }
 }
 
-int mask_rle_launch(bool write, int mode, const void* input, int masks, int height, int width, int stride,
-                    int image_height, int image_width, int out_height, int out_width, int64_t* lengths,
-                    const int64_t* offsets, void* arena, int64_t arena_bytes, hipStream_t stream) {
+static int mask_rle_launch(bool write, int mode, const void* input, int masks, int height, int width, int stride,
+                           int image_height, int image_width, int out_height, int out_width, int64_t* lengths,
+                           const int64_t* offsets, void* arena, int64_t arena_bytes, hipStream_t stream) {
   RleArgs a;
   a.in = input;
   a.h = height; a.w = width;
@@ -210,3 +210,78 @@ int mask_rle_launch(bool write, int mode, const void* input, int masks, int heig
 }
 
 }  // namespace vnx
+
+using namespace vnx;
+
+static int mask_rle_check(const char* fn, int mode, const void* input, int masks, int height, int width, int stride,
+                          int image_height, int image_width, int out_height, int out_width) {
+  if (mode != VNX_MASK_RLE_LOGITS && mode != VNX_MASK_RLE_BINARY) {
+    set_error("%s: unknown mode %d", fn, mode);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (masks < 0 || out_height < 1 || out_width < 1) {
+    set_error("%s: bad sizes (masks %d, out %d x %d)", fn, masks, out_height, out_width);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (int64_t(out_height) * out_width >= (int64_t(1) << 31)) {
+    set_error("%s: out %d x %d has 2^31 pixels or more (int32 counts)", fn, out_height, out_width);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  if (mode == VNX_MASK_RLE_LOGITS) {
+    if (height < 1 || width < 1 || stride < 1 || image_height < 1 || image_width < 1 ||
+        int64_t(image_height) > int64_t(height) * stride || int64_t(image_width) > int64_t(width) * stride) {
+      set_error("%s: bad sizes (map %d x %d, stride %d, image %d x %d)", fn, height, width, stride, image_height,
+                image_width);
+      return VNX_ERR_INVALID_ARGUMENT;
+    }
+    if (int64_t(height) * width >= (int64_t(1) << 31)) {
+      set_error("%s: map %d x %d has 2^31 elements or more", fn, height, width);
+      return VNX_ERR_UNSUPPORTED;
+    }
+    if (masks > 0 && (reinterpret_cast<uintptr_t>(input) & 3) != 0) {
+      set_error("%s: logits must be 4-byte aligned", fn);
+      return VNX_ERR_INVALID_ARGUMENT;
+    }
+  }
+  if (masks > 0 && !input) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return VNX_OK;
+}
+
+extern "C" int vnx_mask_rle_measure(int mode, const void* input, int masks, int height, int width, int stride,
+                                    int image_height, int image_width, int out_height, int out_width, void* lengths,
+                                    void* hip_stream) {
+  const char* fn = "vnx_mask_rle_measure";
+  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width))
+    return st;
+  if (masks == 0) return VNX_OK;
+  if (!lengths) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return mask_rle_launch(false, mode, input, masks, height, width, stride, image_height, image_width, out_height, out_width,
+                         (int64_t*)lengths, nullptr, nullptr, 0, (hipStream_t)hip_stream);
+}
+
+extern "C" int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int width, int stride,
+                                  int image_height, int image_width, int out_height, int out_width, const void* offsets,
+                                  void* arena, long long arena_bytes, void* hip_stream) {
+  const char* fn = "vnx_mask_rle_write";
+  if (int st = mask_rle_check(fn, mode, input, masks, height, width, stride, image_height, image_width, out_height,
+                              out_width))
+    return st;
+  if (arena_bytes < 0) {
+    set_error("%s: arena_bytes %lld < 0", fn, arena_bytes);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (masks == 0) return VNX_OK;
+  if (!offsets || !arena) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  return mask_rle_launch(true, mode, input, masks, height, width, stride, image_height, image_width, out_height, out_width,
+                         nullptr, (const int64_t*)offsets, arena, int64_t(arena_bytes), (hipStream_t)hip_stream);
+}

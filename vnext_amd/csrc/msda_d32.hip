@@ -144,7 +144,7 @@ __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {     // 
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ushort2_t, a), __builtin_bit_cast(ushort2_t, b)));
 }
 // rows per unit of the grad_value kernels for a level of n pixels = gv_level_split(n, units_min, rows_max).rpu
-// (vnx_common.h), here without the integer-division sequence (one lane per sample evaluates it)
+// (msda_units.h), here without the integer-division sequence (one lane per sample evaluates it)
 __device__ __forceinline__ int gv_rows_per_unit(int n, int units_min, int rows_max) {
   int units = (n + rows_max - 1) / rows_max;
   if (units < units_min) units = units_min;

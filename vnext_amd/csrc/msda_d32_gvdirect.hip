@@ -7,7 +7,7 @@
 // the tags (load, ballots, scan, compaction: 8.1 of its 15 us at the T = 5 decoder call) and on a
 // chunk loop (three chunks of 128 distinct queries for the units of a coarse level: the critical path).
 //
-// Here a unit (a pixel range of one level for one (batch, head); gvd_level_split in vnx_common.h) reads, in ONE pass,
+// Here a unit (a pixel range of one level for one (batch, head); gvd_level_split in msda_units.h) reads, in ONE pass,
 //   * the locations and weights of its level's samples of every query -- 32 + 16 bytes per (query, head, level): 14 KB for
 //     the 300 queries of a decoder call -- straight from `sampling_loc` / `attn_weight`, and decodes them (cuh:253-298);
 //   * the grad_out rows of its head of every query (128 B each: 38 KB), streamed into LDS by `buffer_load ... lds`

@@ -13,7 +13,7 @@
 // bounding box of the pixels its samples' corners touch and leaves TWO 4-byte words per (batch, head, level, tile): 1 275
 // word pairs per level at 360p where
 // there were 20 400 tags.  A unit of this kernel -- a rectangle of <= 256 pixels of one level: a band of whole image
-// rows of a narrow level, a block of about 32 x 8 pixels of a wide one (gv_level_grid, vnx_common.h) --
+// rows of a narrow level, a block of about 32 x 8 pixels of a wide one (gv_level_grid, msda_units.h) --
 //   1. reads its level's tile words (one load round per 512 tiles), keeps the tiles whose box meets its rectangle
 //      (wave ballots + one 32-entry scan: ascending order);
 //   2. walks the kept tiles 128 queries (8 tiles) per chunk: one sample per thread -- its location and weight read
@@ -23,7 +23,7 @@
 //      by destination row and register accumulation as the record-fed kernel;
 //   3. writes its rows once -- or, for the pieces of a query-split level (gv_query_splits, split by tile range here), stores
 //      them into the piece's slab of fp32 partial rows; gv_split_finish_kernel adds the pieces (no atomics, no zeroing:
-//      gv_partial_rows_bound in vnx_common.h has the measurement that retired the atomics).
+//      gv_partial_rows_bound in msda_units.h has the measurement that retired the atomics).
 // No records, no tags, no windows.  Levels must be packed (checked on the device).  Reference semantics:
 // ms_deform_im2col_cuda.cuh:87-159 (the scatter this replaces), :253-298 (index decode).
 #include "msda_gv_common.h"

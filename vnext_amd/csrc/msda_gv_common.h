@@ -2,7 +2,7 @@
 // (msda_d32_gvrec.hip: fed by sample records; msda_d32_gvtiles.hip: fed by query-tile summaries).
 #pragma once
 
-#include "vnx_common.h"
+#include "msda_units.h"
 
 namespace vnx {
 namespace rec {

@@ -1,7 +1,7 @@
 // msda_launchers.h -- the host-side launchers of the MSDA kernels, one per source file, as capi.hip calls them.
 // Included by capi.hip and by every file that defines one of them.
 #pragma once
-#include "vnx_common.h"
+#include "msda_units.h"
 
 namespace vnx {
 

@@ -56,9 +56,8 @@ constexpr int kOtaWaves = kOtaThreads / kWave;
 constexpr int kOtaTop = 128;                      // >= the largest candidate count (100)
 constexpr size_t kOtaLdsBytes = 160 * 1024;       // LDS of a gfx950 CU
 
-__host__ __device__ inline int ota_qpad(int Q) { return (Q + 3) & ~3; }
 __host__ __device__ inline size_t ota_lds_bytes(int n, int Q) {
-  const size_t Qp = ota_qpad(Q);
+  const size_t Qp = pad4(Q);
   return size_t(n) * (5 * Qp + 8) + 9 * Qp + size_t(4) * Q + 4 * kOtaTop + 64;
 }
 __host__ __device__ inline int ota_out_words(int n_cap, int Q) {
@@ -95,24 +94,18 @@ struct OtaLds {
 __device__ __forceinline__ OtaLds ota_carve(unsigned char* smem, int n, int Q) {
   OtaLds s;
   s.cost = reinterpret_cast<float*>(smem);
-  s.ikey = reinterpret_cast<int*>(s.cost + size_t(n) * ota_qpad(Q));
-  s.ckey = s.ikey + ota_qpad(Q);
-  s.rank = s.ckey + ota_qpad(Q);
+  s.ikey = reinterpret_cast<int*>(s.cost + size_t(n) * pad4(Q));
+  s.ckey = s.ikey + pad4(Q);
+  s.rank = s.ckey + pad4(Q);
   s.top = reinterpret_cast<float*>(s.rank + Q);
   s.col_has = reinterpret_cast<int*>(s.top + kOtaTop);
   s.inst = s.col_has + n;
   s.misc = s.inst + n;
   s.M = reinterpret_cast<uint8_t*>(s.misc + 16);
-  s.multi = s.M + size_t(n) * ota_qpad(Q);
+  s.multi = s.M + size_t(n) * pad4(Q);
   return s;
 }
 
-// A float as an integer with the same order (x < y <=> key(x) < key(y), -0 = +0): with integer keys "before q in (value,
-// index) order" is ONE comparison, key_j < key_q + (j < q), and the rank counts below need no second compare for the ties
-__device__ __forceinline__ int order_key(float x) {
-  const int b = __float_as_int(x + 0.f);
-  return b ^ ((b >> 31) & 0x7fffffff);
-}
 typedef int vnx_i4 __attribute__((ext_vector_type(4)));
 
 struct Box { float x0, y0, x1, y1; };
@@ -192,7 +185,7 @@ __device__ __forceinline__ int row_count(const OtaLds& s, int q, int n, int Qp) 
 __device__ int dynamic_k(const OtaLds& s, int n, int Q, int kc, bool keep_bit1, const float* __restrict__ boxes,
                          const float* __restrict__ tgt_boxes, int off) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int Qp = ota_qpad(Q);
+  const int Qp = pad4(Q);
   VNX_PLAIN_LOOP for (int c = 0; c < n; ++c) {
     const Box g = to_xyxy(*reinterpret_cast<const vnx_f4*>(tgt_boxes + size_t(off + s.inst[c]) * 4));
     const float* col = s.cost + size_t(c) * Qp;
@@ -283,7 +276,7 @@ __global__ __launch_bounds__(kOtaThreads) void idol_match_kernel(OtaArgs a) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int p = blockIdx.x;
   const bool selection = p >= a.n_det;
-  const int Q = a.Q, K = a.K, Qp = ota_qpad(Q);
+  const int Q = a.Q, K = a.K, Qp = pad4(Q);
   int32_t* out = a.out + size_t(p) * a.stride;
   const int off = a.problems[2 * p], cnt = a.problems[2 * p + 1];
   if (cnt < 0 || off < 0 || cnt > a.n_tot || off > a.n_tot - cnt || cnt > a.n_cap || (selection && off < a.valid_first)) {
@@ -409,18 +402,25 @@ __global__ __launch_bounds__(kOtaThreads) void idol_match_kernel(OtaArgs a) {
 
 }  // namespace
 
-int idol_match_cap(int queries) {
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" int vnx_idol_match_max_targets(int queries) {      // targets of one problem at most
+  if (queries < 1) return 0;
   int n = 0;
   while (ota_lds_bytes(n + 1, queries) <= kOtaLdsBytes) ++n;
   return n;
 }
 
-int idol_match_out_words(int targets_max, int queries) { return ota_out_words(targets_max, queries); }
+extern "C" int vnx_idol_match_out_words(int targets_max, int queries) {      // int32 words of one problem's output
+  return targets_max < 0 || queries < 1 ? 0 : ota_out_words(targets_max, queries);
+}
 
-int idol_match(const float* det_prob, const float* det_boxes, const float* ref_prob, const float* ref_boxes,
-               const float* target_boxes, const int64_t* labels, const uint8_t* valid, const int32_t* problems,
-               int det_problems, int ref_problems, int queries, int classes, int targets_total, int valid_first,
-               int targets_max, int32_t* out, int out_stride, hipStream_t stream) {
+extern "C" int vnx_idol_match(const void* det_prob, const void* det_boxes, const void* ref_prob, const void* ref_boxes,
+                              const void* target_boxes, const void* labels, const void* valid, const void* problems,
+                              int det_problems, int ref_problems, int queries, int classes, int targets_total,
+                              int valid_first, int targets_max, void* out, int out_stride, void* hip_stream) {
   const char* fn = "vnx_idol_match";
   if (det_problems < 0 || ref_problems < 0 || queries < 1 || classes < 1 || targets_total < 0 || targets_max < 0 ||
       targets_max > targets_total || valid_first < 0 || valid_first > targets_total) {
@@ -436,7 +436,7 @@ int idol_match(const float* det_prob, const float* det_boxes, const float* ref_p
   }
   if (ota_lds_bytes(targets_max, queries) > kOtaLdsBytes) {
     set_error("%s: %d targets of one problem against %d queries: at most %d fit the LDS of a CU", fn, targets_max, queries,
-              idol_match_cap(queries));
+              vnx_idol_match_max_targets(queries));
     return VNX_ERR_UNSUPPORTED;
   }
   if (P >= (int64_t(1) << 24) || int64_t(queries) * classes >= (int64_t(1) << 31) || int64_t(queries) >= (int64_t(1) << 20)) {
@@ -470,10 +470,10 @@ int idol_match(const float* det_prob, const float* det_boxes, const float* ref_p
       if (device >= 0 && device < kDevices) asked[device].store(true, std::memory_order_release);
     }
   }
-  const OtaArgs a{det_prob, det_boxes, ref_prob, ref_boxes, target_boxes, labels, valid, problems, out,
-                  det_problems, ref_problems, queries, classes, targets_total, valid_first, targets_max, out_stride};
-  hipLaunchKernelGGL(idol_match_kernel, dim3(unsigned(P)), dim3(kOtaThreads), lds, stream, a);
+  const OtaArgs a{(const float*)det_prob, (const float*)det_boxes, (const float*)ref_prob, (const float*)ref_boxes,
+                  (const float*)target_boxes, (const int64_t*)labels, (const uint8_t*)valid, (const int32_t*)problems,
+                  (int32_t*)out, det_problems, ref_problems, queries, classes, targets_total, valid_first, targets_max,
+                  out_stride};
+  hipLaunchKernelGGL(idol_match_kernel, dim3(unsigned(P)), dim3(kOtaThreads), lds, (hipStream_t)hip_stream, a);
   return check_launch(fn);
 }
-
-}  // namespace vnx

@@ -35,8 +35,6 @@
 //   Gdot_jr = g[j][0] sigmoid(pair_j) ([r in N] softmax_N(dot)_r - [r in P] softmax_P(-dot)_r)
 //   Gcos_jr = g[j][1] 2 (cos_r - [r in P]) [r in A] / max(|A|, 1)
 // Accurate expf / logf / log1pf and true divisions throughout (no fast-math), as mask_loss.hip.
-//
-// C entry points: capi.hip.
 #include "vnx_common.h"
 
 #include <math.h>
@@ -76,22 +74,12 @@ template <> __device__ __forceinline__ float rl_zero<1>() { return 0.f; }
 __device__ __forceinline__ float rl_dot(vnx_f4 a, vnx_f4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
 __device__ __forceinline__ float rl_dot(float a, float b) { return a * b; }
 
-__device__ __forceinline__ float rl_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float rl_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // N values at once over the workgroup, every lane gets the results: the exchange tree, then the four waves in order
 template <int N, bool kMax>
 __device__ __forceinline__ void rl_block_reduce(float (&v)[N], float (*s)[8]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int i = 0; i < N; ++i) v[i] = kMax ? rl_wave_max(v[i]) : rl_wave_sum(v[i]);
+  for (int i = 0; i < N; ++i) v[i] = kMax ? wave_max(v[i]) : wave_sum(v[i]);
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < N; ++i) s[wave][i] = v[i];
@@ -199,7 +187,7 @@ __global__ void __launch_bounds__(kRlThreads) reid_loss_fwd_kernel(const RlIn in
     const Vec kv = rl_load<V>(k + c);
     kk += rl_dot(kv, kv);
   }
-  const float nk = sqrtf(rl_wave_sum(kk));
+  const float nk = sqrtf(wave_sum(kk));
   // kRlFwdRows rows per wave and round (rows r0, r0 + 4, ...): that many 16-byte loads in flight per lane -- with a
   // workgroup per instance the grid is a handful of workgroups, and a round's time is one load latency
   for (int r0 = wave; r0 < R; r0 += kRlFwdRows * kRlWaves) {
@@ -237,8 +225,8 @@ __global__ void __launch_bounds__(kRlThreads) reid_loss_fwd_kernel(const RlIn in
     }
 #pragma unroll
     for (int u = 0; u < kRlFwdRows; ++u) {
-      d[u] = rl_wave_sum(d[u]);
-      n[u] = rl_wave_sum(n[u]);
+      d[u] = wave_sum(d[u]);
+      n[u] = wave_sum(n[u]);
     }
     if (lane == 0) {
 #pragma unroll
@@ -423,32 +411,51 @@ static bool rl_vec(const RlIn& in) {
          (reinterpret_cast<uintptr_t>(in.key) & 15) == 0 && (reinterpret_cast<uintptr_t>(in.ref) & 15) == 0;
 }
 
-int reid_loss_forward(const float* key, int64_t key_stride, int key_rows, const float* ref, int64_t ref_stride, int ref_rows,
-                      int channels, int images, const int32_t* img, const int32_t* key_query, const uint8_t* flags,
-                      int instances, float* out, float* dot, float* ref_norm, float* stats, hipStream_t stream) {
+static RlIn rl_in(const void* key, long long key_image_stride, int key_rows, const void* ref, long long ref_image_stride,
+                  int ref_rows, int channels, int images, const void* img, const void* key_query, const void* flags,
+                  int instances) {
+  return RlIn{(const float*)key, (const float*)ref, int64_t(key_image_stride), int64_t(ref_image_stride), (const int32_t*)img,
+              (const int32_t*)key_query, (const uint8_t*)flags, images, key_rows, ref_rows, channels, instances};
+}
+
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" int vnx_reid_loss_forward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                                     long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                                     const void* key_query, const void* flags, int instances, void* out, void* dot,
+                                     void* ref_norm, void* stats, void* hip_stream) {
   const char* fn = "vnx_reid_loss_forward";
-  const RlIn in{key, ref, key_stride, ref_stride, img, key_query, flags, images, key_rows, ref_rows, channels, instances};
+  const RlIn in = rl_in(key, key_image_stride, key_rows, ref, ref_image_stride, ref_rows, channels, images, img, key_query,
+                        flags, instances);
   if (int st = rl_check(fn, in)) return st;
   if (instances == 0) return VNX_OK;
   if (!out || !dot || !ref_norm || !stats) {
     set_error("%s: null pointer argument", fn);
     return VNX_ERR_INVALID_ARGUMENT;
   }
+  hipStream_t stream = (hipStream_t)hip_stream;
   if (rl_vec(in))
-    hipLaunchKernelGGL(reid_loss_fwd_kernel<4>, dim3(uint32_t(instances)), dim3(kRlThreads), 0, stream, in, out, dot, ref_norm,
-                       stats);
+    hipLaunchKernelGGL(reid_loss_fwd_kernel<4>, dim3(uint32_t(instances)), dim3(kRlThreads), 0, stream, in, (float*)out,
+                       (float*)dot, (float*)ref_norm, (float*)stats);
   else
-    hipLaunchKernelGGL(reid_loss_fwd_kernel<1>, dim3(uint32_t(instances)), dim3(kRlThreads), 0, stream, in, out, dot, ref_norm,
-                       stats);
+    hipLaunchKernelGGL(reid_loss_fwd_kernel<1>, dim3(uint32_t(instances)), dim3(kRlThreads), 0, stream, in, (float*)out,
+                       (float*)dot, (float*)ref_norm, (float*)stats);
   return check_launch("reid_loss_fwd");
 }
 
-int reid_loss_backward(const float* key, int64_t key_stride, int key_rows, const float* ref, int64_t ref_stride, int ref_rows,
-                       int channels, int images, const int32_t* img, const int32_t* key_query, const uint8_t* flags,
-                       int instances, const float* dot, const float* ref_norm, const float* stats, const float* grad_out,
-                       float* grad_key, float* grad_ref, hipStream_t stream) {
+extern "C" int vnx_reid_loss_backward(const void* key, long long key_image_stride, int key_rows, const void* ref,
+                                      long long ref_image_stride, int ref_rows, int channels, int images, const void* img,
+                                      const void* key_query, const void* flags, int instances, const void* dot_v,
+                                      const void* ref_norm_v, const void* stats_v, const void* grad_out_v, void* grad_key,
+                                      void* grad_ref, void* hip_stream) {
   const char* fn = "vnx_reid_loss_backward";
-  const RlIn in{key, ref, key_stride, ref_stride, img, key_query, flags, images, key_rows, ref_rows, channels, instances};
+  const RlIn in = rl_in(key, key_image_stride, key_rows, ref, ref_image_stride, ref_rows, channels, images, img, key_query,
+                        flags, instances);
+  const float *dot = (const float*)dot_v, *ref_norm = (const float*)ref_norm_v, *stats = (const float*)stats_v,
+              *grad_out = (const float*)grad_out_v;
+  hipStream_t stream = (hipStream_t)hip_stream;
   if (int st = rl_check(fn, in)) return st;
   if (!grad_key || !grad_ref || (instances > 0 && (!dot || !ref_norm || !stats || !grad_out))) {
     set_error("%s: null pointer argument", fn);
@@ -458,15 +465,13 @@ int reid_loss_backward(const float* key, int64_t key_stride, int key_rows, const
   const int64_t lanes = int64_t(images) * ref_rows * ((channels + (vec ? 3 : 0)) / (vec ? 4 : 1));
   const dim3 ref_grid(uint32_t((lanes + kRlThreads - 1) / kRlThreads)), key_grid(uint32_t(images) * uint32_t(key_rows));
   if (vec)
-    hipLaunchKernelGGL(reid_loss_bwd_ref_kernel<4>, ref_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, grad_ref);
+    hipLaunchKernelGGL(reid_loss_bwd_ref_kernel<4>, ref_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, (float*)grad_ref);
   else
-    hipLaunchKernelGGL(reid_loss_bwd_ref_kernel<1>, ref_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, grad_ref);
+    hipLaunchKernelGGL(reid_loss_bwd_ref_kernel<1>, ref_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, (float*)grad_ref);
   if (int st = check_launch("reid_loss_bwd_ref")) return st;
   if (vec)
-    hipLaunchKernelGGL(reid_loss_bwd_key_kernel<4>, key_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, grad_key);
+    hipLaunchKernelGGL(reid_loss_bwd_key_kernel<4>, key_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, (float*)grad_key);
   else
-    hipLaunchKernelGGL(reid_loss_bwd_key_kernel<1>, key_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, grad_key);
+    hipLaunchKernelGGL(reid_loss_bwd_key_kernel<1>, key_grid, dim3(kRlThreads), 0, stream, in, dot, ref_norm, stats, grad_out, (float*)grad_key);
   return check_launch("reid_loss_bwd_key");
 }
-
-}  // namespace vnx

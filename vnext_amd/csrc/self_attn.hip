@@ -39,27 +39,12 @@ constexpr int kSaPad = 36;           // floats per staged row (144 B: the 8 rows
 constexpr int kSaPerLane = kSaChunk / kSaLanes;
 constexpr float kSaLowest = -1.0e30f;
 
-__device__ __forceinline__ uint32_t sa_hash(uint32_t idx, uint32_t seed_lo, uint32_t seed_hi) {      // = an_hash (add_norm.hip)
-  uint32_t h = idx ^ seed_lo;
-  h *= 0xcc9e2d51u; h = (h << 15) | (h >> 17); h *= 0x1b873593u;
-  h ^= seed_hi;
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-__device__ __forceinline__ void sa_effective_seed(uint32_t& lo, uint32_t& hi, const unsigned long long* seed_device) {
-  if (seed_device == nullptr) return;                                  // = an_effective_seed (add_norm.hip)
-  const unsigned long long s = *seed_device;
-  uint32_t a = uint32_t(s) * 0x9E3779B1u, b = (uint32_t(s >> 32) + 0x7F4A7C15u) * 0x85EBCA77u;
-  a ^= a >> 15; b ^= b >> 13;
-  lo ^= a * 0xC2B2AE3Du;
-  hi ^= b * 0x27D4EB2Fu + a;
-}
 // keep the probability of (row of the [batch * heads * queries] list, key)?  The 64-bit element index is split: its low 32
 // bits are hashed, the rest is mixed into the seed.
 __device__ __forceinline__ bool sa_keep(uint32_t bh_row, uint32_t key, uint32_t nq, uint32_t threshold, uint32_t seed_lo,
                                         uint32_t seed_hi) {
   const uint64_t e = uint64_t(bh_row) * nq + key;
-  return sa_hash(uint32_t(e), seed_lo, seed_hi ^ (uint32_t(e >> 32) * 0x9E3779B1u)) >= threshold;
+  return dropout_hash(uint32_t(e), seed_lo, seed_hi ^ (uint32_t(e >> 32) * 0x9E3779B1u)) >= threshold;
 }
 
 struct SaArgs {
@@ -180,7 +165,7 @@ query_self_attn_fwd_kernel(SaArgs a, float* __restrict__ out, float* __restrict_
   const bool live = row < a.Q;
   const int rowc = live ? row : a.Q - 1;
   uint32_t seed_lo = a.seed_lo, seed_hi = a.seed_hi;
-  if (DROP) sa_effective_seed(seed_lo, seed_hi, a.seed_device);
+  if (DROP) dropout_effective_seed(seed_lo, seed_hi, a.seed_device);
 
   SaRow q = sa_global_row(a, int64_t(b) * a.Q + rowc, h, 0);
 #pragma unroll
@@ -255,7 +240,7 @@ query_self_attn_bwd_kernel(SaArgs a, const float* __restrict__ out, const float*
   const bool live = row < a.Q;
   const int rowc = live ? row : a.Q - 1;
   uint32_t seed_lo = a.seed_lo, seed_hi = a.seed_hi;
-  if (DROP) sa_effective_seed(seed_lo, seed_hi, a.seed_device);
+  if (DROP) dropout_effective_seed(seed_lo, seed_hi, a.seed_device);
   const float* go_head = grad_out + int64_t(b) * a.Q * C + h * kSaHd;
   const float* o_head = out + int64_t(b) * a.Q * C + h * kSaHd;
 
@@ -350,11 +335,6 @@ query_self_attn_bwd_kernel(SaArgs a, const float* __restrict__ out, const float*
   }
 }
 
-static uint32_t sa_threshold(float p) {      // keep iff hash >= threshold:  P(drop) = threshold / 2^32
-  const double t = double(p) * 4294967296.0;
-  return t <= 0.0 ? 0u : (t >= 4294967295.0 ? 0xffffffffu : uint32_t(t + 0.5));
-}
-
 static int sa_check(const char* fn, int dtype, int batch, int queries, int heads, int head_dim, int ld, float p) {
   if (dtype != VNX_F32) {
     set_error("%s: fp32 only (dtype %d)", fn, dtype);
@@ -391,7 +371,7 @@ extern "C" int vnx_query_self_attention_forward(int dtype, const void* qkv, cons
   }
   const int tiles = (queries + kSaRows - 1) / kSaRows;
   const SaArgs a{(const float*)qkv, (const float*)in_proj_bias, batch, queries, heads, row_stride, 1.f / sqrtf(float(kSaHd)),
-                 sa_threshold(p), 1.f / (1.f - p), uint32_t(seed), uint32_t(seed >> 32), seed_device};
+                 dropout_threshold(p), 1.f / (1.f - p), uint32_t(seed), uint32_t(seed >> 32), seed_device};
   if (a.threshold != 0u)
     hipLaunchKernelGGL(query_self_attn_fwd_kernel<true>, dim3(uint32_t(batch * heads * tiles)), dim3(kSaThreads), 0,
                        (hipStream_t)hip_stream, a, (float*)out, (float*)lse, tiles);
@@ -418,7 +398,7 @@ extern "C" int vnx_query_self_attention_backward(int dtype, const void* qkv, con
   }
   const int tiles = (queries + kSaRows - 1) / kSaRows;
   const SaArgs a{(const float*)qkv, (const float*)in_proj_bias, batch, queries, heads, row_stride, 1.f / sqrtf(float(kSaHd)),
-                 sa_threshold(p), 1.f / (1.f - p), uint32_t(seed), uint32_t(seed >> 32), seed_device};
+                 dropout_threshold(p), 1.f / (1.f - p), uint32_t(seed), uint32_t(seed >> 32), seed_device};
   if (a.threshold != 0u)
     hipLaunchKernelGGL(query_self_attn_bwd_kernel<true>, dim3(uint32_t(2 * batch * heads * tiles)), dim3(kSaThreads), 0,
                        (hipStream_t)hip_stream, a, (const float*)out, (const float*)lse, (const float*)grad_out,

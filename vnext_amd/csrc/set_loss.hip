@@ -41,8 +41,6 @@
 // Gradient conventions are ATen's: sign(pred - want) for the L1 term, sign(0) = 0; maximum / minimum hand the gradient to
 // the selected operand, and at an exact tie split it evenly between the two (the target's half goes nowhere); the
 // intersection is differentiated only where the overlap gate is open.
-//
-// C entry points: capi.hip.
 #include "vnx_common.h"
 
 namespace vnx {
@@ -122,12 +120,6 @@ __device__ __forceinline__ float sl_focal_grad(float x, bool t, float alpha) {  
   const SlElem m = sl_elem(x, t, alpha);
   const float dz = -m.at * (m.s * m.s) * (m.s + 2.f * m.ce * m.q);
   return t ? dz : -dz;
-}
-
-__device__ __forceinline__ float sl_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 struct SlBox { float cx, cy, w, h; };
@@ -212,10 +204,10 @@ __global__ void __launch_bounds__(kSlThreads) set_loss_fwd_kernel(const SlIn in,
       hits += arg == s_label[i] ? 1.f : 0.f;
     }
   }
-  focal = sl_wave_sum(focal);
-  l1 = sl_wave_sum(l1);
-  giou = sl_wave_sum(giou);
-  hits = sl_wave_sum(hits);
+  focal = wave_sum(focal);
+  l1 = wave_sum(l1);
+  giou = wave_sum(giou);
+  hits = wave_sum(hits);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
     s_part[wave][0] = focal; s_part[wave][1] = l1; s_part[wave][2] = giou; s_part[wave][3] = hits;
@@ -239,10 +231,10 @@ __global__ void __launch_bounds__(64) set_loss_finish_kernel(const float* __rest
   const vnx_f4* p = reinterpret_cast<const vnx_f4*>(partial) + int64_t(l) * per_layer;
   vnx_f4 a = {0.f, 0.f, 0.f, 0.f};
   for (int k = lane; k < per_layer; k += 64) a += p[k];
-  a.x = sl_wave_sum(a.x);
-  a.y = sl_wave_sum(a.y);
-  a.z = sl_wave_sum(a.z);
-  a.w = sl_wave_sum(a.w);
+  a.x = wave_sum(a.x);
+  a.y = wave_sum(a.y);
+  a.z = wave_sum(a.z);
+  a.w = wave_sum(a.w);
   if (lane == 0) *reinterpret_cast<vnx_f4*>(out + 4 * int64_t(l)) = a;
 }
 
@@ -341,12 +333,22 @@ static int sl_dims(const char* fn, const SlIn& in, int layers, int clips, int fr
   return VNX_OK;
 }
 
-int set_loss_forward(const float* logits, const float* boxes, const int64_t* lay, const int64_t* clip, const int64_t* qry,
-                     const int64_t* tgt, const int64_t* labels, const float* target_boxes, int layers, int clips,
-                     int frames, int queries, int classes, int pairs, int targets_total, float alpha, float* partial,
-                     size_t partial_bytes, float* out, hipStream_t stream) {
+static SlIn sl_in(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry, const void* tgt,
+                  const void* labels, const void* target_boxes) {
+  return SlIn{(const float*)logits, (const float*)boxes, (const int64_t*)lay, (const int64_t*)clip, (const int64_t*)qry,
+              (const int64_t*)tgt, (const int64_t*)labels, (const float*)target_boxes};
+}
+
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" int vnx_set_loss_forward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                                    const void* tgt, const void* labels, const void* target_boxes, int layers, int clips,
+                                    int frames, int queries, int classes, int pairs, int targets_total, float alpha,
+                                    void* partial, size_t partial_bytes, void* out, void* hip_stream) {
   const char* fn = "vnx_set_loss_forward";
-  const SlIn in{logits, boxes, lay, clip, qry, tgt, labels, target_boxes};
+  const SlIn in = sl_in(logits, boxes, lay, clip, qry, tgt, labels, target_boxes);
   SlDims d;
   if (int st = sl_dims(fn, in, layers, clips, frames, queries, classes, pairs, targets_total, alpha, &d)) return st;
   if (!partial || !out) {
@@ -358,20 +360,21 @@ int set_loss_forward(const float* logits, const float* boxes, const int64_t* lay
     set_error("%s: partial buffer of %zu bytes, %zu needed (partial and out 16-byte aligned)", fn, partial_bytes, need);
     return VNX_ERR_WORKSPACE;
   }
+  hipStream_t stream = (hipStream_t)hip_stream;
   hipLaunchKernelGGL(set_loss_fwd_kernel, dim3(uint32_t(layers) * uint32_t(clips) * uint32_t(d.pieces)), dim3(kSlThreads), 0,
-                     stream, in, d, partial);
+                     stream, in, d, (float*)partial);
   if (int st = check_launch("set_loss_fwd")) return st;
   hipLaunchKernelGGL(set_loss_finish_kernel, dim3(uint32_t(layers)), dim3(64), 0, stream, (const float*)partial,
-                     clips * d.pieces, out);
+                     clips * d.pieces, (float*)out);
   return check_launch("set_loss_finish");
 }
 
-int set_loss_backward(const float* logits, const float* boxes, const int64_t* lay, const int64_t* clip, const int64_t* qry,
-                      const int64_t* tgt, const int64_t* labels, const float* target_boxes, int layers, int clips,
-                      int frames, int queries, int classes, int pairs, int targets_total, float alpha,
-                      const float* grad_out, float* grad_logits, float* grad_boxes, hipStream_t stream) {
+extern "C" int vnx_set_loss_backward(const void* logits, const void* boxes, const void* lay, const void* clip, const void* qry,
+                                     const void* tgt, const void* labels, const void* target_boxes, int layers, int clips,
+                                     int frames, int queries, int classes, int pairs, int targets_total, float alpha,
+                                     const void* grad_out, void* grad_logits, void* grad_boxes, void* hip_stream) {
   const char* fn = "vnx_set_loss_backward";
-  const SlIn in{logits, boxes, lay, clip, qry, tgt, labels, target_boxes};
+  const SlIn in = sl_in(logits, boxes, lay, clip, qry, tgt, labels, target_boxes);
   SlDims d;
   if (int st = sl_dims(fn, in, layers, clips, frames, queries, classes, pairs, targets_total, alpha, &d)) return st;
   if (!grad_out || !grad_logits || !grad_boxes) {
@@ -380,8 +383,6 @@ int set_loss_backward(const float* logits, const float* boxes, const int64_t* la
   }
   d.vec = d.vec && (reinterpret_cast<uintptr_t>(grad_logits) & 15) == 0;
   hipLaunchKernelGGL(set_loss_bwd_kernel, dim3(uint32_t(layers) * uint32_t(clips) * uint32_t(d.pieces)), dim3(kSlThreads), 0,
-                     stream, in, d, grad_out, grad_logits, grad_boxes);
+                     (hipStream_t)hip_stream, in, d, (const float*)grad_out, (float*)grad_logits, (float*)grad_boxes);
   return check_launch("set_loss_bwd");
 }
-
-}  // namespace vnx

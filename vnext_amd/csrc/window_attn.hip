@@ -343,16 +343,20 @@ static WaArgs wa_args(const void* qkv, const void* bias, const void* table, int 
 
 static bool wa_aligned(const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-size_t window_attention_partial_bytes(int batch, int height, int width, int heads, int window) {
+}  // namespace vnx
+
+using namespace vnx;
+
+extern "C" size_t vnx_window_attention_partial_bytes(int batch, int height, int width, int heads, int window) {
   if (batch < 0 || height < 1 || width < 1 || heads < 1 || window < 1 || window > kWaMaxWin) return 0;
   const int64_t nwin = int64_t((height + window - 1) / window) * ((width + window - 1) / window);
   const int64_t T = int64_t(2 * window - 1) * (2 * window - 1);
   return size_t(int64_t(batch) * nwin * heads * (T + 64) * int64_t(sizeof(float)));
 }
 
-int window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, void* out, void* lse,
-                             int batch, int height, int width, int heads, int head_dim, int row_stride, int window,
-                             int shift, float scale, void* hip_stream) {
+extern "C" int vnx_window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table,
+                                            void* out, void* lse, int batch, int height, int width, int heads, int head_dim,
+                                            int row_stride, int window, int shift, float scale, void* hip_stream) {
   const char* fn = "vnx_window_attention_forward";
   if (int st = wa_check(fn, dtype, batch, height, width, heads, head_dim, row_stride, window, shift)) return st;
   if (batch == 0) return VNX_OK;
@@ -372,11 +376,11 @@ int window_attention_forward(int dtype, const void* qkv, const void* qkv_bias, c
   return check_launch("window_attn_fwd");
 }
 
-int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table, const void* out,
-                              const void* lse, const void* grad_out, void* grad_qkv, void* grad_bias_table,
-                              void* grad_pad_bias, void* partial, size_t partial_bytes, int batch, int height, int width,
-                              int heads, int head_dim, int row_stride, int window, int shift, float scale,
-                              void* hip_stream) {
+extern "C" int vnx_window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, const void* bias_table,
+                                             const void* out, const void* lse, const void* grad_out, void* grad_qkv,
+                                             void* grad_bias_table, void* grad_pad_bias, void* partial, size_t partial_bytes,
+                                             int batch, int height, int width, int heads, int head_dim, int row_stride,
+                                             int window, int shift, float scale, void* hip_stream) {
   const char* fn = "vnx_window_attention_backward";
   if (int st = wa_check(fn, dtype, batch, height, width, heads, head_dim, row_stride, window, shift)) return st;
   if (batch == 0) return VNX_OK;
@@ -388,7 +392,7 @@ int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, 
     set_error("%s: qkv, qkv_bias, out, grad_out and grad_qkv must be 16-byte aligned", fn);
     return VNX_ERR_INVALID_ARGUMENT;
   }
-  const size_t need = window_attention_partial_bytes(batch, height, width, heads, window);
+  const size_t need = vnx_window_attention_partial_bytes(batch, height, width, heads, window);
   if (partial == nullptr || partial_bytes < need) {
     set_error("%s: partial buffer of %zu bytes, %zu needed", fn, partial_bytes, need);
     return VNX_ERR_WORKSPACE;
@@ -410,5 +414,3 @@ int window_attention_backward(int dtype, const void* qkv, const void* qkv_bias, 
                      heads * kWaHd, (float*)grad_bias_table, (float*)grad_pad_bias);
   return check_launch("window_attn_reduce");
 }
-
-}  // namespace vnx
