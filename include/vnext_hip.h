@@ -864,6 +864,47 @@ int vnx_clip_link_update(const vnx_clip_link_config* cfg, void* state, const voi
 int vnx_clip_link_result(const vnx_clip_link_config* cfg, const void* state, int num_tracks, void* cls_out,
                          void* logits_out, void* hip_stream);
 
+/*
+ * uint8 frames to network inputs (ingest.hip): normalise + pad + padding mask in one launch, and the per-level padding masks
+ * and sine positions of the padded batch in one more.  ADDITIVE: two symbols, no existing signature changed, so
+ * VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * pixels: uint8 device buffer of pixel_bytes bytes, 4-byte aligned, holding each frame's three CHW planes back to back
+ * (R plane, G plane, B plane of h x w bytes each).  table: int32 device [batch][3] = {byte offset of the frame's first plane
+ * inside pixels (any value: no alignment asked), h, w}.  The geometry is read from memory by the kernels, not by the host:
+ * a captured launch replays on new pixels AND new frame sizes; batch, height, width, the layout, mean / std, the level
+ * sizes, num_pos_feats and the two tables are baked in.  A row that does not describe planes inside pixels (a negative
+ * value, h > height, w > width, offset + 3 h w > pixel_bytes) is taken as an empty frame (all padding) by
+ * vnx_ingest_frames; no read leaves the buffer whatever the table holds.
+ *
+ * vnx_ingest_frames: height, width multiples of 32.  x fp32 [batch][3][height][width] (channels_last 0) or
+ * [batch][height][width][3] (channels_last 1), mask uint8 / bool [batch][height][width], both 16-byte aligned.  Inside a
+ * frame x = (float(u) - mean[c]) / std[c] -- an IEEE subtract, then a correctly rounded IEEE divide -- and mask = 0; outside
+ * x = 0 and mask = 1.  Every element of both is written: no memset is needed before the call.
+ *
+ * vnx_ingest_levels: for num_levels <= VNX_INGEST_MAX_LEVELS levels, level_sizes = host int [num_levels][2] = (h_l, w_l):
+ *   masks[l] uint8 / bool [batch][h_l][w_l]: torch's nearest resize of the padding mask (source index
+ *     min(int(floorf(dst * scale)), in - 1), scale = float(in) / out);
+ *   positions[l] fp32 [batch][h_l][w_l][2 * num_pos_feats], 16-byte aligned: the normalised sine position embedding of
+ *     that mask (models/position_encoding.py, normalize=True, scale 2 pi), the y half first, sin on even and cos on odd
+ *     features -- fp32 operations in the order of the eager chain.
+ * masks and positions are host arrays of num_levels device pointers.  dim_t, degenerate: fp32 device [num_pos_feats],
+ * 16-byte aligned: temperature ** (2 * (i / 2) / num_pos_feats), and the embedding's value where the row / column holds no
+ * valid pixel (its normaliser is 0 and the sine's argument about -3.1e6 / dim_t: the caller supplies what its reference
+ * computes there).  num_pos_feats: a multiple of 4 up to VNX_INGEST_MAX_POS_FEATS, else VNX_ERR_UNSUPPORTED.
+ *
+ * One launch each; no atomics, no workspace, no allocation, no synchronisation: both are capturable.  batch == 0 (or
+ * num_levels == 0): VNX_OK, no launch.
+ */
+#define VNX_INGEST_MAX_LEVELS 8
+#define VNX_INGEST_MAX_POS_FEATS 128
+int vnx_ingest_frames(const void* pixels, size_t pixel_bytes, const void* table, int batch, int height, int width,
+                      float mean0, float mean1, float mean2, float std0, float std1, float std2, int channels_last,
+                      void* x, void* mask, void* hip_stream);
+int vnx_ingest_levels(const void* table, int batch, int height, int width, int num_levels, const int* level_sizes,
+                      int num_pos_feats, const void* dim_t, const void* degenerate, void* const* masks,
+                      void* const* positions, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -89,6 +89,9 @@ SIGNATURES = {
     "vnx_clip_link_reset": (_i, [_vp, _vp, _vp]),
     "vnx_clip_link_update": (_i, [_vp] * 5 + [_i, _vp, _vp, _sz, _vp]),
     "vnx_clip_link_result": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "vnx_ingest_frames": (_i, [_vp, _sz, _vp, _i, _i, _i] + [ctypes.c_float] * 6 + [_i, _vp, _vp, _vp]),
+    "vnx_ingest_levels": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), _i, _vp, _vp, ctypes.POINTER(_vp),
+                               ctypes.POINTER(_vp), _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -130,6 +133,9 @@ REID_LOSS_MAX_ROWS = 1024                            # VNX_REID_LOSS_MAX_ROWS
 
 
 CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_INSTANCES, VNX_CLIP_LINK_MAX_FRAMES
+
+
+INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
 
 
 class ClipLinkConfig(ctypes.Structure):

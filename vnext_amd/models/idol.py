@@ -40,6 +40,7 @@ from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, bu
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
 from ..ops.det_select import DetSelectUnsupported, class_aware_nms, select_detections, select_detections_host  # noqa: F401 (class_aware_nms: the host NMS, re-exported)
+from ..ops import ingest
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import rle_encode, ytvis_records
 
@@ -134,6 +135,10 @@ class IDOL(nn.Module):
         # per-frame candidate selection (score threshold + class-aware NMS) by one kernel for the whole chunk
         # (vnext_amd/ops/det_select.py) instead of the host loop (opt-in: train.enable_device_selection); CUDA tensors only
         self.device_selection = False
+        # uint8 frames are uploaded as bytes and normalised, padded and masked by one kernel; the level masks and positions
+        # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
+        self.device_ingest = False
+        self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -142,8 +147,12 @@ class IDOL(nn.Module):
 
     # ---- shared trunk -------------------------------------------------------------------------
     def _preprocess(self, frames):
-        """normalise + pad to a multiple of 32 (idol.py:473-482, util/misc.py nested tensor)."""
-        frames = [(f.to(self.device, torch.float32) - self.pixel_mean) / self.pixel_std for f in frames]
+        """normalise + pad to a multiple of 32 (idol.py:473-482, util/misc.py nested tensor) -> (x, mask); with
+        `device_ingest` and uint8 frames -> (x, mask, table) from the ingest kernel (`_encode_decode` takes the table)."""
+        frames = list(frames)
+        if self.device_ingest and ingest.applies(frames, self.device):
+            return self._ingest(*ingest.stage_frames(frames, self.device), len(frames), *ingest.padded_size(frames))
+        frames =[(f.to(self.device, torch.float32) - self.pixel_mean) / self.pixel_std for f in frames]
         H = (max(f.shape[-2] for f in frames) + 31) // 32 * 32
         W = (max(f.shape[-1] for f in frames) + 31) // 32 * 32
         x = frames[0].new_zeros(len(frames), 3, H, W)
@@ -153,16 +162,32 @@ class IDOL(nn.Module):
             mask[i, :f.shape[-2], :f.shape[-1]] = False
         return x, mask
 
-    def _encode_decode(self, x, mask):
+    def _ingest(self, pixels, table, B, H, W):
+        """staged uint8 frames -> (x, mask, table): one launch; channels-last exactly where the ResNet trunk would convert"""
+        from . import seqformer      # (CHANNELS_LAST is set after import: read the module's attribute)
+        d = self.detr.detr
+        nhwc = (seqformer.CHANNELS_LAST and isinstance(d.backbone, ResNet50Trunk) and d.backbone.training
+                and torch.is_grad_enabled() and pixels.is_cuda)
+        x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
+        return x, mask, table
+
+    def _encode_decode(self, x, mask, table=None):
         """-> srcs, hs [Ld, N, Q, C], memory [N, S, C], per-layer pre-sigmoid references, the refined references, and the box
-        predictions of the decoder's refinement loop (what _box_heads would compute again; None if it used other heads)"""
+        predictions of the decoder's refinement loop (what _box_heads would compute again; None if it used other heads).
+        table: the frames' geometry on the device when x, mask came from `_ingest`: the level masks and positions are then one
+        launch of the ingest op"""
         d = self.detr.detr
         feats = d.backbone(x)
         srcs = [d.input_proj[l](f) for l, f in enumerate(feats)]
         for l in range(len(feats), d.num_feature_levels):
             srcs.append(d.input_proj[l](feats[-1] if l == len(feats) else srcs[-1]))
-        masks = [F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0] for s in srcs]
-        poss = [sine_position(mk, s.shape[1] // 2).to(s.dtype) for s, mk in zip(srcs, masks)]
+        if table is not None:
+            masks, poss = ingest.level_constants(table, x.shape[0], x.shape[-2], x.shape[-1],
+                                                 [s.shape[-2:] for s in srcs], srcs[0].shape[1] // 2)
+            poss = [p.to(s.dtype) for p, s in zip(poss, srcs)]
+        else:
+            masks = [F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0] for s in srcs]
+            poss = [sine_position(mk, s.shape[1] // 2).to(s.dtype) for s, mk in zip(srcs, masks)]
         hs, memory, init_ref, inter_refs, _, inter_boxes, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
         refs = [inverse_sigmoid(init_ref if l == 0 else inter_refs[l - 1]) for l in range(hs.shape[0])]
         if d.transformer.decoder.bbox_embed is not d.bbox_embed:
@@ -197,13 +222,13 @@ class IDOL(nn.Module):
             start += h * w
         return self.detr.mask_head(mem).float().contiguous()
 
-    def _train_trunk(self, x, mask):
+    def _train_trunk(self, x, mask, table=None):
         """Padded frames of the key / reference pairs (key frames at even positions) -> everything `losses` needs from the
         network, as a flat tuple of tensors: query states of every decoder layer [Ld, N, Q, C]; class logits and boxes of every
         layer on the KEY frames; the layers' pre-sigmoid reference xy on the key frames [Ld, bz, Q, 2]; the last layer's
         refined references on the REFERENCE frames; the key frames' stride-8 mask features; the reference frames' class logits
         (last layer); the reid embeddings of all frames."""
-        srcs, hs, memory, refs, inter_refs, inter_boxes = self._encode_decode(x, mask)
+        srcs, hs, memory, refs, inter_refs, inter_boxes = self._encode_decode(x, mask, table)
         loop_boxes = None if inter_boxes is None else inter_boxes[:, 0::2]
         logits, boxes = self._box_heads(hs[:, 0::2], [r[0::2] for r in refs], range(hs.shape[0]), loop_boxes)
         feats = self._mask_features([s[0::2] for s in srcs], memory[0::2])
@@ -340,7 +365,9 @@ class IDOL(nn.Module):
     @torch.no_grad()
     def _coco_trunk(self, batched_inputs):
         """-> logits, boxes, a `masks_of(image, queries)` callable (None with MASK_ON false), image sizes, output sizes"""
-        images = [x["image"].to(self.device, torch.float32) for x in batched_inputs]
+        images = [x["image"] for x in batched_inputs]
+        if not (self.device_ingest and ingest.applies(images, self.device)):      # uint8 images stay bytes until the kernel
+            images = [im.to(self.device, torch.float32) for im in images]
         image_sizes = [tuple(int(v) for v in im.shape[-2:]) for im in images]
         out_sizes = [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, image_sizes)]
         logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(images))
@@ -454,23 +481,29 @@ class IDOL(nn.Module):
                 records.append(rec)
         return records
 
-    def _chunk_trunk(self, x, mask):
+    def _chunk_trunk(self, x, mask, table=None):
         """Padded frames -> (logits [F,Q,K], boxes [F,Q,4], query states, pre-sigmoid reference of the
         last decoder layer, stride-8 mask features): the shape-static, sync-free part of inference."""
-        srcs, hs, memory, refs, _, inter_boxes = self._encode_decode(x, mask)
+        srcs, hs, memory, refs, _, inter_boxes = self._encode_decode(x, mask, table)
         last = hs.shape[0] - 1
         logits, boxes = self._box_heads(hs, refs, [last], inter_boxes)
         return logits[0], boxes[0], hs[last], refs[last], self._mask_features(srcs, memory)
 
-    def _chunk_trunk_graphed(self, stack):
-        """`_chunk_trunk` of same-sized frames replayed from a hipGraph captured per chunk shape
-        (a video is chunks of BATCH_INFER_LEN frames + one shorter tail: two graphs)."""
-        key = tuple(stack.shape)
+    def _chunk_trunk_graphed(self, stack, table=None, size=None):
+        """`_chunk_trunk` of same-sized frames replayed from a hipGraph captured per chunk shape and input dtype
+        (a video is chunks of BATCH_INFER_LEN frames + one shorter tail: two graphs).
+        With `table` (`device_ingest`): `stack` is the staged uint8 buffer of the chunk's frames padded to size = (H, W);
+        buffer and table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are
+        inside, and a replay reads the frames' sizes from the table."""
+        key = tuple(stack.shape) if table is None else (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
         entry = self._graphs.get(key)
         if entry is None:
             static_in = stack.clone()
+            static_table = None if table is None else table.clone()
 
             def run():
+                if static_table is not None:
+                    return self._chunk_trunk(*self._ingest(static_in, static_table, static_table.shape[0], *size))
                 h, w = static_in.shape[-2:]
                 H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
                 x = static_in.new_zeros(static_in.shape[0], 3, H, W)
@@ -489,9 +522,11 @@ class IDOL(nn.Module):
                 static_out = run()
             if len(self._graphs) >= 4:
                 self._graphs.pop(next(iter(self._graphs)))
-            entry = self._graphs[key] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
+            entry = self._graphs[key] = (graph, (static_in, static_table), static_out)
+        graph, (static_in, static_table), static_out = entry
         static_in.copy_(stack)
+        if table is not None:
+            static_table.copy_(table)
         graph.replay()
         return static_out
 
@@ -501,11 +536,20 @@ class IDOL(nn.Module):
         idol.py:331-349): list over frames of dicts {indices, logits [n,K], boxes [n,4], embeds
         [n,C], masks [n,1,H/4,W/4]} for the queries that survive the score threshold and the
         class-aware box NMS (0.9)."""
-        frames = [f.to(self.device, torch.float32) for f in frames]
-        if self.graph_inference and frames[0].is_cuda and all(f.shape == frames[0].shape for f in frames):
-            logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(torch.stack(frames))
+        frames = list(frames)
+        same = all(f.shape == frames[0].shape for f in frames)
+        if self.device_ingest and ingest.applies(frames, self.device):      # uint8 frames stay bytes until the kernel
+            if self.graph_inference and self.device.type == "cuda" and same:
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(
+                    *ingest.stage_frames(frames, self.device), ingest.padded_size(frames))
+            else:
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
         else:
-            logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
+            frames = [f.to(self.device, torch.float32) for f in frames]
+            if self.graph_inference and frames[0].is_cuda and same:
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(torch.stack(frames))
+            else:
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
         picks = self.select_candidates(logits, boxes)
         frame_of = torch.from_numpy(np.concatenate([np.full(len(c), f) for f, c in enumerate(picks)])).to(self.device)
         query = torch.from_numpy(np.concatenate(picks)).to(self.device)

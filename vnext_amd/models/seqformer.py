@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
+from ..ops import ingest
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
@@ -414,6 +415,10 @@ class SeqFormer(nn.Module):
         self.graph_training = False     # capture the training trunk's forward and backward (opt-in)
         self.device_matching = False    # match queries to targets on the device: no host round trip in `losses` (opt-in)
         self.device_clip_matching = False     # CLIP_MATCHING inference: link the clips on the device, no host copy per clip (opt-in)
+        # uint8 frames are uploaded as bytes and normalised, padded and masked by one kernel; the level masks and positions
+        # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
+        self.device_ingest = False
+        self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -422,8 +427,12 @@ class SeqFormer(nn.Module):
 
     # ---- shared trunk -------------------------------------------------------------------------
     def _preprocess(self, batched_inputs):
-        """normalise + pad to a multiple of 32 (seqformer.py:413-429, util/misc.py:298-302)."""
-        frames = [f.to(self.device, torch.float32) for clip in batched_inputs for f in clip["image"]]
+        """normalise + pad to a multiple of 32 (seqformer.py:413-429, util/misc.py:298-302) -> (x, mask); with
+        `device_ingest` and uint8 frames -> (x, mask, table) from the ingest kernel (`_features` takes the table)."""
+        frames = [f for clip in batched_inputs for f in clip["image"]]
+        if self.device_ingest and ingest.applies(frames, self.device):
+            return self._ingest(*ingest.stage_frames(frames, self.device), len(frames), *ingest.padded_size(frames))
+        frames = [f.to(self.device, torch.float32) for f in frames]
         frames = [(f - self.pixel_mean) / self.pixel_std for f in frames]
         H = max(f.shape[-2] for f in frames)
         W = max(f.shape[-1] for f in frames)
@@ -435,7 +444,17 @@ class SeqFormer(nn.Module):
             mask[i, :f.shape[-2], :f.shape[-1]] = False
         return x, mask
 
-    def _features(self, x, mask):
+    def _ingest(self, pixels, table, B, H, W):
+        """staged uint8 frames -> (x, mask, table): one launch; channels-last exactly where the ResNet trunk would convert"""
+        d = self.detr.detr
+        nhwc = (CHANNELS_LAST and isinstance(d.backbone, ResNet50Trunk) and d.backbone.training
+                and torch.is_grad_enabled() and pixels.is_cuda)
+        x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
+        return x, mask, table
+
+    def _features(self, x, mask, table=None):
+        """table: the frames' geometry on the device when x, mask came from `_ingest`: the level masks and positions are
+        then one launch of the ingest op instead of ~20 small ones per level"""
         d = self.detr.detr
         T = self.num_frames
         N = x.shape[0] // T
@@ -445,10 +464,15 @@ class SeqFormer(nn.Module):
             srcs.append(d.input_proj[l](f))
         for l in range(len(feats), d.num_feature_levels):
             srcs.append(d.input_proj[l](feats[-1] if l == len(feats) else srcs[-1]))
-        for s in srcs:
-            mk = F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0]
-            masks.append(mk)
-            poss.append(sine_position(mk, s.shape[1] // 2).to(s.dtype))
+        if table is not None:
+            masks, poss = ingest.level_constants(table, x.shape[0], x.shape[-2], x.shape[-1],
+                                                 [s.shape[-2:] for s in srcs], srcs[0].shape[1] // 2)
+            poss = [p.to(s.dtype) for p, s in zip(poss, srcs)]
+        else:
+            for s in srcs:
+                mk = F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0]
+                masks.append(mk)
+                poss.append(sine_position(mk, s.shape[1] // 2).to(s.dtype))
         fold = lambda t: t.reshape(N, T, *t.shape[1:])  # noqa: E731
         return [fold(s) for s in srcs], [fold(mk) for mk in masks], [fold(p) for p in poss]
 
@@ -473,8 +497,9 @@ class SeqFormer(nn.Module):
         return torch.stack(classes), torch.stack(coords)
 
     def _run(self, batched_inputs, want_refs=False):
-        x, mask = self._preprocess(batched_inputs)
-        srcs, masks, poss = self._features(x, mask)
+        pre = self._preprocess(batched_inputs)
+        x = pre[0]
+        srcs, masks, poss = self._features(*pre)
         hs, hs_box, memory, init_ref, inter_refs, inter_boxes, _, _ = self.detr.detr.transformer(
             srcs, masks, poss, self.detr.detr.query_embed.weight)
         logits, boxes = self._heads(hs, hs_box, init_ref, inter_refs, inter_boxes)
@@ -599,35 +624,50 @@ class SeqFormer(nn.Module):
         x[:, :, :h, :w] = (stack - self.pixel_mean) / self.pixel_std
         mask = torch.ones(stack.shape[0], H, W, dtype=torch.bool, device=stack.device)
         mask[:, :h, :w] = False
-        srcs, masks, poss = self._features(x, mask)
+        return self._clip_trunk_tail(x, mask)
+
+    def _clip_trunk_bytes(self, pixels, table, T, H, W):
+        """`_clip_trunk` from staged uint8 frames (`device_ingest`): T frames padded to H x W"""
+        return self._clip_trunk_tail(*self._ingest(pixels, table, T, H, W))
+
+    def _clip_trunk_tail(self, x, mask, table=None):
+        srcs, masks, poss = self._features(x, mask, table)
         d = self.detr.detr
         hs, _, memory, init_ref, inter_refs, _, _, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
         last = hs.shape[0] - 1
         ref = inverse_sigmoid(init_ref if last == 0 else inter_refs[last - 1])
         return d.class_embed[last](hs[last]), ref, hs[last], self._mask_features(srcs, memory)
 
-    def _clip_trunk_graphed(self, stack):
-        """`_clip_trunk` replayed from a hipGraph captured per (T, h, w): the ~1 500 launches of
+    def _clip_trunk_graphed(self, stack, table=None, size=None):
+        """`_clip_trunk` replayed from a hipGraph captured per (T, h, w) and input dtype: the ~1 500 launches of
         backbone + 6+6 transformer layers + mask-feature convs become one graph launch
-        (SURVEY section 8(f) rank 2).  Outputs live in the graph's static buffers until the next call."""
-        key = tuple(stack.shape)
+        (SURVEY section 8(f) rank 2).  Outputs live in the graph's static buffers until the next call.
+        With `table` (`device_ingest`): `stack` is the staged uint8 buffer of T frames padded to size = (H, W); buffer and
+        table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are inside, and
+        a replay reads the frames' sizes from the table."""
+        if table is None:
+            key, inputs, fn = tuple(stack.shape), (stack,), self._clip_trunk
+        else:
+            key = (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
+            inputs, fn = (stack, table), lambda p, t: self._clip_trunk_bytes(p, t, t.shape[0], *size)
         entry = self._graphs.get(key)
         if entry is None:
-            static_in = stack.clone()
+            static_in = tuple(t.clone() for t in inputs)
             side = torch.cuda.Stream(device=stack.device)
             side.wait_stream(torch.cuda.current_stream(stack.device))
             with torch.cuda.stream(side):           # warm-up outside capture: lazy inits, cached level tensors
                 for _ in range(2):
-                    self._clip_trunk(static_in)
+                    fn(*static_in)
             torch.cuda.current_stream(stack.device).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                static_out = self._clip_trunk(static_in)
+                static_out = fn(*static_in)
             if len(self._graphs) >= 4:              # a few resolutions at most; drop the oldest
                 self._graphs.pop(next(iter(self._graphs)))
             entry = self._graphs[key] = (graph, static_in, static_out)
         graph, static_in, static_out = entry
-        static_in.copy_(stack)
+        for s, t in zip(static_in, inputs):
+            s.copy_(t)
         graph.replay()
         return static_out
 
@@ -638,7 +678,14 @@ class SeqFormer(nn.Module):
         T = len(frames)
         keep, self.num_frames = self.num_frames, T
         try:
-            if all(f.shape == frames[0].shape for f in frames):
+            if frames[0].dtype == torch.uint8 and all(f.shape == frames[0].shape for f in frames):      # `device_ingest`
+                pixels, table = ingest.stage_frames(frames, self.device)
+                size = ingest.padded_size(frames)
+                if self.graph_inference and pixels.is_cuda:
+                    logits, ref_last, hs_last, feats = self._clip_trunk_graphed(pixels, table, size)
+                else:
+                    logits, ref_last, hs_last, feats = self._clip_trunk_bytes(pixels, table, T, *size)
+            elif all(f.shape == frames[0].shape for f in frames):
                 stack = torch.stack(frames)
                 trunk = self._clip_trunk_graphed if (self.graph_inference and stack.is_cuda) else self._clip_trunk
                 logits, ref_last, hs_last, feats = trunk(stack)
@@ -735,13 +782,15 @@ class SeqFormer(nn.Module):
         every CLIP_STRIDE, linked by mask sIoU (vnext_amd/models/clip_matching.py), tracks averaged."""
         assert len(batched_inputs) == 1
         video = batched_inputs[0]
-        frames = [f.to(self.device, torch.float32) for f in video["image"]]
+        frames = list(video["image"])
+        if not (self.device_ingest and ingest.applies(frames, self.device)):      # uint8 frames stay bytes until the kernel
+            frames = [f.to(self.device, torch.float32) for f in frames]
         ih, iw = frames[0].shape[-2:]
         out_size = (video.get("height", ih), video.get("width", iw))
         if not self.clip_matching:
             prob, mask_logits = self._top_instances(frames)
             return self._report(prob, mask_logits, (ih, iw), out_size, rle)
-        if self.device_clip_matching and frames[0].is_cuda:
+        if self.device_clip_matching and (frames[0].is_cuda or (frames[0].dtype == torch.uint8 and self.device.type == "cuda")):
             from ..ops.clip_link import ClipLinkUnsupported
             try:
                 cls, mask_logits = self._linked_clips(frames, on_device=True)

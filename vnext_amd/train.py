@@ -337,6 +337,20 @@ def enable_device_clip_matching(model, on: bool = True) -> None:
     model.device_clip_matching = bool(on)
 
 
+def enable_device_ingest(model, on: bool = True) -> None:
+    """Opt in to ingesting uint8 frames on the device (`SeqFormer.device_ingest` / `IDOL.device_ingest`,
+    vnext_amd/ops/ingest.py): the mappers' uint8 CHW frames cross the bus as bytes in one pinned, non-blocking copy (not as
+    floats, frame by frame, pageable), one kernel normalises, pads and writes the padding mask, and one more writes every
+    pyramid level's padding mask and sine position -- instead of a cast, a subtract, a divide, a slice copy and a mask fill
+    per frame and about 20 launches per level.  x and the masks are bit-identical to the eager path's; the positions agree to
+    fp32 rounding of the sine's argument, and exactly on rows and columns without a valid pixel.  Float frames take the
+    eager path whatever the switch says; the captured training trunks (`graph_training`) are unchanged.  Raises for a model
+    without the switch."""
+    if not hasattr(model, "device_ingest"):
+        raise ValueError("enable_device_ingest: %s has no device_ingest switch" % type(model).__name__)
+    model.device_ingest = bool(on)
+
+
 def enable_fused_mask_loss(model, on: bool = True) -> None:
     """Opt in to the fused mask losses (`criterion.fused_mask_loss`, vnext_amd/ops/mask_loss.py): focal + dice of the
     matched instances' mask logits in one kernel pass each way, the ground truth read in place at image resolution --
