@@ -905,6 +905,43 @@ int vnx_ingest_levels(const void* table, int batch, int height, int width, int n
                       int num_pos_feats, const void* dim_t, const void* degenerate, void* const* masks,
                       void* const* positions, void* hip_stream);
 
+/*
+ * Test-time resize fused into the ingest (resize.hip): staged uint8 source frames to the x and mask of vnx_ingest_frames, of
+ * the frames RESIZED as Pillow's Image.resize(..., BILINEAR) resizes 8-bit images -- byte for byte -- in one launch.
+ * ADDITIVE: one symbol, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs it looks it up.
+ *
+ * pixels: uint8 device buffer of pixel_bytes bytes, 4-byte aligned.  interleaved 0: each frame is three planes of h x w bytes
+ * back to back (CHW); interleaved 1: h x w pixels of 3 bytes (HWC).  src_table: int32 device [batch][3] = {byte offset of the
+ * frame inside pixels (any value: no alignment asked), h, w}.  dst_table: int32 device [batch][3] = {0, nh, nw}, the target
+ * sizes: the table vnx_ingest_levels takes for the resized batch.  coeffs: int32 device buffer of coeff_words words; its first
+ * 6 * batch words are a row per frame {bounds offset, weights offset, ksize} for the horizontal pass (w -> nw), then the same
+ * for the vertical pass (h -> nh), offsets in words from the start of coeffs.  bounds: int32 [n_out][2] = {first source
+ * index, tap count}; weights: int32 [n_out][ksize], 22-bit fixed point, non-negative: Pillow's precompute_coeffs for the
+ * bilinear filter, normalised and rounded as its 8-bit path does (the caller computes them in double; the kernel never
+ * evaluates the filter).  ksize 0: the axis keeps its size and the pass is skipped.  A pass is
+ * min((2^21 + sum_t weight[t] * src[first + t]) >> 22, 255); the horizontal pass runs first and is rounded to bytes.
+ * 1 <= ksize <= VNX_RESIZE_MAX_KSIZE: a downscale of up to 8x, any upscale.
+ *
+ * Everything the kernel needs of the frames is read from memory by the kernel, not by the host: a captured launch replays
+ * on new pixels (and on other sizes, as long as the tables and coefficients in memory describe them); batch, height, width,
+ * the layouts and mean / std are baked in.  A frame whose rows do not describe bytes inside pixels, a target inside height x
+ * width and tables inside coeffs (a negative value, nh > height, nw > width, offset + 3 h w > pixel_bytes, ksize above the
+ * limit, ksize 0 on an axis whose size changes, table offsets outside coeffs) is taken as an empty frame (all padding), and
+ * table entries are clamped to the source: no read leaves a buffer whatever the tables hold.
+ *
+ * height, width multiples of 32.  x fp32 [batch][3][height][width] (channels_last 0) or [batch][height][width][3]
+ * (channels_last 1), mask uint8 / bool [batch][height][width], both 16-byte aligned.  Inside a resized frame
+ * x = (float(u) - mean[c]) / std[c] -- an IEEE subtract, then a correctly rounded IEEE divide -- and mask = 0; outside x = 0
+ * and mask = 1.  A frame whose target equals its source gives exactly what vnx_ingest_frames gives.  Every element of both
+ * is written: no memset is needed before the call.  One launch; no atomics, no workspace, no allocation, no
+ * synchronisation: capturable.  batch == 0: VNX_OK, no launch.
+ */
+#define VNX_RESIZE_MAX_KSIZE 17
+int vnx_resize_ingest_frames(const void* pixels, size_t pixel_bytes, const void* src_table, const void* dst_table,
+                             const void* coeffs, size_t coeff_words, int batch, int height, int width, float mean0,
+                             float mean1, float mean2, float std0, float std1, float std2, int channels_last,
+                             int interleaved, void* x, void* mask, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -92,6 +92,8 @@ SIGNATURES = {
     "vnx_ingest_frames": (_i, [_vp, _sz, _vp, _i, _i, _i] + [ctypes.c_float] * 6 + [_i, _vp, _vp, _vp]),
     "vnx_ingest_levels": (_i, [_vp, _i, _i, _i, _i, ctypes.POINTER(_i), _i, _vp, _vp, ctypes.POINTER(_vp),
                                ctypes.POINTER(_vp), _vp]),
+    "vnx_resize_ingest_frames": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i] + [ctypes.c_float] * 6 +
+                                 [_i, _i, _vp, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -136,6 +138,9 @@ CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_I
 
 
 INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
+
+
+RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
 
 
 class ClipLinkConfig(ctypes.Structure):

@@ -40,7 +40,7 @@ from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, bu
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
 from ..ops.det_select import DetSelectUnsupported, class_aware_nms, select_detections, select_detections_host  # noqa: F401 (class_aware_nms: the host NMS, re-exported)
-from ..ops import ingest
+from ..ops import ingest, resize
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import rle_encode, ytvis_records
 
@@ -139,6 +139,10 @@ class IDOL(nn.Module):
         # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
         self.device_ingest = False
         self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
+        # eval mode, uint8 video frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel
+        # that also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
+        self.device_resize = False
+        self._test_size = (int(getattr(cfg.INPUT, "MIN_SIZE_TEST", 480)), int(getattr(cfg.INPUT, "MAX_SIZE_TEST", 1333)))
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -170,6 +174,13 @@ class IDOL(nn.Module):
                 and torch.is_grad_enabled() and pixels.is_cuda)
         x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
         return x, mask, table
+
+    def _resize_ingest(self, pixels, src_table, dst_table, coeffs, B, H, W, layout):
+        """staged uint8 SOURCE frames -> (x, mask, table) of the frames resized to the targets in dst_table: one launch
+        (eval mode only: never channels-last); dst_table is the geometry `_encode_decode` hands to the level launch"""
+        x, mask = resize.resize_ingest_frames(pixels, src_table, dst_table, coeffs, B, H, W, *self._pixel_stats,
+                                              channels_last=False, layout=layout)
+        return x, mask, dst_table
 
     def _encode_decode(self, x, mask, table=None):
         """-> srcs, hs [Ld, N, Q, C], memory [N, S, C], per-layer pre-sigmoid references, the refined references, and the box
@@ -489,19 +500,32 @@ class IDOL(nn.Module):
         logits, boxes = self._box_heads(hs, refs, [last], inter_boxes)
         return logits[0], boxes[0], hs[last], refs[last], self._mask_features(srcs, memory)
 
-    def _chunk_trunk_graphed(self, stack, table=None, size=None):
+    def _chunk_trunk_graphed(self, stack, table=None, size=None, resized=None):
         """`_chunk_trunk` of same-sized frames replayed from a hipGraph captured per chunk shape and input dtype
         (a video is chunks of BATCH_INFER_LEN frames + one shorter tail: two graphs).
         With `table` (`device_ingest`): `stack` is the staged uint8 buffer of the chunk's frames padded to size = (H, W);
         buffer and table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are
-        inside, and a replay reads the frames' sizes from the table."""
-        key = tuple(stack.shape) if table is None else (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
+        inside, and a replay reads the frames' sizes from the table.
+        With `resized` = (layout, source sizes, targets) (`device_resize`): `stack` is the four tensors of
+        `resize.stage_sources`, all static inputs; the coefficients' layout follows the sizes, so the key holds the source
+        and target sizes as well."""
+        extra = ()
+        if resized is not None:
+            layout, sizes, targets = resized
+            stack, table, *extra = stack
+            key = ("resize", tuple(stack.shape), layout, tuple(sizes), tuple(targets)) + tuple(size)
+        else:
+            key = tuple(stack.shape) if table is None else (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
         entry = self._graphs.get(key)
         if entry is None:
             static_in = stack.clone()
             static_table = None if table is None else table.clone()
+            static_extra = tuple(t.clone() for t in extra)
 
             def run():
+                if resized is not None:
+                    return self._chunk_trunk(*self._resize_ingest(static_in, static_table, *static_extra,
+                                                                  static_table.shape[0], *size, layout))
                 if static_table is not None:
                     return self._chunk_trunk(*self._ingest(static_in, static_table, static_table.shape[0], *size))
                 h, w = static_in.shape[-2:]
@@ -522,23 +546,37 @@ class IDOL(nn.Module):
                 static_out = run()
             if len(self._graphs) >= 4:
                 self._graphs.pop(next(iter(self._graphs)))
-            entry = self._graphs[key] = (graph, (static_in, static_table), static_out)
-        graph, (static_in, static_table), static_out = entry
+            entry = self._graphs[key] = (graph, (static_in, static_table, static_extra), static_out)
+        graph, (static_in, static_table, static_extra), static_out = entry
         static_in.copy_(stack)
         if table is not None:
             static_table.copy_(table)
+        for s, t in zip(static_extra, extra):
+            s.copy_(t)
         graph.replay()
         return static_out
 
     @torch.no_grad()
-    def inference_forward(self, frames):
+    def inference_forward(self, frames, rz=None):
         """One chunk of frames -> per-frame candidates (inference_forward :234-321 + the selection of
         idol.py:331-349): list over frames of dicts {indices, logits [n,K], boxes [n,4], embeds
         [n,C], masks [n,1,H/4,W/4]} for the queries that survive the score threshold and the
-        class-aware box NMS (0.9)."""
+        class-aware box NMS (0.9).
+        rz = (targets, layout) (`device_resize`): the frames are uint8 sources, resized to their targets by the ingest."""
         frames = list(frames)
         same = all(f.shape == frames[0].shape for f in frames)
-        if self.device_ingest and ingest.applies(frames, self.device):      # uint8 frames stay bytes until the kernel
+        if rz is not None:
+            targets, layout = rz
+            staged = resize.stage_sources(frames, targets, self.device, layout)
+            size = resize.padded_size(targets)
+            if self.graph_inference and self.device.type == "cuda":
+                sizes = [resize.frame_size(f, layout) for f in frames]
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(staged, None, size,
+                                                                                    (layout, sizes, targets))
+            else:
+                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(
+                    *self._resize_ingest(*staged, len(frames), *size, layout))
+        elif self.device_ingest and ingest.applies(frames, self.device):      # uint8 frames stay bytes until the kernel
             if self.graph_inference and self.device.type == "cuda" and same:
                 logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(
                     *ingest.stage_frames(frames, self.device), ingest.padded_size(frames))
@@ -554,7 +592,7 @@ class IDOL(nn.Module):
         frame_of = torch.from_numpy(np.concatenate([np.full(len(c), f) for f, c in enumerate(picks)])).to(self.device)
         query = torch.from_numpy(np.concatenate(picks)).to(self.device)
         sel_hs = hs_last[frame_of, query]
-        ih, iw = frames[0].shape[-2:]
+        ih, iw = frames[0].shape[-2:] if rz is None else rz[0][0]
         scale = scale_tensor([iw, ih], self.device)
         points = ref_last[frame_of, query, :2].sigmoid() * scale              # = inter_references[-2][..., :2]
         masks = dynamic_mask_head(feats, points.float(), self.detr.controller(sel_hs).float(),
@@ -571,10 +609,15 @@ class IDOL(nn.Module):
     @torch.no_grad()
     def inference_video(self, batched_inputs, rle=False):
         """idol.py:236-281: chunks of BATCH_INFER_LEN frames through the network, then the tracker."""
-        video = batched_inputs[0]["image"]
+        video, rz, src_size = batched_inputs[0]["image"], None, None
+        if self.device_resize and not self.training:      # -> (targets, layout), or frames for the usual path (resize.plan_video)
+            video, rz, src_size = resize.plan_video(list(video), batched_inputs[0].get("image_layout", "chw"),
+                                                    *self._test_size, self.device)
         per_frame = []
         for s in range(0, len(video), self.batch_infer_len):
-            per_frame.extend(self.inference_forward(video[s:s + self.batch_infer_len]))
+            e = s + self.batch_infer_len
+            per_frame.extend(self.inference_forward(video[s:e]) if rz is None else
+                             self.inference_forward(video[s:e], (rz[0][s:e], rz[1])))
         args = dict(init_score_thr=0.2, obj_score_thr=0.1, nms_thr_pre=self.nms_pre, nms_thr_post=0.05,
                     addnew_score_thr=self.add_new_score, memo_tracklet_frames=10, memo_momentum=0.8,
                     long_match=self.inference_tw, frame_weight=(self.inference_tw | self.inference_fw),
@@ -582,8 +625,9 @@ class IDOL(nn.Module):
         most = max((len(fr["indices"]) for fr in per_frame), default=0)
         on_device = self.device.type == "cuda" and DeviceTracker.supports(memory_len=self.memory_len, max_dets=most)
         tracker = (DeviceTracker if on_device else IDOL_Tracker)(**args)
-        ih, iw = video[0].shape[-2:]
-        oh, ow = batched_inputs[0].get("height", ih), batched_inputs[0].get("width", iw)
+        ih, iw = video[0].shape[-2:] if rz is None else rz[0][0]      # the size the network sees: with `device_resize` the target
+        sh, sw = (ih, iw) if src_size is None else src_size
+        oh, ow = batched_inputs[0].get("height", sh), batched_inputs[0].get("width", sw)
         return self.associate(per_frame, tracker, (oh, ow), (ih, iw), host_factory=lambda: IDOL_Tracker(**args), rle=rle)
 
     @staticmethod

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
-from ..ops import ingest
+from ..ops import ingest, resize
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
@@ -419,6 +419,10 @@ class SeqFormer(nn.Module):
         # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
         self.device_ingest = False
         self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
+        # eval mode, uint8 frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel that
+        # also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
+        self.device_resize = False
+        self._test_size = (int(getattr(cfg.INPUT, "MIN_SIZE_TEST", 360)), int(getattr(cfg.INPUT, "MAX_SIZE_TEST", 1333)))
         self._graphs = {}
         self._train_trunks = {}
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
@@ -451,6 +455,20 @@ class SeqFormer(nn.Module):
                 and torch.is_grad_enabled() and pixels.is_cuda)
         x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
         return x, mask, table
+
+    def _resize_ingest(self, pixels, src_table, dst_table, coeffs, B, H, W, layout):
+        """staged uint8 SOURCE frames -> (x, mask, table) of the frames resized to the targets in dst_table: one launch
+        (eval mode only: never channels-last); dst_table is the geometry `_features` hands to the level launch"""
+        x, mask = resize.resize_ingest_frames(pixels, src_table, dst_table, coeffs, B, H, W, *self._pixel_stats,
+                                              channels_last=False, layout=layout)
+        return x, mask, dst_table
+
+    def _plan_resize(self, video, frames):
+        """`device_resize`: -> (frames, (targets, layout) or None, the first source frame's size or None); see
+        `resize.plan_video`.  Off, or in training mode: the frames untouched."""
+        if not self.device_resize or self.training:
+            return frames, None, None
+        return resize.plan_video(frames, video.get("image_layout", "chw"), *self._test_size, self.device)
 
     def _features(self, x, mask, table=None):
         """table: the frames' geometry on the device when x, mask came from `_ingest`: the level masks and positions are
@@ -630,6 +648,10 @@ class SeqFormer(nn.Module):
         """`_clip_trunk` from staged uint8 frames (`device_ingest`): T frames padded to H x W"""
         return self._clip_trunk_tail(*self._ingest(pixels, table, T, H, W))
 
+    def _clip_trunk_resized(self, pixels, src_table, dst_table, coeffs, T, H, W, layout):
+        """`_clip_trunk` from staged uint8 source frames (`device_resize`): T frames resized, then padded to H x W"""
+        return self._clip_trunk_tail(*self._resize_ingest(pixels, src_table, dst_table, coeffs, T, H, W, layout))
+
     def _clip_trunk_tail(self, x, mask, table=None):
         srcs, masks, poss = self._features(x, mask, table)
         d = self.detr.detr
@@ -638,14 +660,23 @@ class SeqFormer(nn.Module):
         ref = inverse_sigmoid(init_ref if last == 0 else inter_refs[last - 1])
         return d.class_embed[last](hs[last]), ref, hs[last], self._mask_features(srcs, memory)
 
-    def _clip_trunk_graphed(self, stack, table=None, size=None):
+    def _clip_trunk_graphed(self, stack, table=None, size=None, resized=None):
         """`_clip_trunk` replayed from a hipGraph captured per (T, h, w) and input dtype: the ~1 500 launches of
         backbone + 6+6 transformer layers + mask-feature convs become one graph launch
         (SURVEY section 8(f) rank 2).  Outputs live in the graph's static buffers until the next call.
         With `table` (`device_ingest`): `stack` is the staged uint8 buffer of T frames padded to size = (H, W); buffer and
         table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are inside, and
-        a replay reads the frames' sizes from the table."""
-        if table is None:
+        a replay reads the frames' sizes from the table.
+        With `resized` = (layout, source sizes, targets) (`device_resize`): `stack` is the four tensors of
+        `resize.stage_sources`, all static inputs; the coefficients' layout follows the sizes, so the key holds the source
+        and target sizes as well."""
+        if resized is not None:
+            layout, sizes, targets = resized
+            inputs = tuple(stack)
+            stack = inputs[0]
+            key = ("resize", tuple(stack.shape), layout, tuple(sizes), tuple(targets)) + tuple(size)
+            fn = lambda p, s, d, c: self._clip_trunk_resized(p, s, d, c, s.shape[0], *size, layout)      # noqa: E731
+        elif table is None:
             key, inputs, fn = tuple(stack.shape), (stack,), self._clip_trunk
         else:
             key = (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
@@ -671,14 +702,24 @@ class SeqFormer(nn.Module):
         graph.replay()
         return static_out
 
-    def _top_instances(self, frames):
+    def _top_instances(self, frames, rz=None):
         """Frames of one clip (any length; the reference sets `num_frames` to it, seqformer.py:231,249)
         -> class probabilities [10, K] of the 10 best queries and their mask logits
-        [10, T, H/4, W/4] at a quarter of the padded input size (`inference_clip`, :302-326)."""
+        [10, T, H/4, W/4] at a quarter of the padded input size (`inference_clip`, :302-326).
+        rz = (targets, layout) (`device_resize`): the frames are uint8 sources, resized to their targets by the ingest."""
         T = len(frames)
         keep, self.num_frames = self.num_frames, T
         try:
-            if frames[0].dtype == torch.uint8 and all(f.shape == frames[0].shape for f in frames):      # `device_ingest`
+            if rz is not None:
+                targets, layout = rz
+                staged = resize.stage_sources(frames, targets, self.device, layout)
+                size = resize.padded_size(targets)
+                if self.graph_inference and staged[0].is_cuda:
+                    sizes = [resize.frame_size(f, layout) for f in frames]
+                    logits, ref_last, hs_last, feats = self._clip_trunk_graphed(staged, None, size, (layout, sizes, targets))
+                else:
+                    logits, ref_last, hs_last, feats = self._clip_trunk_resized(*staged, T, *size, layout)
+            elif frames[0].dtype == torch.uint8 and all(f.shape == frames[0].shape for f in frames):      # `device_ingest`
                 pixels, table = ingest.stage_frames(frames, self.device)
                 size = ingest.padded_size(frames)
                 if self.graph_inference and pixels.is_cuda:
@@ -694,7 +735,7 @@ class SeqFormer(nn.Module):
                 logits, ref_last, hs_last, feats = logits_all[-1], refs[-1], hs[-1], self._mask_features(srcs, memory)
         finally:
             self.num_frames = keep
-        ih, iw = frames[0].shape[-2:]                                         # size fed to the network
+        ih, iw = frames[0].shape[-2:] if rz is None else rz[0][0]             # size fed to the network
         prob = logits[0].sigmoid()                                            # [Q, classes]
         query = prob.max(1)[0].topk(min(10, prob.shape[0]))[1]
         params = self.detr.controller(hs_last[0, query])                     # [10, 169]
@@ -744,7 +785,7 @@ class SeqFormer(nn.Module):
         the device (`_report(rle=True)`) instead of copied to the host as bool masks."""
         return ytvis_records(batched_inputs, self.inference(batched_inputs, rle=True))
 
-    def _linked_clips(self, frames, on_device):
+    def _linked_clips(self, frames, on_device, rz=None):
         """CLIP_MATCHING: the video's overlapping clips, linked into tracks -> (class probabilities [N, K], mask logits
         [N, L, H/4, W/4]).  `on_device`: through `DeviceVideos`, whose per-clip call copies nothing to the host (and
         needs neither `prob.max(-1)` nor the sigmoid copy a `Clips` object makes)."""
@@ -759,7 +800,9 @@ class SeqFormer(nn.Module):
             if last:
                 break
         for idx in clips:
-            prob, mask_logits = self._top_instances([frames[i] for i in idx])
+            clip = [frames[i] for i in idx]
+            prob, mask_logits = (self._top_instances(clip) if rz is None else
+                                 self._top_instances(clip, ([rz[0][i] for i in idx], rz[1])))
             if merged is None and on_device:      # the clip count bounds the tracks the state needs room for
                 merged = DeviceVideos(self.clip_length, n_frames, self.num_classes, mask_logits.shape[-2:], self.device,
                                       max_instances=prob.shape[0], num_clips=len(clips))
@@ -782,20 +825,21 @@ class SeqFormer(nn.Module):
         every CLIP_STRIDE, linked by mask sIoU (vnext_amd/models/clip_matching.py), tracks averaged."""
         assert len(batched_inputs) == 1
         video = batched_inputs[0]
-        frames = list(video["image"])
-        if not (self.device_ingest and ingest.applies(frames, self.device)):      # uint8 frames stay bytes until the kernel
+        frames, rz, src_size = self._plan_resize(video, list(video["image"]))
+        if rz is None and not (self.device_ingest and ingest.applies(frames, self.device)):      # uint8 frames stay bytes until the kernel
             frames = [f.to(self.device, torch.float32) for f in frames]
-        ih, iw = frames[0].shape[-2:]
-        out_size = (video.get("height", ih), video.get("width", iw))
+        ih, iw = frames[0].shape[-2:] if rz is None else rz[0][0]      # the size the network sees: with `device_resize` the target
+        sh, sw = (ih, iw) if src_size is None else src_size
+        out_size = (video.get("height", sh), video.get("width", sw))
         if not self.clip_matching:
-            prob, mask_logits = self._top_instances(frames)
+            prob, mask_logits = self._top_instances(frames) if rz is None else self._top_instances(frames, rz)
             return self._report(prob, mask_logits, (ih, iw), out_size, rle)
         if self.device_clip_matching and (frames[0].is_cuda or (frames[0].dtype == torch.uint8 and self.device.type == "cuda")):
             from ..ops.clip_link import ClipLinkUnsupported
             try:
-                cls, mask_logits = self._linked_clips(frames, on_device=True)
+                cls, mask_logits = self._linked_clips(frames, on_device=True, rz=rz)
             except ClipLinkUnsupported:      # a clip beyond the kernels' limits, or more tracks than the state holds
-                cls, mask_logits = self._linked_clips(frames, on_device=False)
+                cls, mask_logits = self._linked_clips(frames, on_device=False, rz=rz)
         else:
-            cls, mask_logits = self._linked_clips(frames, on_device=False)
+            cls, mask_logits = self._linked_clips(frames, on_device=False, rz=rz)
         return self._report(cls, mask_logits, (ih, iw), out_size, rle)

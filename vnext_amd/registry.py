@@ -81,7 +81,7 @@ def get_seqformer_cfg(**overrides):
                                 HIDDEN_DIM=256, NUM_OBJECT_QUERIES=300, DEC_N_POINTS=4, ENC_N_POINTS=4,
                                 NUM_FEATURE_LEVELS=4, MERGE_ON_CPU=True, MULTI_CLS_ON=True,
                                 APPLY_CLS_THRES=0.05, CLIP_MATCHING=False, CLIP_LENGTH=5, CLIP_STRIDE=1)),
-        INPUT=_ns(SAMPLING_FRAME_NUM=5),
+        INPUT=_ns(SAMPLING_FRAME_NUM=5, MIN_SIZE_TEST=360, MAX_SIZE_TEST=1333),      # configs/base_ytvis.yaml; D2's default maximum
         SOLVER=_ns(OPTIMIZER="ADAMW", BACKBONE_MULTIPLIER=0.1, BASE_LR=2e-4, WEIGHT_DECAY=1e-4),
         FIND_UNUSED_PARAMETERS=True,
     )
@@ -109,7 +109,7 @@ def get_idol_cfg(**overrides):
                            APPLY_CLS_THRES=0.05, TEMPORAL_SCORE_TYPE="mean", INFERENCE_SELECT_THRES=0.1,
                            NMS_PRE=0.5, ADD_NEW_SCORE=0.2, INFERENCE_FW=True, INFERENCE_TW=True, MEMORY_LEN=3,
                            BATCH_INFER_LEN=10)),
-        INPUT=_ns(SAMPLING_FRAME_NUM=2, COCO_PRETRAIN=False),
+        INPUT=_ns(SAMPLING_FRAME_NUM=2, COCO_PRETRAIN=False, MIN_SIZE_TEST=480, MAX_SIZE_TEST=1333),      # configs/ytvis19_r50.yaml; D2's default maximum
         DATASETS=_ns(TEST=("ytvis_2019_val",)),
         SOLVER=_ns(OPTIMIZER="ADAMW", BACKBONE_MULTIPLIER=0.1, BASE_LR=1e-4, WEIGHT_DECAY=1e-4),
         FIND_UNUSED_PARAMETERS=True,

@@ -351,6 +351,20 @@ def enable_device_ingest(model, on: bool = True) -> None:
     model.device_ingest = bool(on)
 
 
+def enable_device_resize(model, on: bool = True) -> None:
+    """Opt in to the test-time resize on the device (`SeqFormer.device_resize` / `IDOL.device_resize`,
+    vnext_amd/ops/resize.py): in eval mode, uint8 frames handed to `inference` / `inference_video` / `ytvis_results` at
+    their DECODED size are resized to `ResizeShortestEdge(INPUT.MIN_SIZE_TEST, INPUT.MAX_SIZE_TEST)`'s target by the kernel
+    that also normalises, pads and masks them -- byte for byte what Pillow's bilinear resize on the host gives, so the
+    network sees the inputs it would have seen after the reference's test-time augmentation.  The input dict's optional
+    "image_layout" ("chw", the default, or "hwc") names the frames' layout; "height" / "width" default to the source frame's
+    size.  A video whose frames are already at their target takes the path it takes without the switch; float frames and
+    training are unchanged.  Raises for a model without the switch."""
+    if not hasattr(model, "device_resize"):
+        raise ValueError("enable_device_resize: %s has no device_resize switch" % type(model).__name__)
+    model.device_resize = bool(on)
+
+
 def enable_fused_mask_loss(model, on: bool = True) -> None:
     """Opt in to the fused mask losses (`criterion.fused_mask_loss`, vnext_amd/ops/mask_loss.py): focal + dice of the
     matched instances' mask logits in one kernel pass each way, the ground truth read in place at image resolution --
