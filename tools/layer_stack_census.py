@@ -11,7 +11,7 @@ from torch.profiler import ProfilerActivity, profile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import vnext_amd.models  # noqa: F401,E402
 from vnext_amd import tuning  # noqa: E402
-from vnext_amd.models.seqformer import sine_position  # noqa: E402
+from vnext_amd.ops.ingest import sine_position  # noqa: E402
 from vnext_amd.registry import build_model, get_seqformer_cfg  # noqa: E402
 
 dev = "cuda:0"

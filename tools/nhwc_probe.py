@@ -3,7 +3,7 @@ import os, sys, time, collections
 import torch
 from torch.profiler import ProfilerActivity, profile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from vnext_amd.models.seqformer import ResNet50Trunk
+from vnext_amd.models.resnet import ResNet50Trunk
 dev = "cuda:0"
 torch.manual_seed(0)
 for fmt in ("nchw", "nhwc"):

@@ -79,7 +79,7 @@ def level_sizes(H, W):
 
 def entry(model, frames, chunk, on):
     """CPU uint8 frames -> x, mask, level masks and positions of every chunk, on the device"""
-    from vnext_amd.models.seqformer import sine_position
+    from vnext_amd.ops.ingest import sine_position
     from vnext_amd.ops import ingest
     model.device_ingest = on
     out = []

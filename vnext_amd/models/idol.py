@@ -35,12 +35,14 @@ from ..heads import dynamic_mask_head, loss_reid
 from ..registry import META_ARCH_REGISTRY
 from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, reid_terms_fused, sample_aux_masks, select_pos_neg_masks
+from .frames import (TrainTrunk, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
+                     replay_captured, stage_chunk)
 from .idol_transformer import DeformableTransformer
-from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, ResNet50Trunk, build_backbone, scale_tensor, sine_position
+from .resnet import build_backbone
+from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, scale_tensor
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
 from ..ops.det_select import DetSelectUnsupported, class_aware_nms, select_detections, select_detections_host  # noqa: F401 (class_aware_nms: the host NMS, re-exported)
-from ..ops import ingest, resize
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import rle_encode, ytvis_records
 
@@ -57,37 +59,6 @@ class CondInstSegmIDOL(nn.Module):
             nn.init.zeros_(layer.bias)
         self.mask_head = MaskHeadSmallConv(hidden)
         self.reid_embed_head = MLP(hidden, hidden, hidden, 3)
-
-
-class _TrainTrunk(nn.Module):
-    """The shape-static, sync-free part of an IDOL training step -- normalise + pad, backbone, input projections, 6 + 6
-    transformer layers, the class / box heads of every decoder layer on the key frames, the stride-8 mask features, the
-    reference frames' class scores and the reid embeddings -- as one module, so that `torch.cuda.make_graphed_callables` can
-    capture its forward AND its backward into two hipGraphs (SeqFormer's twin:
-    seqformer.py:_TrainTrunk).  Shares the owner's parameters; not registered on the owner.
-
-    Why IDOL wants it more than SeqFormer: a key / reference pair is TWO frames -- the ~3 300 launches of a step carry 38 ms of
-    kernels (720p, bf16) and the step took 52-56 ms: the host could not issue them fast enough (round 6)."""
-
-    def __init__(self, owner):
-        super().__init__()
-        self.detr = owner.detr
-        object.__setattr__(self, "_owner", owner)
-
-    def forward(self, stack):
-        from ..ops.fused_norm import step_scope
-        with step_scope(stack.device):     # the fused dropout sites read a device-side step seed bumped HERE per replay
-            return self._forward(stack)
-
-    def _forward(self, stack):
-        o = self._owner
-        h, w = stack.shape[-2:]
-        H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-        x = stack.new_zeros(stack.shape[0], 3, H, W)
-        x[:, :, :h, :w] = (stack - o.pixel_mean) / o.pixel_std
-        mask = torch.ones(stack.shape[0], H, W, dtype=torch.bool, device=stack.device)
-        mask[:, :h, :w] = False
-        return o._train_trunk(x, mask)
 
 
 @META_ARCH_REGISTRY.register()
@@ -138,13 +109,10 @@ class IDOL(nn.Module):
         # uint8 frames are uploaded as bytes and normalised, padded and masked by one kernel; the level masks and positions
         # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
         self.device_ingest = False
-        self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
         # eval mode, uint8 video frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel
         # that also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
         self.device_resize = False
-        self._test_size = (int(getattr(cfg.INPUT, "MIN_SIZE_TEST", 480)), int(getattr(cfg.INPUT, "MAX_SIZE_TEST", 1333)))
-        self._graphs = {}
-        self._train_trunks = {}
+        self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 480)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
         self.to(self.device)
@@ -153,52 +121,18 @@ class IDOL(nn.Module):
     def _preprocess(self, frames):
         """normalise + pad to a multiple of 32 (idol.py:473-482, util/misc.py nested tensor) -> (x, mask); with
         `device_ingest` and uint8 frames -> (x, mask, table) from the ingest kernel (`_encode_decode` takes the table)."""
-        frames = list(frames)
-        if self.device_ingest and ingest.applies(frames, self.device):
-            return self._ingest(*ingest.stage_frames(frames, self.device), len(frames), *ingest.padded_size(frames))
-        frames =[(f.to(self.device, torch.float32) - self.pixel_mean) / self.pixel_std for f in frames]
-        H = (max(f.shape[-2] for f in frames) + 31) // 32 * 32
-        W = (max(f.shape[-1] for f in frames) + 31) // 32 * 32
-        x = frames[0].new_zeros(len(frames), 3, H, W)
-        mask = torch.ones(len(frames), H, W, dtype=torch.bool, device=self.device)
-        for i, f in enumerate(frames):
-            x[i, :, :f.shape[-2], :f.shape[-1]] = f
-            mask[i, :f.shape[-2], :f.shape[-1]] = False
-        return x, mask
-
-    def _ingest(self, pixels, table, B, H, W):
-        """staged uint8 frames -> (x, mask, table): one launch; channels-last exactly where the ResNet trunk would convert"""
-        from . import seqformer      # (CHANNELS_LAST is set after import: read the module's attribute)
-        d = self.detr.detr
-        nhwc = (seqformer.CHANNELS_LAST and isinstance(d.backbone, ResNet50Trunk) and d.backbone.training
-                and torch.is_grad_enabled() and pixels.is_cuda)
-        x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
-        return x, mask, table
-
-    def _resize_ingest(self, pixels, src_table, dst_table, coeffs, B, H, W, layout):
-        """staged uint8 SOURCE frames -> (x, mask, table) of the frames resized to the targets in dst_table: one launch
-        (eval mode only: never channels-last); dst_table is the geometry `_encode_decode` hands to the level launch"""
-        x, mask = resize.resize_ingest_frames(pixels, src_table, dst_table, coeffs, B, H, W, *self._pixel_stats,
-                                              channels_last=False, layout=layout)
-        return x, mask, dst_table
+        return preprocess(list(frames), *front_end(self))
 
     def _encode_decode(self, x, mask, table=None):
         """-> srcs, hs [Ld, N, Q, C], memory [N, S, C], per-layer pre-sigmoid references, the refined references, and the box
         predictions of the decoder's refinement loop (what _box_heads would compute again; None if it used other heads).
-        table: the frames' geometry on the device when x, mask came from `_ingest`: the level masks and positions are then one
-        launch of the ingest op"""
+        table: the frames' geometry on the device when x, mask came from the ingest kernel (`level_inputs`)"""
         d = self.detr.detr
         feats = d.backbone(x)
         srcs = [d.input_proj[l](f) for l, f in enumerate(feats)]
         for l in range(len(feats), d.num_feature_levels):
             srcs.append(d.input_proj[l](feats[-1] if l == len(feats) else srcs[-1]))
-        if table is not None:
-            masks, poss = ingest.level_constants(table, x.shape[0], x.shape[-2], x.shape[-1],
-                                                 [s.shape[-2:] for s in srcs], srcs[0].shape[1] // 2)
-            poss = [p.to(s.dtype) for p, s in zip(poss, srcs)]
-        else:
-            masks = [F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0] for s in srcs]
-            poss = [sine_position(mk, s.shape[1] // 2).to(s.dtype) for s, mk in zip(srcs, masks)]
+        masks, poss = level_inputs(srcs, mask, table)
         hs, memory, init_ref, inter_refs, _, inter_boxes, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
         refs = [inverse_sigmoid(init_ref if l == 0 else inter_refs[l - 1]) for l in range(hs.shape[0])]
         if d.transformer.decoder.bbox_embed is not d.bbox_embed:
@@ -253,8 +187,7 @@ class IDOL(nn.Module):
         (`torch.cuda.make_graphed_callables`: eager warm-up iterations on a side stream, then capture).  Under torch.autocast
         the capture runs with autocast's weight cache OFF: a cast cached before the capture would be a tensor outside the
         graph's memory pool."""
-        from .seqformer import graphed_callable
-        return graphed_callable(self._train_trunks, lambda: _TrainTrunk(self).train(), stack)
+        return graphed_callable(self._train_trunks, lambda: TrainTrunk(self).train(), stack)
 
     # ---- training -----------------------------------------------------------------------------
     def prepare_targets(self, batched_inputs):
@@ -376,9 +309,7 @@ class IDOL(nn.Module):
     @torch.no_grad()
     def _coco_trunk(self, batched_inputs):
         """-> logits, boxes, a `masks_of(image, queries)` callable (None with MASK_ON false), image sizes, output sizes"""
-        images = [x["image"] for x in batched_inputs]
-        if not (self.device_ingest and ingest.applies(images, self.device)):      # uint8 images stay bytes until the kernel
-            images = [im.to(self.device, torch.float32) for im in images]
+        images = [x["image"] for x in batched_inputs]      # (`_preprocess` uploads them: as floats, or as bytes for the kernel)
         image_sizes = [tuple(int(v) for v in im.shape[-2:]) for im in images]
         out_sizes = [(int(x.get("height", s[0])), int(x.get("width", s[1]))) for x, s in zip(batched_inputs, image_sizes)]
         logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(images))
@@ -500,62 +431,6 @@ class IDOL(nn.Module):
         logits, boxes = self._box_heads(hs, refs, [last], inter_boxes)
         return logits[0], boxes[0], hs[last], refs[last], self._mask_features(srcs, memory)
 
-    def _chunk_trunk_graphed(self, stack, table=None, size=None, resized=None):
-        """`_chunk_trunk` of same-sized frames replayed from a hipGraph captured per chunk shape and input dtype
-        (a video is chunks of BATCH_INFER_LEN frames + one shorter tail: two graphs).
-        With `table` (`device_ingest`): `stack` is the staged uint8 buffer of the chunk's frames padded to size = (H, W);
-        buffer and table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are
-        inside, and a replay reads the frames' sizes from the table.
-        With `resized` = (layout, source sizes, targets) (`device_resize`): `stack` is the four tensors of
-        `resize.stage_sources`, all static inputs; the coefficients' layout follows the sizes, so the key holds the source
-        and target sizes as well."""
-        extra = ()
-        if resized is not None:
-            layout, sizes, targets = resized
-            stack, table, *extra = stack
-            key = ("resize", tuple(stack.shape), layout, tuple(sizes), tuple(targets)) + tuple(size)
-        else:
-            key = tuple(stack.shape) if table is None else (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = stack.clone()
-            static_table = None if table is None else table.clone()
-            static_extra = tuple(t.clone() for t in extra)
-
-            def run():
-                if resized is not None:
-                    return self._chunk_trunk(*self._resize_ingest(static_in, static_table, *static_extra,
-                                                                  static_table.shape[0], *size, layout))
-                if static_table is not None:
-                    return self._chunk_trunk(*self._ingest(static_in, static_table, static_table.shape[0], *size))
-                h, w = static_in.shape[-2:]
-                H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-                x = static_in.new_zeros(static_in.shape[0], 3, H, W)
-                x[:, :, :h, :w] = (static_in - self.pixel_mean) / self.pixel_std
-                mask = torch.ones(static_in.shape[0], H, W, dtype=torch.bool, device=static_in.device)
-                mask[:, :h, :w] = False
-                return self._chunk_trunk(x, mask)
-            side = torch.cuda.Stream(device=stack.device)
-            side.wait_stream(torch.cuda.current_stream(stack.device))
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    run()
-            torch.cuda.current_stream(stack.device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = run()
-            if len(self._graphs) >= 4:
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = self._graphs[key] = (graph, (static_in, static_table, static_extra), static_out)
-        graph, (static_in, static_table, static_extra), static_out = entry
-        static_in.copy_(stack)
-        if table is not None:
-            static_table.copy_(table)
-        for s, t in zip(static_extra, extra):
-            s.copy_(t)
-        graph.replay()
-        return static_out
-
     @torch.no_grad()
     def inference_forward(self, frames, rz=None):
         """One chunk of frames -> per-frame candidates (inference_forward :234-321 + the selection of
@@ -564,30 +439,14 @@ class IDOL(nn.Module):
         class-aware box NMS (0.9).
         rz = (targets, layout) (`device_resize`): the frames are uint8 sources, resized to their targets by the ingest."""
         frames = list(frames)
-        same = all(f.shape == frames[0].shape for f in frames)
-        if rz is not None:
-            targets, layout = rz
-            staged = resize.stage_sources(frames, targets, self.device, layout)
-            size = resize.padded_size(targets)
-            if self.graph_inference and self.device.type == "cuda":
-                sizes = [resize.frame_size(f, layout) for f in frames]
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(staged, None, size,
-                                                                                    (layout, sizes, targets))
-            else:
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(
-                    *self._resize_ingest(*staged, len(frames), *size, layout))
-        elif self.device_ingest and ingest.applies(frames, self.device):      # uint8 frames stay bytes until the kernel
-            if self.graph_inference and self.device.type == "cuda" and same:
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(
-                    *ingest.stage_frames(frames, self.device), ingest.padded_size(frames))
-            else:
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
+        staged = stage_chunk(frames, rz, *front_end(self))
+        if staged is None:      # frames of different sizes: the eager, padded-batch path
+            logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
+        elif self.graph_inference and staged.tensors[0].is_cuda:      # one hipGraph per chunk shape and input kind
+            logits, boxes, hs_last, ref_last, feats = replay_captured(
+                self._graphs, staged.key, staged.tensors, lambda *t: self._chunk_trunk(*staged.to_net(*t)))
         else:
-            frames = [f.to(self.device, torch.float32) for f in frames]
-            if self.graph_inference and frames[0].is_cuda and same:
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk_graphed(torch.stack(frames))
-            else:
-                logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*self._preprocess(frames))
+            logits, boxes, hs_last, ref_last, feats = self._chunk_trunk(*staged.to_net(*staged.tensors))
         picks = self.select_candidates(logits, boxes)
         frame_of = torch.from_numpy(np.concatenate([np.full(len(c), f) for f, c in enumerate(picks)])).to(self.device)
         query = torch.from_numpy(np.concatenate(picks)).to(self.device)
@@ -609,10 +468,8 @@ class IDOL(nn.Module):
     @torch.no_grad()
     def inference_video(self, batched_inputs, rle=False):
         """idol.py:236-281: chunks of BATCH_INFER_LEN frames through the network, then the tracker."""
-        video, rz, src_size = batched_inputs[0]["image"], None, None
-        if self.device_resize and not self.training:      # -> (targets, layout), or frames for the usual path (resize.plan_video)
-            video, rz, src_size = resize.plan_video(list(video), batched_inputs[0].get("image_layout", "chw"),
-                                                    *self._test_size, self.device)
+        video, rz, src_size = plan_resize(self.device_resize and not self.training, batched_inputs[0], self._test_size,
+                                          self.device)
         per_frame = []
         for s in range(0, len(video), self.batch_infer_len):
             e = s + self.batch_infer_len

@@ -21,18 +21,20 @@ of scope is deliberately thin:
 from __future__ import annotations
 
 import math
-import os
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
-from ..ops import ingest, resize
+from ..ops.ingest import sine_position  # noqa: F401  (its home; importable from here by name, as the three below)
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from ..registry import META_ARCH_REGISTRY
+from .frames import (TrainTrunk, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
+                     replay_captured, stage_chunk, takes_bytes)
+from .resnet import FrozenBatchNorm2d, ResNet50Trunk, build_backbone, conv_bn  # noqa: F401
 from .seqformer_transformer import DeformableTransformer, inverse_sigmoid
 
 
@@ -50,220 +52,6 @@ def scale_tensor(values, device):
             _SCALES.clear()
         t = _SCALES[key] = torch.tensor(key[0], dtype=torch.float32, device=device)
     return t
-
-
-# TRAINING steps run the ResNet trunk in channels-last memory format on the GPU: MIOpen's fp32 convolutions of these shapes
-# are NHWC implicit-GEMM kernels in the backward either way, and given NCHW tensors it transposes in and out around each of
-# them (156 + 88 transpose / sub-tensor launches, ~2.2 ms of a 66 ms SeqFormer step on MI355X).  PyTorch only hands MIOpen an
-# NHWC problem when PYTORCH_MIOPEN_SUGGEST_NHWC is set.  Measured on one box (bench.py model legs, ms per step, NCHW -> this):
-# SeqFormer fp32 two clips 66.2 -> 64.3, one clip 52.4 -> 50.6, bf16 autocast 76.9 -> 74.3, IDOL bf16 pair 67.1 -> 65.8.
-# Inference keeps NCHW (forward-only NHWC is slower: SeqFormer 12.0 -> 12.9 ms per clip, IDOL 720p 185 -> 172 frames/s),
-# which is why the filters stay NCHW (channels-last filters select NHWC whatever the input is).  A training-only process can
-# set VNX_CHANNELS_LAST_WEIGHTS=1 to store the filters channels-last as well (no per-call filter conversion: IDOL pair
-# 65.8 -> 60.7 ms, bf16 autocast 74.3 -> 69.7; fp32 SeqFormer unchanged).
-# OFF unless the process asks for it: vnext_amd.train.enable_channels_last() sets the MIOpen variable and this switch
-# together (importing this module changes nothing process-wide; until round 4 it did both at import time).
-CHANNELS_LAST = False
-
-
-class FrozenBatchNorm2d(nn.Module):
-    """models/backbone.py:27-64: fixed statistics and affine parameters.  As a standalone module it
-    is `x * scale + shift`; inside the trunk below the two constants are folded into the preceding
-    convolution instead (`folded()`), which removes two full-resolution elementwise passes per
-    convolution from the forward and one from the backward."""
-
-    def __init__(self, n):
-        super().__init__()
-        self.register_buffer("weight", torch.ones(n))
-        self.register_buffer("bias", torch.zeros(n))
-        self.register_buffer("running_mean", torch.zeros(n))
-        self.register_buffer("running_var", torch.ones(n))
-        self._fold = None
-
-    def folded(self):
-        """(scale [C], shift [C]), recomputed only when a buffer changed (load_state_dict, .to())."""
-        key = tuple((t.data_ptr(), t._version) for t in (self.weight, self.bias, self.running_mean, self.running_var))
-        if self._fold is None or self._fold[0] != key:
-            with torch.no_grad():
-                scale = self.weight * (self.running_var + 1e-5).rsqrt()
-                self._fold = (key, scale, self.bias - self.running_mean * scale)
-        return self._fold[1], self._fold[2]
-
-    def expanded_scale(self, weight):
-        """the scale broadcast to the shape of the preceding convolution's filters (a cached constant: the
-        multi-tensor multiply of `fold_all` wants equal shapes)"""
-        scale, _ = self.folded()
-        cached = getattr(self, "_expanded", None)
-        if cached is None or cached[0] is not scale or cached[1].shape != weight.shape or cached[1].device != weight.device:
-            fmt = torch.channels_last if weight.dim() == 4 and weight.is_contiguous(memory_format=torch.channels_last) \
-                and not weight.is_contiguous() else torch.contiguous_format
-            cached = self._expanded = (scale, scale.reshape(-1, 1, 1, 1).expand_as(weight).contiguous(memory_format=fmt))
-        return cached[1]
-
-    def forward(self, x):
-        scale, shift = self.folded()
-        return x * scale.reshape(1, -1, 1, 1) + shift.reshape(1, -1, 1, 1)
-
-
-def conv_bn(x, conv, bn, folded_weight=None):
-    """bn(conv(x)) for a frozen bn: one convolution with scaled filters and the shift as its bias
-    (the filters stay trainable: the scaling is a differentiable [Cout,1,1,1] multiply on the weights).
-    `folded_weight`: the scaled filters -- or a (filters, shift) pair -- when the caller has folded all convolutions at
-    once (`fold_all`)."""
-    if isinstance(folded_weight, tuple):
-        folded_weight, shift = folded_weight
-    else:
-        scale, shift = bn.folded()
-        if folded_weight is None:
-            folded_weight = conv.weight * scale.reshape(-1, 1, 1, 1)
-    return F.conv2d(x, folded_weight, shift, conv.stride, conv.padding)
-
-
-class _FoldScales(torch.autograd.Function):
-    """weights[i] * scales[i] for a list of filters in one multi-tensor launch (and one in the backward)
-    instead of one small launch per convolution: 53 + 43 launches -> a handful per training step."""
-
-    @staticmethod
-    def forward(ctx, scales, out_dtype, *weights):
-        ctx.scales = scales
-        ctx.set_materialize_grads(False)
-        return tuple(_cast_all(torch._foreach_mul(list(weights), scales), out_dtype))
-
-    @staticmethod
-    def backward(ctx, *grads):
-        live = [i for i, g in enumerate(grads) if g is not None]
-        out = [None] * len(grads)
-        if live:
-            gs = _cast_all([grads[i] for i in live], torch.float32)      # (16-bit under autocast: one multi-tensor cast back)
-            for i, g in zip(live, torch._foreach_mul(gs, [ctx.scales[i] for i in live])):
-                out[i] = g
-        return (None, None, *out)
-
-
-def _cast_all(tensors, dtype):
-    """the list in `dtype` with ONE multi-tensor launch (torch._foreach_copy_ converts), itself when it already is"""
-    if dtype is None or not tensors or all(t.dtype == dtype for t in tensors):
-        return list(tensors)
-    out = [torch.empty_like(t, dtype=dtype) for t in tensors]
-    torch._foreach_copy_(out, list(tensors))
-    return out
-
-
-def fold_all(pairs):
-    """[(conv, frozen bn)] -> {conv: scaled filters}.  Trainable filters go through `_FoldScales`
-    (differentiable), frozen ones through a plain multi-tensor multiply.  Under torch.autocast the filters come out in the
-    autocast dtype (round 6): autocast would otherwise cast every convolution's filters at its call -- 53 launches forward and
-    53 casts of their gradients backward per step where two multi-tensor launches do."""
-    out = {}
-    adt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() and pairs and pairs[0][0].weight.is_cuda else None
-    for trainable in (True, False):
-        group = [(c, b) for c, b in pairs if c.weight.requires_grad == trainable]
-        if not group:
-            continue
-        scales = [b.expanded_scale(c.weight) for c, b in group]
-        weights = [c.weight for c, _ in group]
-        if trainable and torch.is_grad_enabled():
-            scaled = _FoldScales.apply(scales, adt, *weights)
-        else:
-            with torch.no_grad():
-                scaled = _cast_all(torch._foreach_mul(weights, scales), adt)
-        out.update({c: w for (c, _), w in zip(group, scaled)})
-    if adt is not None:      # the shifts (the convolutions' biases) too: one multi-tensor cast instead of one per convolution
-        convs = [c for c, _ in pairs]
-        with torch.no_grad():
-            shifts = _cast_all([b.folded()[1] for _, b in pairs], adt)
-        out = {c: (out[c], sh) for c, sh in zip(convs, shifts)}
-    return out
-
-
-class _Bottleneck(nn.Module):
-    def __init__(self, cin, mid, cout, stride):
-        super().__init__()
-        self.conv1 = nn.Conv2d(cin, mid, 1, bias=False); self.bn1 = FrozenBatchNorm2d(mid)
-        self.conv2 = nn.Conv2d(mid, mid, 3, stride, 1, bias=False); self.bn2 = FrozenBatchNorm2d(mid)
-        self.conv3 = nn.Conv2d(mid, cout, 1, bias=False); self.bn3 = FrozenBatchNorm2d(cout)
-        self.down = None
-        if stride != 1 or cin != cout:
-            self.down = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), FrozenBatchNorm2d(cout))
-
-    def pairs(self):
-        out = [(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
-        return out + ([(self.down[0], self.down[1])] if self.down is not None else [])
-
-    def forward(self, x, folded=None):
-        w = (lambda c: folded[c]) if folded is not None else (lambda c: None)
-        y = F.relu(conv_bn(x, self.conv1, self.bn1, w(self.conv1)))
-        y = F.relu(conv_bn(y, self.conv2, self.bn2, w(self.conv2)))
-        y = conv_bn(y, self.conv3, self.bn3, w(self.conv3))
-        return F.relu(y + (x if self.down is None else conv_bn(x, self.down[0], self.down[1], w(self.down[0]))))
-
-
-class ResNet50Trunk(nn.Module):
-    """res3/res4/res5 features (strides 8/16/32, 512/1024/2048 channels)."""
-    strides = (8, 16, 32)
-    num_channels = (512, 1024, 2048)
-
-    def __init__(self):
-        super().__init__()
-        self.stem = nn.Sequential(nn.Conv2d(3, 64, 7, 2, 3, bias=False), FrozenBatchNorm2d(64), nn.ReLU(),
-                                  nn.MaxPool2d(3, 2, 1))
-        def stage(cin, mid, cout, n, stride):
-            return nn.Sequential(*[_Bottleneck(cin if i == 0 else cout, mid, cout, stride if i == 0 else 1)
-                                   for i in range(n)])
-        self.res2 = stage(64, 64, 256, 3, 1)
-        self.res3 = stage(256, 128, 512, 4, 2)
-        self.res4 = stage(512, 256, 1024, 6, 2)
-        self.res5 = stage(1024, 512, 2048, 3, 2)
-        if CHANNELS_LAST and os.environ.get("VNX_CHANNELS_LAST_WEIGHTS", "0") == "1":
-            self.to(memory_format=torch.channels_last)
-
-    def freeze(self, freeze_at=2):
-        """detectron2's MODEL.BACKBONE.FREEZE_AT (default 2, kept by the reference's configs): the
-        stem and res2 are not trained, so the backward stops at res3's input."""
-        stages = [self.stem, self.res2, self.res3, self.res4, self.res5]
-        for stage in stages[:freeze_at]:
-            for p in stage.parameters():
-                p.requires_grad_(False)
-        return self
-
-    def forward(self, x):
-        if CHANNELS_LAST and self.training and torch.is_grad_enabled():
-            x = x.contiguous(memory_format=torch.channels_last)
-        blocks = [b for stage in (self.res2, self.res3, self.res4, self.res5) for b in stage]
-        folded = fold_all([(self.stem[0], self.stem[1])] + [p for b in blocks for p in b.pairs()])
-        x = F.max_pool2d(F.relu(conv_bn(x, self.stem[0], self.stem[1], folded[self.stem[0]])), 3, 2, 1)
-        outs = []
-        for stage in (self.res2, self.res3, self.res4, self.res5):
-            for b in stage:
-                x = b(x, folded)
-            outs.append(x)
-        return outs[1:]
-
-
-def build_backbone(cfg):
-    """MODEL.BACKBONE.NAME "D2SwinTransformer": the Swin backbone (models/swin.py); otherwise the ResNet-50 trunk with
-    its stem and res2 frozen."""
-    from .swin import D2SwinTransformer, is_swin
-    if is_swin(cfg):
-        return D2SwinTransformer(cfg)
-    return ResNet50Trunk().freeze(2)
-
-
-def sine_position(mask, num_pos_feats=128, temperature=10000):
-    """models/position_encoding.py:35-55 with normalize=True."""
-    not_mask = ~mask
-    y_embed = not_mask.cumsum(1, dtype=torch.float32)
-    x_embed = not_mask.cumsum(2, dtype=torch.float32)
-    eps, scale = 1e-6, 2 * math.pi
-    y_embed = (y_embed - 0.5) / (y_embed[:, -1:, :] + eps) * scale
-    x_embed = (x_embed - 0.5) / (x_embed[:, :, -1:] + eps) * scale
-    dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=mask.device)
-    dim_t = temperature ** (2 * (dim_t // 2) / num_pos_feats)
-    pos_x = x_embed[:, :, :, None] / dim_t
-    pos_y = y_embed[:, :, :, None] / dim_t
-    pos_x = torch.stack((pos_x[..., 0::2].sin(), pos_x[..., 1::2].cos()), dim=4).flatten(3)
-    pos_y = torch.stack((pos_y[..., 0::2].sin(), pos_y[..., 1::2].cos()), dim=4).flatten(3)
-    return torch.cat((pos_y, pos_x), dim=3).permute(0, 3, 1, 2)
 
 
 class MLP(nn.Module):
@@ -331,56 +119,6 @@ class CondInstSegm(nn.Module):
         self.mask_head = MaskHeadSmallConv(hidden)
 
 
-class _TrainTrunk(nn.Module):
-    """The shape-static, sync-free part of a training step -- normalise + pad, backbone, input
-    projections, 6+6 transformer layers, class / box heads, mask-feature convs -- as one module, so
-    that `torch.cuda.make_graphed_callables` can capture its forward AND its backward into two
-    hipGraphs.  Shares the owner's parameters; not registered on the owner."""
-
-    def __init__(self, owner):
-        super().__init__()
-        self.detr = owner.detr
-        object.__setattr__(self, "_owner", owner)
-
-    def forward(self, stack):
-        from ..ops.fused_norm import step_scope
-        with step_scope(stack.device):     # the fused dropout sites read a device-side step seed bumped HERE per replay
-            return self._forward(stack)
-
-    def _forward(self, stack):
-        o = self._owner
-        h, w = stack.shape[-2:]
-        H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-        x = stack.new_zeros(stack.shape[0], 3, H, W)
-        x[:, :, :h, :w] = (stack - o.pixel_mean) / o.pixel_std
-        mask = torch.ones(stack.shape[0], H, W, dtype=torch.bool, device=stack.device)
-        mask[:, :h, :w] = False
-        srcs, masks, poss = o._features(x, mask)
-        d = self.detr.detr
-        hs, hs_box, memory, init_ref, inter_refs, inter_boxes, _, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
-        logits, boxes = o._heads(hs, hs_box, init_ref, inter_refs, inter_boxes)
-        return (hs, logits, boxes, inverse_sigmoid(init_ref), inverse_sigmoid(inter_refs),
-                o._mask_features(srcs, memory))
-
-
-def graphed_callable(cache, make_module, stack, keep=2):
-    """`make_module()(stack)` replayed from forward + backward hipGraphs captured per (input shape, autocast dtype); `cache`: the
-    owner's dict (at most `keep` entries).  Under torch.autocast the capture -- warm-up iterations included -- runs with
-    autocast's weight cache off: a weight cast cached BEFORE the capture is a tensor outside the graph's memory pool, and one
-    cached DURING it would be served, stale, to the eager code after it.  Replays run no Python of the module, so they need
-    nothing from the ambient autocast state."""
-    amp = torch.is_autocast_enabled() and stack.is_cuda
-    adt = torch.get_autocast_dtype("cuda") if amp else None
-    key = (tuple(stack.shape), adt)
-    fn = cache.get(key)
-    if fn is None:
-        if len(cache) >= keep:
-            cache.pop(next(iter(cache)))
-        with torch.autocast("cuda", dtype=adt, enabled=amp, cache_enabled=False):
-            fn = cache[key] = torch.cuda.make_graphed_callables(make_module(), (stack.clone(),), allow_unused_input=True)
-    return fn(stack)
-
-
 @META_ARCH_REGISTRY.register()
 class SeqFormer(nn.Module):
     def __init__(self, cfg):
@@ -418,13 +156,10 @@ class SeqFormer(nn.Module):
         # uint8 frames are uploaded as bytes and normalised, padded and masked by one kernel; the level masks and positions
         # come from one more (vnext_amd/ops/ingest.py; opt-in: train.enable_device_ingest).  Float frames: unchanged
         self.device_ingest = False
-        self._pixel_stats = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
         # eval mode, uint8 frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel that
         # also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
         self.device_resize = False
-        self._test_size = (int(getattr(cfg.INPUT, "MIN_SIZE_TEST", 360)), int(getattr(cfg.INPUT, "MAX_SIZE_TEST", 1333)))
-        self._graphs = {}
-        self._train_trunks = {}
+        self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 360)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
         self.to(self.device)
@@ -433,64 +168,20 @@ class SeqFormer(nn.Module):
     def _preprocess(self, batched_inputs):
         """normalise + pad to a multiple of 32 (seqformer.py:413-429, util/misc.py:298-302) -> (x, mask); with
         `device_ingest` and uint8 frames -> (x, mask, table) from the ingest kernel (`_features` takes the table)."""
-        frames = [f for clip in batched_inputs for f in clip["image"]]
-        if self.device_ingest and ingest.applies(frames, self.device):
-            return self._ingest(*ingest.stage_frames(frames, self.device), len(frames), *ingest.padded_size(frames))
-        frames = [f.to(self.device, torch.float32) for f in frames]
-        frames = [(f - self.pixel_mean) / self.pixel_std for f in frames]
-        H = max(f.shape[-2] for f in frames)
-        W = max(f.shape[-1] for f in frames)
-        H, W = (H + 31) // 32 * 32, (W + 31) // 32 * 32
-        x = frames[0].new_zeros(len(frames), 3, H, W)
-        mask = torch.ones(len(frames), H, W, dtype=torch.bool, device=self.device)
-        for i, f in enumerate(frames):
-            x[i, :, :f.shape[-2], :f.shape[-1]] = f
-            mask[i, :f.shape[-2], :f.shape[-1]] = False
-        return x, mask
-
-    def _ingest(self, pixels, table, B, H, W):
-        """staged uint8 frames -> (x, mask, table): one launch; channels-last exactly where the ResNet trunk would convert"""
-        d = self.detr.detr
-        nhwc = (CHANNELS_LAST and isinstance(d.backbone, ResNet50Trunk) and d.backbone.training
-                and torch.is_grad_enabled() and pixels.is_cuda)
-        x, mask = ingest.ingest_frames(pixels, table, B, H, W, *self._pixel_stats, channels_last=nhwc)
-        return x, mask, table
-
-    def _resize_ingest(self, pixels, src_table, dst_table, coeffs, B, H, W, layout):
-        """staged uint8 SOURCE frames -> (x, mask, table) of the frames resized to the targets in dst_table: one launch
-        (eval mode only: never channels-last); dst_table is the geometry `_features` hands to the level launch"""
-        x, mask = resize.resize_ingest_frames(pixels, src_table, dst_table, coeffs, B, H, W, *self._pixel_stats,
-                                              channels_last=False, layout=layout)
-        return x, mask, dst_table
-
-    def _plan_resize(self, video, frames):
-        """`device_resize`: -> (frames, (targets, layout) or None, the first source frame's size or None); see
-        `resize.plan_video`.  Off, or in training mode: the frames untouched."""
-        if not self.device_resize or self.training:
-            return frames, None, None
-        return resize.plan_video(frames, video.get("image_layout", "chw"), *self._test_size, self.device)
+        return preprocess([f for clip in batched_inputs for f in clip["image"]], *front_end(self))
 
     def _features(self, x, mask, table=None):
-        """table: the frames' geometry on the device when x, mask came from `_ingest`: the level masks and positions are
-        then one launch of the ingest op instead of ~20 small ones per level"""
+        """table: the frames' geometry on the device when x, mask came from the ingest kernel (`level_inputs`)"""
         d = self.detr.detr
         T = self.num_frames
         N = x.shape[0] // T
         feats = d.backbone(x)
-        srcs, masks, poss = [], [], []
+        srcs = []
         for l, f in enumerate(feats):
             srcs.append(d.input_proj[l](f))
         for l in range(len(feats), d.num_feature_levels):
             srcs.append(d.input_proj[l](feats[-1] if l == len(feats) else srcs[-1]))
-        if table is not None:
-            masks, poss = ingest.level_constants(table, x.shape[0], x.shape[-2], x.shape[-1],
-                                                 [s.shape[-2:] for s in srcs], srcs[0].shape[1] // 2)
-            poss = [p.to(s.dtype) for p, s in zip(poss, srcs)]
-        else:
-            for s in srcs:
-                mk = F.interpolate(mask[None].float(), size=s.shape[-2:]).to(torch.bool)[0]
-                masks.append(mk)
-                poss.append(sine_position(mk, s.shape[1] // 2).to(s.dtype))
+        masks, poss = level_inputs(srcs, mask, table)
         fold = lambda t: t.reshape(N, T, *t.shape[1:])  # noqa: E731
         return [fold(s) for s in srcs], [fold(mk) for mk in masks], [fold(p) for p in poss]
 
@@ -570,11 +261,21 @@ class SeqFormer(nn.Module):
             start += h * w
         return self.detr.mask_head(mem).float().contiguous()
 
+    def _train_trunk(self, x, mask):
+        """Padded frames -> what `losses` needs from the network, as a flat tuple of tensors: the shape-static, sync-free
+        part of a training step (`frames.TrainTrunk` captures it)."""
+        srcs, masks, poss = self._features(x, mask)
+        d = self.detr.detr
+        hs, hs_box, memory, init_ref, inter_refs, inter_boxes, _, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
+        logits, boxes = self._heads(hs, hs_box, init_ref, inter_refs, inter_boxes)
+        return (hs, logits, boxes, inverse_sigmoid(init_ref), inverse_sigmoid(inter_refs),
+                self._mask_features(srcs, memory))
+
     def _graphed_train_trunk(self, stack):
         """Forward + backward hipGraphs of the training trunk for this clip batch shape, captured
         on first use (3 eager warm-up iterations on a side stream, then capture -- what
         make_graphed_callables does)."""
-        return graphed_callable(self._train_trunks, lambda: _TrainTrunk(self).train(), stack)
+        return graphed_callable(self._train_trunks, lambda: TrainTrunk(self).train(), stack)
 
     def losses(self, batched_inputs):
         """CondInst_segm.forward (segmentation_condInst.py:69-207) + SetCriterion."""
@@ -630,77 +331,18 @@ class SeqFormer(nn.Module):
         return self.inference(batched_inputs)
 
     # ---- inference --------------------------------------------------------------------------
-    def _clip_trunk(self, stack):
-        """[T, 3, h, w] raw frames of ONE clip -> what `inference` needs from the network: class
+    def _clip_trunk_tail(self, x, mask, table=None):
+        """Padded frames of ONE clip -> what `inference` needs from the network: class
         logits and (pre-sigmoid) reference of the last decoder layer, its query states and the
         stride-8 mask features.  Shape-static and free of host synchronisation, so it can be
         captured into a hipGraph; boxes of the other layers are not computed (whole-video
         inference never reads them, seqformer.py:351-410)."""
-        h, w = stack.shape[-2:]
-        H, W = (h + 31) // 32 * 32, (w + 31) // 32 * 32
-        x = stack.new_zeros(stack.shape[0], 3, H, W)
-        x[:, :, :h, :w] = (stack - self.pixel_mean) / self.pixel_std
-        mask = torch.ones(stack.shape[0], H, W, dtype=torch.bool, device=stack.device)
-        mask[:, :h, :w] = False
-        return self._clip_trunk_tail(x, mask)
-
-    def _clip_trunk_bytes(self, pixels, table, T, H, W):
-        """`_clip_trunk` from staged uint8 frames (`device_ingest`): T frames padded to H x W"""
-        return self._clip_trunk_tail(*self._ingest(pixels, table, T, H, W))
-
-    def _clip_trunk_resized(self, pixels, src_table, dst_table, coeffs, T, H, W, layout):
-        """`_clip_trunk` from staged uint8 source frames (`device_resize`): T frames resized, then padded to H x W"""
-        return self._clip_trunk_tail(*self._resize_ingest(pixels, src_table, dst_table, coeffs, T, H, W, layout))
-
-    def _clip_trunk_tail(self, x, mask, table=None):
         srcs, masks, poss = self._features(x, mask, table)
         d = self.detr.detr
         hs, _, memory, init_ref, inter_refs, _, _, _ = d.transformer(srcs, masks, poss, d.query_embed.weight)
         last = hs.shape[0] - 1
         ref = inverse_sigmoid(init_ref if last == 0 else inter_refs[last - 1])
         return d.class_embed[last](hs[last]), ref, hs[last], self._mask_features(srcs, memory)
-
-    def _clip_trunk_graphed(self, stack, table=None, size=None, resized=None):
-        """`_clip_trunk` replayed from a hipGraph captured per (T, h, w) and input dtype: the ~1 500 launches of
-        backbone + 6+6 transformer layers + mask-feature convs become one graph launch
-        (SURVEY section 8(f) rank 2).  Outputs live in the graph's static buffers until the next call.
-        With `table` (`device_ingest`): `stack` is the staged uint8 buffer of T frames padded to size = (H, W); buffer and
-        table are the graph's static inputs -- the upload stays outside the capture, the ingest launches are inside, and
-        a replay reads the frames' sizes from the table.
-        With `resized` = (layout, source sizes, targets) (`device_resize`): `stack` is the four tensors of
-        `resize.stage_sources`, all static inputs; the coefficients' layout follows the sizes, so the key holds the source
-        and target sizes as well."""
-        if resized is not None:
-            layout, sizes, targets = resized
-            inputs = tuple(stack)
-            stack = inputs[0]
-            key = ("resize", tuple(stack.shape), layout, tuple(sizes), tuple(targets)) + tuple(size)
-            fn = lambda p, s, d, c: self._clip_trunk_resized(p, s, d, c, s.shape[0], *size, layout)      # noqa: E731
-        elif table is None:
-            key, inputs, fn = tuple(stack.shape), (stack,), self._clip_trunk
-        else:
-            key = (tuple(stack.shape), stack.dtype, table.shape[0]) + tuple(size)
-            inputs, fn = (stack, table), lambda p, t: self._clip_trunk_bytes(p, t, t.shape[0], *size)
-        entry = self._graphs.get(key)
-        if entry is None:
-            static_in = tuple(t.clone() for t in inputs)
-            side = torch.cuda.Stream(device=stack.device)
-            side.wait_stream(torch.cuda.current_stream(stack.device))
-            with torch.cuda.stream(side):           # warm-up outside capture: lazy inits, cached level tensors
-                for _ in range(2):
-                    fn(*static_in)
-            torch.cuda.current_stream(stack.device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                static_out = fn(*static_in)
-            if len(self._graphs) >= 4:              # a few resolutions at most; drop the oldest
-                self._graphs.pop(next(iter(self._graphs)))
-            entry = self._graphs[key] = (graph, static_in, static_out)
-        graph, static_in, static_out = entry
-        for s, t in zip(static_in, inputs):
-            s.copy_(t)
-        graph.replay()
-        return static_out
 
     def _top_instances(self, frames, rz=None):
         """Frames of one clip (any length; the reference sets `num_frames` to it, seqformer.py:231,249)
@@ -710,29 +352,15 @@ class SeqFormer(nn.Module):
         T = len(frames)
         keep, self.num_frames = self.num_frames, T
         try:
-            if rz is not None:
-                targets, layout = rz
-                staged = resize.stage_sources(frames, targets, self.device, layout)
-                size = resize.padded_size(targets)
-                if self.graph_inference and staged[0].is_cuda:
-                    sizes = [resize.frame_size(f, layout) for f in frames]
-                    logits, ref_last, hs_last, feats = self._clip_trunk_graphed(staged, None, size, (layout, sizes, targets))
-                else:
-                    logits, ref_last, hs_last, feats = self._clip_trunk_resized(*staged, T, *size, layout)
-            elif frames[0].dtype == torch.uint8 and all(f.shape == frames[0].shape for f in frames):      # `device_ingest`
-                pixels, table = ingest.stage_frames(frames, self.device)
-                size = ingest.padded_size(frames)
-                if self.graph_inference and pixels.is_cuda:
-                    logits, ref_last, hs_last, feats = self._clip_trunk_graphed(pixels, table, size)
-                else:
-                    logits, ref_last, hs_last, feats = self._clip_trunk_bytes(pixels, table, T, *size)
-            elif all(f.shape == frames[0].shape for f in frames):
-                stack = torch.stack(frames)
-                trunk = self._clip_trunk_graphed if (self.graph_inference and stack.is_cuda) else self._clip_trunk
-                logits, ref_last, hs_last, feats = trunk(stack)
-            else:   # frames of different sizes: the general (eager, padded-batch) path
+            staged = stage_chunk(frames, rz, *front_end(self))
+            if staged is None:      # frames of different sizes: the general (eager, padded-batch) path
                 x, srcs, hs, memory, logits_all, _, refs = self._run([{"image": frames}], want_refs=True)
                 logits, ref_last, hs_last, feats = logits_all[-1], refs[-1], hs[-1], self._mask_features(srcs, memory)
+            elif self.graph_inference and staged.tensors[0].is_cuda:      # one hipGraph per clip shape and input kind
+                logits, ref_last, hs_last, feats = replay_captured(
+                    self._graphs, staged.key, staged.tensors, lambda *t: self._clip_trunk_tail(*staged.to_net(*t)))
+            else:
+                logits, ref_last, hs_last, feats = self._clip_trunk_tail(*staged.to_net(*staged.tensors))
         finally:
             self.num_frames = keep
         ih, iw = frames[0].shape[-2:] if rz is None else rz[0][0]             # size fed to the network
@@ -825,8 +453,8 @@ class SeqFormer(nn.Module):
         every CLIP_STRIDE, linked by mask sIoU (vnext_amd/models/clip_matching.py), tracks averaged."""
         assert len(batched_inputs) == 1
         video = batched_inputs[0]
-        frames, rz, src_size = self._plan_resize(video, list(video["image"]))
-        if rz is None and not (self.device_ingest and ingest.applies(frames, self.device)):      # uint8 frames stay bytes until the kernel
+        frames, rz, src_size = plan_resize(self.device_resize and not self.training, video, self._test_size, self.device)
+        if rz is None and not takes_bytes(frames, self.device_ingest, self.device):      # uint8 frames stay bytes until the kernel
             frames = [f.to(self.device, torch.float32) for f in frames]
         ih, iw = frames[0].shape[-2:] if rz is None else rz[0][0]      # the size the network sees: with `device_resize` the target
         sh, sw = (ih, iw) if src_size is None else src_size

@@ -16,7 +16,7 @@ hipGraph capture: a host integer is baked into a captured graph, so 
 would drop the same elements every step, where the `nn.Dropout` this replaces is graph-safe (its Philox offset advances
 per replay).  Under capture with p > 0 the kernels therefore also read a per-device STEP SEED from device memory
 (`seed_device` of the C ABI): `step_scope(device)` -- entered by the owner of the captured callable at the top of its
-forward, `_TrainTrunk.forward` here -- bumps that word with a captured `add_`, once per replay; the baked host seeds
+forward, `models.frames.TrainTrunk.forward` here -- bumps that word with a captured `add_`, once per replay; the baked host seeds
 only tell the call sites apart.  What the kernels read is not the bumped word itself but a SNAPSHOT of it taken when the
 scope is entered (one captured 8-byte copy per scope entry): the backward of a site reads the snapshot its forward
 read, so a second `step_scope` entry between a forward and its backward -- two trunk forwards before one backward,

@@ -22,6 +22,7 @@ or above 128) or more than 8 levels takes the reference expression too.  `CALLS`
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 import torch.nn.functional as F
@@ -99,9 +100,25 @@ def reference_ingest(pixels, table, B, H, W, mean, std, channels_last=False):
     return x, mask
 
 
+def sine_position(mask, num_pos_feats=128, temperature=10000):
+    """models/position_encoding.py:35-55 with normalize=True."""
+    not_mask = ~mask
+    y_embed = not_mask.cumsum(1, dtype=torch.float32)
+    x_embed = not_mask.cumsum(2, dtype=torch.float32)
+    eps, scale = 1e-6, 2 * math.pi
+    y_embed = (y_embed - 0.5) / (y_embed[:, -1:, :] + eps) * scale
+    x_embed = (x_embed - 0.5) / (x_embed[:, :, -1:] + eps) * scale
+    dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=mask.device)
+    dim_t = temperature ** (2 * (dim_t // 2) / num_pos_feats)
+    pos_x = x_embed[:, :, :, None] / dim_t
+    pos_y = y_embed[:, :, :, None] / dim_t
+    pos_x = torch.stack((pos_x[..., 0::2].sin(), pos_x[..., 1::2].cos()), dim=4).flatten(3)
+    pos_y = torch.stack((pos_y[..., 0::2].sin(), pos_y[..., 1::2].cos()), dim=4).flatten(3)
+    return torch.cat((pos_y, pos_x), dim=3).permute(0, 3, 1, 2)
+
+
 def reference_levels(mask, level_sizes, num_pos_feats, temperature=10000):
     """`level_constants` by torch from the padding mask [B, H, W]: the expression of the models' eager path"""
-    from ..models.seqformer import sine_position
     masks = [F.interpolate(mask[None].float(), size=tuple(s)).to(torch.bool)[0] for s in level_sizes]
     return masks, [sine_position(mk, num_pos_feats, temperature) for mk in masks]
 
@@ -139,7 +156,6 @@ def position_tables(device, num_pos_feats: int, temperature=10000):
     key = (str(device), int(num_pos_feats), float(temperature))
     t = _TABLES.get(key)
     if t is None:
-        from ..models.seqformer import sine_position
         with torch.no_grad():
             dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=device)
             dim_t = temperature ** (2 * (dim_t // 2) / num_pos_feats)

@@ -220,16 +220,16 @@ def enable_conv_search(db_dir=None) -> dict:
 
 
 def enable_channels_last() -> dict:
-    """Opt in to the channels-last ResNet trunk for TRAINING steps (vnext_amd/models/seqformer.py: MIOpen's fp32 backward
+    """Opt in to the channels-last ResNet trunk for TRAINING steps (vnext_amd/models/resnet.py: MIOpen's fp32 backward
     convolutions are NHWC kernels either way; given NCHW tensors it transposes around each: SeqFormer step 66.2 -> 64.3 ms).
     Two process-wide settings, which is why this is an explicit call and not an import side effect:
       * PYTORCH_MIOPEN_SUGGEST_NHWC=1 -- PyTorch hands MIOpen an NHWC problem only with it, and reads it ONCE: call this
         before the process runs its first convolution (a later call still flips the trunk's switch, but PyTorch has read
         the variable by then and the inputs are converted for nothing -- this function cannot see that; it is the caller's
         ordering to keep);
-      * the trunk's switch `models.seqformer.CHANNELS_LAST`.
+      * the trunk's switch `models.resnet.CHANNELS_LAST`.
     VNX_CHANNELS_LAST=0 or an explicit PYTORCH_MIOPEN_SUGGEST_NHWC=0 opt out.  -> {"enabled", "why"} for the bench line."""
-    from .models import seqformer
+    from .models import resnet
     if os.environ.get("VNX_CHANNELS_LAST", "1") == "0":
         return {"enabled": False, "why": "VNX_CHANNELS_LAST=0"}
     if not torch.cuda.is_available():
@@ -237,7 +237,7 @@ def enable_channels_last() -> dict:
     if os.environ.get("PYTORCH_MIOPEN_SUGGEST_NHWC", "1") != "1":
         return {"enabled": False, "why": "PYTORCH_MIOPEN_SUGGEST_NHWC is set to something else"}
     os.environ["PYTORCH_MIOPEN_SUGGEST_NHWC"] = "1"
-    seqformer.CHANNELS_LAST = True
+    resnet.CHANNELS_LAST = True
     return {"enabled": True, "why": "PYTORCH_MIOPEN_SUGGEST_NHWC=1 set before the first convolution; training trunk in channels-last"}
 
 
