@@ -14,14 +14,14 @@ import pytest
 from oracle import msda_oracle as O
 from vnext_amd import _lib
 
-QC, ROWS = 304, 768      # VNX_GVD_QC, VNX_GVD_ROWS (msda_units.h)
+QC, ROWS = 304, 768      # kGvdQc, kGvdRows (msda_units.h)
 CAP = 4 * QC * 4         # kGvdCap (msda_d32_gvdirect_body.h): taps of a pass the sorted list holds
 SLOTS = 3 * 256          # kIters x 256 groups (msda_d32_gvdirect_body.h): the slots the walk covers
 P360 = [(48, 80), (24, 40), (12, 20), (6, 10)]
 
 
 def pass_queries(Lq, P):
-    """queries a pass stages (the kernel's qc): min(VNX_GVD_QC, 4 * VNX_GVD_QC / P), never more than the call has"""
+    """queries a pass stages (the kernel's qc): min(kGvdQc, 4 * kGvdQc / P), never more than the call has"""
     return min(Lq, QC, (4 * QC) // P)
 
 

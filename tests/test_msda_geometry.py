@@ -28,7 +28,7 @@ from oracle import msda_oracle as O  # noqa: E402
 from vnext_amd import _lib  # noqa: E402
 
 DEV = "cuda:0"
-QC = 304                                                   # VNX_GVD_QC
+QC = 304                                                   # kGvdQc (msda_units.h)
 P360 = [(48, 80), (24, 40), (12, 20), (6, 10)]
 P360_8 = P360 + [(3, 5), (2, 3), (1, 2), (1, 1)]
 GUARD = 256                                                # elements before and after every output buffer

@@ -22,6 +22,13 @@ MSDA_LEVELS_PACKED = 1
 MSDA_REF_F32 = 0x100       # or-ed into ref_dim of vnx_msda_fused_*: fp32 reference points beside 16-bit offsets / logits
 MASK_RLE_LOGITS, MASK_RLE_BINARY = 0, 1   # vnx_mask_rle_*: input modes
 MSDA_FORK = 2              # vnx_msda_backward: grad_value kernel on the library's side stream (include/vnext_hip.h)
+# limits of include/vnext_hip.h, by their names there
+MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096            # VNX_MASK_LOSS_MAX_CLIPS, VNX_MASK_LOSS_PIECE
+SET_LOSS_PIECE, SET_LOSS_MAX_ROWS = 4096, 1024             # VNX_SET_LOSS_PIECE, VNX_SET_LOSS_MAX_ROWS
+REID_LOSS_MAX_ROWS = 1024                                  # VNX_REID_LOSS_MAX_ROWS
+CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_INSTANCES, VNX_CLIP_LINK_MAX_FRAMES
+INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
+RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 
@@ -116,31 +123,12 @@ DEV_SIGNATURES = {
 }
 
 
-
 class TrackerConfig(ctypes.Structure):
     """`vnx_tracker_config` of include/vnext_hip.h, field by field."""
     _fields_ = [(k, _i) for k in ("capacity", "channels", "memory_len", "memo_tracklet_frames", "match_metric",
                                   "long_match", "frame_weight", "temporal_weight")] + \
                [(k, ctypes.c_float) for k in ("nms_thr_pre", "nms_thr_post", "init_score_thr", "addnew_score_thr",
                                               "match_score_thr", "memo_momentum")]
-
-
-MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096      # VNX_MASK_LOSS_MAX_CLIPS, VNX_MASK_LOSS_PIECE
-
-
-SET_LOSS_PIECE, SET_LOSS_MAX_ROWS = 4096, 1024       # VNX_SET_LOSS_PIECE, VNX_SET_LOSS_MAX_ROWS
-
-
-REID_LOSS_MAX_ROWS = 1024                            # VNX_REID_LOSS_MAX_ROWS
-
-
-CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_INSTANCES, VNX_CLIP_LINK_MAX_FRAMES
-
-
-INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
-
-
-RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
 
 
 class ClipLinkConfig(ctypes.Structure):
@@ -195,7 +183,7 @@ def _load(path: str, tables) -> ctypes.CDLL:
 def product_lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
-        path = os.environ.get("VNX_HIP_LIB") or LIB_PATH    # override: experiment builds (tools/wpe_sweep.py)
+        path = os.environ.get("VNX_HIP_LIB") or LIB_PATH    # override: experiment builds (tools/bench_ab.sh)
         _lib = _load(path, (SIGNATURES, DEBUG_SIGNATURES))
     return _lib
 

@@ -61,8 +61,9 @@ def _headers() -> list[str]:
 
 def build_hip(force: bool = False, verbose: bool = False, out: str | None = None, defines=()) -> str:
     """One object per source file, compiled in parallel and cached by mtime (a one-file edit rebuilds
-    in seconds), then linked.  `out` / `defines` build an experiment copy (e.g. -DVNX_FWD_WPE=4) beside
-    the product library; `VNX_HIP_LIB=<path>` makes vnext_amd._lib load it (development aid)."""
+    in seconds), then linked.  `out` / `defines` build a copy with extra -D defines (the development build's
+    -DVNX_DEV_VARIANTS, or the macro of a temporary local A/B patch) beside the product library;
+    `VNX_HIP_LIB=<path>` makes vnext_amd._lib load it (development aid)."""
     from concurrent.futures import ThreadPoolExecutor
     target = out or LIB_PATH
     dev = DEV_DEFINE in defines

@@ -80,9 +80,6 @@ namespace vnx {
 // (720p B = 2: 271.4 / 272.1, unchanged).  (Round 3 measured 2 against 1 as 175.2 vs 176.4 us: then the pieces flushed
 // through atomics.)  Also re-measured on the partial-row scheme: a piece per 5 chunks instead of 10 190 us, per 20 chunks
 // 194 us (360p) / 265.6 us (720p B = 2, - 6); 4 pieces for the middle levels 171 / 293 us.
-#ifndef VNX_TILE_UNITS_MIN
-#define VNX_TILE_UNITS_MIN 1
-#endif
 int gv_units_min(const MsdaDims& d, bool tiles, int forced) {
   if (forced) return forced;
   // Tried with per-unit selection: enough units that each expects about one selection window of
@@ -90,7 +87,7 @@ int gv_units_min(const MsdaDims& d, bool tiles, int forced) {
   // backward -- because a unit's chunk count is set by its DISTINCT queries (128 staged rows per
   // chunk), and finer units multiply the (query, unit) incidences.
   (void)d;
-  return tiles ? VNX_TILE_UNITS_MIN : 2;
+  return tiles ? 1 : 2;
 }
 }  // namespace vnx
 
@@ -257,9 +254,6 @@ int vnx_msda_forward(int value_dtype, int loc_dtype, const void* value,
 // general path follows (unpacked_levels_tail), each kernel of which does nothing on the device when the levels ARE packed.
 // No host sync either way.  (The record-less predecessor of Records -- every unit re-deriving its level's geometry -- and
 // the side stream that overlapped it with the grad_loc kernel are archived under tools/experiments/msda_d32_gv.hip.)
-#ifndef VNX_PAIR_ORDER
-#define VNX_PAIR_ORDER -1     // role order of the paired backward kernel's workgroup groups (msda_d32.hip): -1 = the launcher's choice
-#endif
 enum class BwdPath { Generic, Pair, Direct, Tiles, Records };
 // Workspace: [sample records (Records) or tile words (Tiles) | locations, weights | partial rows (Tiles) | fp32 image], every
 // region a multiple of 256 B; a region a call does not need has no bytes.
@@ -296,7 +290,7 @@ static MsdaBackwardPlan plan_backward(int vdt, int ldt, const MsdaDims& d, int f
   // T = 5 encoder calls, model-like locations, cold: see DESIGN.md section 3.3b.  The development build forces records / tiles
   // for A/B runs (KernelVariant::gv_path; the variants that name a record-fed kernel keep it).
   // The self-decoding kernel is built for calls below 1 024 queries: beyond, every unit would re-stage all grad_out rows of
-  // its head once per pass of VNX_GVD_QC queries, and 16-bit rows would be rounded once per pass -- such calls (L * P != 16 or
+  // its head once per pass of kGvdQc queries, and 16-bit rows would be rounded once per pass -- such calls (L * P != 16 or
   // P != 4 at encoder sizes) keep the record-fed path, which accumulates in fp32.
   const bool records_forced = kv.gv_path == GvPath::Records;
   if (!records_forced && d.P == 4 && d.L * d.P == 16 && msda_d32_gvtiles_supported(vdt, ldt, d) &&
@@ -447,7 +441,7 @@ int vnx_msda_backward(int value_dtype, int loc_dtype, const void* value,
   if (plan.path == BwdPath::Pair) {
     st = msda_backward_pair_d32(value_dtype, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                                 grad_value, grad_sampling_loc, grad_attn_weight, d,
-                                kv.pair_order >= 0 ? kv.pair_order : VNX_PAIR_ORDER, stream);
+                                kv.pair_order, stream);
     if (st != VNX_OK) return st;
   } else if (plan.path == BwdPath::Direct) {
     // (1) grad_value from the op's own inputs and (2) grad_loc / grad_attn: neither reads what the other writes.  One after

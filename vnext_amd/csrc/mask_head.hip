@@ -30,10 +30,7 @@ constexpr int kMhHidden = 8;      // dynamic_mask_channels
 constexpr int kMhParams = (kMhChannels + 2) * kMhHidden + kMhHidden * kMhHidden + kMhHidden + kMhHidden + kMhHidden + 1;
 constexpr int kMhStripW = 63;     // stored columns per wave (64 lanes - 1 halo lane)
 #ifdef VNX_DEV_VARIANTS
-#ifndef VNX_MH_ROWS
-#define VNX_MH_ROWS 5
-#endif
-constexpr int kMhStripH = VNX_MH_ROWS;   // strip kernel: stored rows per wave (+1 halo row, all held in registers)
+constexpr int kMhStripH = 5;   // strip kernel: stored rows per wave (+1 halo row, all held in registers)
 #endif
 static_assert(kMhParams == 169, "parameter vector layout");
 
@@ -108,11 +105,7 @@ __device__ __forceinline__ void mask_logits(const float* P, const float2_t (&x0)
                  : "memory");
   };
   auto landed = [&](Group& g) {   // everything issued so far is in its registers (the loads are invisible to hipcc's own counting)
-#if defined(VNX_MH_ABL) && (VNX_MH_ABL & 8)     // timing ablation: the parameter groups are not waited for
-    asm volatile("" : "+s"(g.w), "+s"(g.w2), "+s"(g.b)::"memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(g.w), "+s"(g.w2), "+s"(g.b)::"memory");
-#endif
   };
   auto wpair = [](const Group& g, int k) -> uint64_t {   // weights 2k, 2k + 1 of the group as one SGPR pair
     return k < 8 ? (uint64_t(g.w[2 * k + 1]) << 32) | g.w[2 * k] : (uint64_t(g.w2[2 * (k - 8) + 1]) << 32) | g.w2[2 * (k - 8)];
@@ -402,12 +395,8 @@ dynamic_mask_head_runs_kernel(const float* __restrict__ feats, const float* __re
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int c = 0; c < kMhChannels; ++c) {
-#if defined(VNX_MH_ABL) && (VNX_MH_ABL & 4)     // timing ablation: no feature loads
-          const float f = float(pix) * 1e-6f + float(c);
-#else
           const float f = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(fsrc, int(pix + 256u * (2 * p + h)),
                                                                                int(uint32_t(c) * plane_bytes), 0));
-#endif
           if (h == 0) feat[p][c].x = f; else feat[p][c].y = f;
         }
       }
@@ -447,18 +436,9 @@ dynamic_mask_head_runs_kernel(const float* __restrict__ feats, const float* __re
     const int next = done + 64 * R;
     // the next chunk's features leave once this chunk's are consumed (their registers are free): layers two and three
     // and the stores below cover the latency
-#if defined(VNX_MH_ABL) && (VNX_MH_ABL & 2)     // timing ablation: no layers
-#pragma unroll
-    for (int p = 0; p < RP; ++p) {
-      float2_t t = x0[p][0];
-#pragma unroll
-      for (int c = 1; c < kMhChannels + 2; ++c) t += x0[p][c];
-      logit[2 * p] = t.x; logit[2 * p + 1] = t.y;
-    }
-    if (next < total) issue(next);
-#else
+    // (what the loads, the layers and the stores each cost -- timing ablations of round 4, since removed from the source:
+    //  DESIGN.md section 3.5b)
     mask_logits<RP>(P, x0, logit, [&] { if (next < total) issue(next); });
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) *reinterpret_cast<float*>(at_d + 256 * r) = logit[r];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -484,9 +464,6 @@ dynamic_mask_head_runs_kernel(const float* __restrict__ feats, const float* __re
       const float2_t bot = {0.5f * (nc[r] + d), d};
       // byte offset of out[2y][2x] in the run's rows: 4 * (4 (y - ya) W + 2 x) = 16 (f - f0) - 8 x
       const int off = (chunk16 + 1024 * r) - ((xs[r] << 3) + neg_lane16);
-#if defined(VNX_MH_ABL) && (VNX_MH_ABL & 1)     // timing ablation: no stores (but for results no run produces)
-      if (top.x != 1234.5f) continue;
-#endif
       // write-once output streamed past the caches (`nt`)
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(store2_t, top), osrc, off, 0, 2);
       __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(store2_t, bot), osrc, off + 8 * W, 0, 2);
@@ -552,14 +529,9 @@ static int mask_head_runs(int n, int H, int W, int forced) {
 // through coalesced fp32 atomics.  Outputs are zero-filled by the C entry point (memset nodes,
 // graph-capturable).  Lane 63 is a one-pixel halo on the right: the transpose of the
 // up-sampling needs the upstream gradient around pixel (y, x+1) and (y+1, x+1).
-#ifndef VNX_MB_ROWS
-#define VNX_MB_ROWS 8
-#endif
-constexpr int kMbRows = VNX_MB_ROWS;
-#ifndef VNX_MB_GROUP
-#define VNX_MB_GROUP 4
-#endif
-constexpr int kMbGroup = VNX_MB_GROUP;   // waves (consecutive instances) per workgroup of the backward
+// (The kernel's time by parts -- timing ablations, since removed from the source: DESIGN.md section 3.5b.)
+constexpr int kMbRows = 8;
+constexpr int kMbGroup = 4;   // waves (consecutive instances) per workgroup of the backward
 
 struct UpAdj { float d, c, b, a; };  // what a pixel's 2x2 output block sends to in[y][x], in[y][x-1], in[y-1][x], in[y-1][x-1]
 
@@ -757,11 +729,7 @@ mask_head_bwd_part(const int block, const float* __restrict__ feats, const float
 
   auto up_adj = [&](int y) -> UpAdj {
     float2_t top = {0.f, 0.f}, bot = {0.f, 0.f};
-#if defined(VNX_MB_ABL) && (VNX_MB_ABL & 8)      // timing ablation: no upstream-gradient loads
-    if (y < H && col_ok && relx == 1234.5f) {
-#else
     if (y < H && col_ok) {
-#endif
       top = *reinterpret_cast<const float2_t*>(G + int64_t(2 * y) * (2 * W) + 2 * x);
       bot = *reinterpret_cast<const float2_t*>(G + int64_t(2 * y + 1) * (2 * W) + 2 * x);
     }
@@ -815,11 +783,7 @@ mask_head_bwd_part(const int block, const float* __restrict__ feats, const float
     for (int q = 0; q < 8; ++q) g.w[q] = t[q];
   };
   auto landed = [&](Group& g) {
-#if defined(VNX_MB_ABL) && (VNX_MB_ABL & 2)      // timing ablation: the parameter groups are not waited for
-    asm volatile("" : "+s"(g.w), "+s"(g.w2), "+s"(g.b)::"memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(g.w), "+s"(g.w2), "+s"(g.b)::"memory");
-#endif
   };
   auto wpair = [](const Group& g, int k) -> uint64_t {   // weights 2k, 2k + 1 of the group as one SGPR pair
     return k < 8 ? (uint64_t(g.w[2 * k + 1]) << 32) | g.w[2 * k] : (uint64_t(g.w2[2 * (k - 8) + 1]) << 32) | g.w2[2 * (k - 8)];
@@ -851,11 +815,7 @@ mask_head_bwd_part(const int block, const float* __restrict__ feats, const float
     x0[0] = float2_t{relx, refy - (float(y * stride) + half)};
 #pragma unroll
     for (int c = 0; c < kMhChannels; c += 2)
-#if defined(VNX_MB_ABL) && (VNX_MB_ABL & 4)      // timing ablation: no feature loads
-      x0[1 + c / 2] = float2_t{relx * float(c), refy * float(y)};
-#else
       x0[1 + c / 2] = float2_t{F[(int64_t(c) * H + y) * W + xc], F[(int64_t(c + 1) * H + y) * W + xc]};
-#endif
 
     // ---- forward, recomputed: a dot product is a chain of packed FMAs over input pairs + one add of the halves
     float2_t x1[kP1], x2[kP1];

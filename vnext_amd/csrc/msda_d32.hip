@@ -42,12 +42,10 @@ template <typename TV>
 __device__ __forceinline__ float4_t load_tap(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off);
 
 template <>
-#ifndef VNX_TAP_AUX      // cache policy of the fp32 row gathers (A/B: 1 = sc0, 2 = nt, 16 = sc1; 0 = default).  Measured, forward, cold:
-                         // headline 8.6 / 8.9 / 10.9 / 9.0 us for default / sc0 / nt / sc1, encoder-360p 54.2 / 54.3 / 87.4 / 58.3 us
-#define VNX_TAP_AUX 0
-#endif
 __device__ __forceinline__ float4_t load_tap<float>(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
-  uint4_t r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, int(off), 0, VNX_TAP_AUX);
+  // default cache policy.  Tried, measured, not adopted (forward, cold): headline 8.6 / 8.9 / 10.9 / 9.0 us for default /
+  // sc0 / nt / sc1, encoder-360p 54.2 / 54.3 / 87.4 / 58.3 us
+  uint4_t r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, int(off), 0, 0);
   float4_t v;
   v.x = __uint_as_float(r.x); v.y = __uint_as_float(r.y);
   v.z = __uint_as_float(r.z); v.w = __uint_as_float(r.w);
@@ -247,64 +245,18 @@ __device__ __forceinline__ void fused_decode(const TL* __restrict__ raw_off, con
   }
 }
 
-// VNX_FWD_WPE / VNX_K1_WPE: amdgpu_waves_per_eu hint (second __launch_bounds__ argument); the
-// register-allocation and scheduling heuristics follow it, and the measured best is built in.
-// VNX_FWD_BATCH: samples whose 4 row loads each are issued before the first use (4: 16 loads in flight)
-#ifndef VNX_FWD_BATCH
-#define VNX_FWD_BATCH 4
-#endif
-#ifndef VNX_K1_BATCH
-#define VNX_K1_BATCH 4
-#endif
-#ifndef VNX_K1_BATCH_F32      // the 8-lanes-per-row fp32 path of the one-wave configuration (need not divide the samples of a group)
-#define VNX_K1_BATCH_F32 VNX_K1_BATCH
-#endif
-// tile boxes of the tile-fed grad_value path per WAVE (QPW = 4 queries on large calls) instead of per workgroup (16): a
-// tile's box is 4 + 12 pixels wide instead of 16 + 12, so fewer tiles meet a block (encoder backward, cold: 175.2 -> 169.1 us
-// at 360p, 654.8 -> 625.8 us at 720p B = 5), this kernel loses its LDS step, the grad_value kernel scans four times the
-// words (1 275 per level at 360p: two load rounds instead of one).  VNX_TILE_PER_WAVE=0: the per-workgroup form.
-#ifndef VNX_TILE_PER_WAVE
-#define VNX_TILE_PER_WAVE 1
-#endif
-constexpr bool kTilePerWave = VNX_TILE_PER_WAVE != 0;
-// fp32 rows of the grad_loc kernel as 4 lanes x 32 B (A/B macro: 0 = never, 1 = large-call configurations, 2 = all)
-#ifndef VNX_K1_F32_LPR4_MODE
-#define VNX_K1_F32_LPR4_MODE 0
-#endif
-#define VNX_K1_F32_LPR4(WPB_) (VNX_K1_F32_LPR4_MODE == 2 || (VNX_K1_F32_LPR4_MODE == 1 && (WPB_) > 1))
-#ifndef VNX_K1_BATCH_LARGE
-#define VNX_K1_BATCH_LARGE 2
-#endif
-// Timing ablations of the grad_loc kernel (A/B builds of the development library only; wrong results by construction), a
-// bit mask: 1 = no phase 3 (combination + gradient stores), 2 = no tile boxes, 4 = phase 2 without the 8-lane reductions
-// and result writes (row loads + dots only), 8 = no zeroing of the query-split levels' rows.
-#ifndef VNX_K1_ABL
-#define VNX_K1_ABL 0
-#endif
-// Phase 3's stores: 0 = three plain 4-byte stores per sample (rounds 1-3); 1 = (x, y) as one 8-byte store; 2 = that, and
-// both gradients non-temporal.  Measured (round 4, cold, grad_loc kernel alone / whole backward): encoder-360p 75.5 / 170.7 us
-// (0), 75.6 / 171.2 (1), 64.4 / 165.0 (2); headline 11.4 / 26.6 -> 11.2 / 26.0; encoder-720p B = 5 623 -> 620.  The gradients
-// are read much later, by the caller: streamed past the caches they no longer evict the rows this kernel gathers.  (Round 2
-// tried `nt` on the sample RECORDS as well, which the grad_value kernel reads right away: that lost; boxes and records stay plain.)
-#ifndef VNX_K1_P3
-#define VNX_K1_P3 2
-#endif
-#ifndef VNX_FWD_WPE
-#define VNX_FWD_WPE 0
-#endif
-#ifndef VNX_K1_WPE
-#define VNX_K1_WPE 0
-#endif
-#if VNX_FWD_WPE > 0
-#define VNX_FWD_BOUNDS(n) __launch_bounds__(n, VNX_FWD_WPE)
-#else
-#define VNX_FWD_BOUNDS(n) __launch_bounds__(n)
-#endif
-#if VNX_K1_WPE > 0
-#define VNX_K1_BOUNDS(n) __launch_bounds__(n, VNX_K1_WPE)
-#else
-#define VNX_K1_BOUNDS(n) __launch_bounds__(n)
-#endif
+// Samples whose 4 row loads each the forward issues before the first use in its one-wave configuration (4: 16 loads in
+// flight); the large-call configurations (WPB > 1) take 2
+constexpr int kFwdBatch = 4;
+// Tried, measured, not adopted (forward and grad_loc kernel):
+//  * an amdgpu_waves_per_eu hint as the second __launch_bounds__ argument of the forward and the grad_loc kernel (the
+//    register-allocation and scheduling heuristics follow it): no hint measured best (round 2);
+//  * the tile boxes of the tile-fed grad_value path per workgroup (16 queries) instead of per WAVE (QPW = 4 queries on large
+//    calls): per wave a tile's box is 4 + 12 pixels wide instead of 16 + 12, so fewer tiles meet a block (encoder backward,
+//    cold: 175.2 -> 169.1 us at 360p, 654.8 -> 625.8 us at 720p B = 5), this kernel has no LDS step for them, the grad_value
+//    kernel scans four times the words (1 275 per level at 360p: two load rounds instead of one);
+//  * fp32 rows of the grad_loc kernel as 4 lanes x 32 B: 178.7 against 175.7 us (encoder-360p backward, round 3);
+//  * the kernel's time by parts (timing ablations of round 4, since removed from the source): DESIGN.md section 3.3c.
 // PF: stream this wave's share of the head's rows towards L2 while the locations are in flight
 // (see "phase 0" below); built for the one-pass case (QPW * L*P <= 64), unfused.
 constexpr int kPfSteps = 3;       // LDS-DMA instructions per wave, 32 rows (2 x 64-B halves) each
@@ -312,7 +264,7 @@ constexpr int kPfSteps = 3;       // LDS-DMA instructions per wave, 32 rows (2 x
 // instructions and L1 cycles as fp32 -- bf16 bought nothing).  4: 16-bit rows as 4 x 16 B -- a wave instruction
 // covers 16 rows instead of 8, a sample's four taps cost a lane 4 loads of 16 B instead of 8 of 8 B (L*P == 16 only).
 template <typename TV, typename TL, int QPW, int WPB, int LP_T, bool FUSED = false, bool PF = false, int LPR = 8>
-__global__ void VNX_FWD_BOUNDS(64 * WPB)
+__global__ void __launch_bounds__(64 * WPB)
 msda_fwd_d32_kernel(const TV* __restrict__ value, const int64_t* __restrict__ shapes,
                     const int64_t* __restrict__ lsi, const TL* __restrict__ loc,
                     const TL* __restrict__ attn, TV* __restrict__ out, MsdaDims d,
@@ -479,7 +431,7 @@ msda_fwd_d32_kernel(const TV* __restrict__ value, const int64_t* __restrict__ sh
   if constexpr (LPR == 4) {
     // 16-bit rows, 8 channels per lane: the taps stay packed (4 dwords) until they are used
     constexpr int kPer = LP_T / PG;
-    constexpr int kWant = WPB == 1 ? VNX_FWD_BATCH : 2;
+    constexpr int kWant = WPB == 1 ? kFwdBatch : 2;
     constexpr int kBatch = kPer < kWant ? kPer : kWant;
     static_assert(kPer % kBatch == 0, "whole batches");
     float4_t acc_lo = {0.f, 0.f, 0.f, 0.f}, acc_hi = acc_lo;
@@ -532,7 +484,7 @@ msda_fwd_d32_kernel(const TV* __restrict__ value, const int64_t* __restrict__ sh
     constexpr int kPer = LP_T / PG;
     // 4 samples on the small calls (one wave per workgroup, 3 waves per SIMD: latency is everything); 2 on the large
     // ones, where 55 instead of 95 VGPRs = 8 instead of 5 waves per SIMD matter more (encoder 360p: 59.9 -> 54.8 us)
-    constexpr int kWant = WPB == 1 ? VNX_FWD_BATCH : 2;
+    constexpr int kWant = WPB == 1 ? kFwdBatch : 2;
     constexpr int kBatch = kPer < kWant ? kPer : kWant;
 #pragma unroll
     for (int i0 = 0; i0 < kPer; i0 += kBatch) {
@@ -650,14 +602,11 @@ msda_fwd_slab_kernel(const TV* __restrict__ value, const int64_t* __restrict__ s
   int* s_lvl = reinterpret_cast<int*>(smem + size_t(CAP128 + 1) * 128 + slab_rec_bytes(WAVES));      // [4][4]: H, W, start, -
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifndef VNX_SLAB_BATCH_MAJOR
-#define VNX_SLAB_BATCH_MAJOR 1
-#endif
   // batch-major: the workgroups resident at one time (64 per XCD) belong to one or two batch elements, whose rows of the XCD's
   // head then stay in its 4-MB L2 (2.5 MB per (batch, head) at 720p; with all five batch elements in flight the kernel fetched
   // 929 MB for 100 MB of values -- PMC, profiles/r05_shapes_kernel_avg_us.json)
   const int x = blockIdx.x % d.M, rest = blockIdx.x / d.M;
-  const int b = VNX_SLAB_BATCH_MAJOR ? rest / parts : rest % d.B, part = VNX_SLAB_BATCH_MAJOR ? rest % parts : rest / d.B;
+  const int b = rest / parts, part = rest % parts;
   const int m = (x + b) % d.M;      // head <-> XCD map rotating with the batch element, as the gather kernel
 
   // ---- the level table; which levels are staged ----
@@ -896,14 +845,12 @@ static bool use_slab_forward(int vdt, int ldt, const MsdaDims& d, int forced) {
 // (1, 2, 4, ...) as bring a workgroup to twelve tiles or fewer: every workgroup copies the slab once, but on the largest
 // calls shorter workgroups pack the launch's tail better (encoder-720p B = 5: one round = 25 tiles each 247 us, four rounds
 // 231-234; B = 2, 9.6 tiles each: 85 us with one round, 87 with two; encoder-360p at B = 10 -- two clips -- 13.3 tiles in one
-// round 88.5 us, 6.7 in two rounds 83.4, the gather kernel 110.9; VNX_SLAB_TILES_MAX 8 / 12 / 16 measured: 12).
+// round 88.5 us, 6.7 in two rounds 83.4, the gather kernel 110.9; a cap of 8 / 12 / 16 tiles measured: 12).
 static int slab_parts(const MsdaDims& d, int n_tiles, int resident = 512) {
   const int per_round = resident / (d.B * d.M) > 0 ? resident / (d.B * d.M) : 1;
   int parts = per_round;
-#ifndef VNX_SLAB_TILES_MAX
-#define VNX_SLAB_TILES_MAX 12
-#endif
-  while (parts < n_tiles && (n_tiles + parts - 1) / parts > VNX_SLAB_TILES_MAX) parts *= 2;
+  constexpr int kSlabTilesMax = 12;
+  while (parts < n_tiles && (n_tiles + parts - 1) / parts > kSlabTilesMax) parts *= 2;
   return parts > n_tiles ? n_tiles : parts;
 }
 
@@ -1185,6 +1132,10 @@ __device__ __forceinline__ void store_loc(TL* p, float v) { *p = from_acc<TL>(v)
 // The kernel's body as a device function of the workgroup's index `vblock`, the wave's index inside it `wave` and the
 // workgroup's LDS: msda_bwd_d32_kernel below is this and nothing else; msda_bwd_pair_kernel runs the one-wave-per-workgroup
 // configuration in every WAVE of its grad_loc workgroups (vblock = that wave's own workgroup index, wave = 0, its own LDS slice).
+// Samples whose 4 tap loads each phase 2 has in flight: KB where the caller fixes it (the paired kernel: kPairBatch), else
+constexpr int kK1Batch = 4;           // the one-wave configuration (WPB == 1), 16-bit rows
+constexpr int kK1BatchF32 = 4;        // ... its fp32 rows, 8 lanes per row (need not divide the samples of a group)
+constexpr int kK1BatchLarge = 2;      // the large-call configurations (WPB > 1); 1 or 4 measured 172 / 181 against 169 us (round 3)
 template <typename TV, typename TL, int QPW, int WPB, int LP_T, bool ATOMICS, bool FUSED = false, int LPR = 8, int KB = 0>
 __device__ __forceinline__ void
 msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shapes,
@@ -1225,7 +1176,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
   //      and no zeroing since round 4: its pieces store partial rows, msda_d32_gvtiles.hip; this phase cost 6.7 us of
   //      the 81-us kernel at encoder-360p.) ---------------------------------------------------------------
   if constexpr (!ATOMICS) {      // (fp32 values: rows of grad_value itself; 16-bit values: rows of the fp32 split image)
-    if (!(VNX_K1_ABL & 8) && fa.qsplit_zero != nullptr && sample_units != nullptr && d.Lq >= 1024 &&
+    if (fa.qsplit_zero != nullptr && sample_units != nullptr && d.Lq >= 1024 &&
         levels_packed(shapes, lsi, d.L, d.S)) {
       const int t_in_b = tile - b * tiles_per_batch;
       for (int l = 0; l < d.L; ++l) {
@@ -1306,7 +1257,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
         record = uint4_t{gv_pack_corner(h0, w0, H, W), __float_as_uint(g4.x),
                          __float_as_uint(g4.y), __float_as_uint(a)};
         if constexpr (LP_T == 16 && !ATOMICS) {
-          if (!(VNX_K1_ABL & 2) && tile_summary != nullptr) {
+          if (tile_summary != nullptr) {
             // coordinates saturate at 0xfffe, which the grad_value kernel reads as "or beyond" (a level side of 65 535+)
             const uint32_t x_lo = min(uint32_t(lef ? w0 : w0 + 1), 0xfffeu), x_hi = min(uint32_t(rig ? w0 + 1 : w0), 0xfffeu);
             const uint32_t y_lo = min(uint32_t(top ? h0 : h0 + 1), 0xfffeu), y_hi = min(uint32_t(bot ? h0 + 1 : h0), 0xfffeu);
@@ -1342,10 +1293,9 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
     s_off[qi * (LP + 1) + p] = o4;
     s_geo[qi * (LP + 1) + p] = g4;
   }
-  uint2_t* s_tile = reinterpret_cast<uint2_t*>(smem + size_t(WPB) * 3 * ent * 16);    // [WPB][4] (tile mode)
   uint2_t* tile_words = reinterpret_cast<uint2_t*>(tile_summary);                       // [b][head][level][tile]
   if constexpr (LP_T == 16 && !ATOMICS) {
-    if (!(VNX_K1_ABL & 2) && tile_summary != nullptr) {       // uniform.  A lane's samples all have level (lane & 15) >> 2 (P == 4):
+    if (tile_summary != nullptr) {       // uniform.  A lane's samples all have level (lane & 15) >> 2 (P == 4):
       // minimum over the 4 points (quad) and over the wave's queries (lane bits 4, 5)
       tile_kx = pk_min_u16(tile_kx, uint32_t(__builtin_amdgcn_update_dpp(int(tile_kx), int(tile_kx), 0xB1, 0xF, 0xF, true)));
       tile_ky = pk_min_u16(tile_ky, uint32_t(__builtin_amdgcn_update_dpp(int(tile_ky), int(tile_ky), 0xB1, 0xF, 0xF, true)));
@@ -1355,28 +1305,14 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
       tile_ky = pk_min_u16(tile_ky, uint32_t(__shfl_xor(int(tile_ky), 16, 64)));
       tile_kx = pk_min_u16(tile_kx, uint32_t(__shfl_xor(int(tile_kx), 32, 64)));
       tile_ky = pk_min_u16(tile_ky, uint32_t(__shfl_xor(int(tile_ky), 32, 64)));
-      if ((lane & 3) == 0 && lane < 16) {
-        if (kTilePerWave) {      // one box per WAVE (QPW queries): finer selection for the grad_value kernel, no LDS step here
-          const int wt = (tile - b * tiles_per_batch) * WPB + wave, wn = (d.Lq + QPW - 1) / QPW;
-          if (wt < wn) tile_words[((int64_t(b) * d.M + m) * d.L + (lane >> 2)) * wn + wt] = uint2_t{tile_kx, tile_ky};
-        } else if (WPB > 1) s_tile[wave * 4 + (lane >> 2)] = uint2_t{tile_kx, tile_ky};
-        else tile_words[((int64_t(b) * d.M + m) * d.L + (lane >> 2)) * tiles_per_batch + (tile - b * tiles_per_batch)] = uint2_t{tile_kx, tile_ky};
+      if ((lane & 3) == 0 && lane < 16) {      // one box per WAVE (QPW queries), not per workgroup: see the notes at kFwdBatch
+        const int wt = (tile - b * tiles_per_batch) * WPB + wave, wn = (d.Lq + QPW - 1) / QPW;
+        if (wt < wn) tile_words[((int64_t(b) * d.M + m) * d.L + (lane >> 2)) * wn + wt] = uint2_t{tile_kx, tile_ky};
       }
     }
   }
   if (WPB > 1) __syncthreads(); else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  if constexpr (LP_T == 16 && !ATOMICS && WPB > 1 && !kTilePerWave) {
-    if (tile_summary != nullptr && threadIdx.x < 4) {
-      uint2_t k = s_tile[threadIdx.x];
-#pragma unroll
-      for (int w2 = 1; w2 < WPB; ++w2) {
-        const uint2_t o = s_tile[w2 * 4 + threadIdx.x];
-        k.x = pk_min_u16(k.x, o.x); k.y = pk_min_u16(k.y, o.y);
-      }
-      tile_words[((int64_t(b) * d.M + m) * d.L + int(threadIdx.x)) * tiles_per_batch + (tile - b * tiles_per_batch)] = k;
-    }
-  }
 
   // ---- phase 2 ------------------------------------------------------------------
   const int ch = lane & (LPR - 1);
@@ -1426,7 +1362,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
       return dot8f(lo, hi);
     };
     constexpr int kPer = LP_T / PG;
-    constexpr int kWant = KB > 0 ? KB : k16 ? (WPB == 1 ? VNX_K1_BATCH : VNX_K1_BATCH_LARGE) : (WPB == 1 ? 2 : 1);   // fp32: 8 registers per tap
+    constexpr int kWant = KB > 0 ? KB : k16 ? (WPB == 1 ? kK1Batch : kK1BatchLarge) : (WPB == 1 ? 2 : 1);   // fp32: 8 registers per tap
     constexpr int kBatch = kPer < kWant ? kPer : kWant;
     static_assert(kPer % kBatch == 0, "whole batches");
     const uint32_t lane_off = uint32_t(ch * kLaneBytes);
@@ -1528,7 +1464,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
     // 2 for the large ones (4 waves per workgroup, rows > 4096), which are bound by how many waves fit:
     // encoder shape 106 vs 112 us.
     constexpr int kPer = LP_T / PG;
-    constexpr int kWant = KB > 0 ? KB : WPB == 1 ? VNX_K1_BATCH_F32 : VNX_K1_BATCH_LARGE;
+    constexpr int kWant = KB > 0 ? KB : WPB == 1 ? kK1BatchF32 : kK1BatchLarge;
     constexpr int kBatch = kPer < kWant ? kPer : kWant;
     // Round 2, late: this kernel is bound by vector-instruction issue on large calls (PMC, encoder 360p: 46.6 M wave
     // instructions x 4 clk / 1 024 SIMDs = 96 us = its duration), and most of them were the per-channel bilinear
@@ -1562,10 +1498,6 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
       for (int j = 0; j < kBatch; ++j) {
         if (i0 + j >= kPer) continue;
         const float4_t dd = {dot(v[j][0]), dot(v[j][1]), dot(v[j][2]), dot(v[j][3])};
-        if (VNX_K1_ABL & 4) {
-          if (dd.x + dd.y + dd.z + dd.w == 12345.678f) g_res[i0 + j] = dd;
-          continue;
-        }
         float t0, t1;
         group8_sum4_split(dd, t0, t1);        // lanes 0..3 of the set: (d1, d2); lanes 4..7: (d3, d4)
         if ((ch & 3) == 0) reinterpret_cast<float2_t*>(g_res + i0 + j)[ch >> 2] = float2_t{t0, t1};
@@ -1581,7 +1513,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
   __builtin_amdgcn_wave_barrier();
 
   // ---- phase 3 ------------------------------------------------------------------
-  for (int e = lane; e < ((VNX_K1_ABL & 1) ? 0 : pairs); e += 64) {
+  for (int e = lane; e < pairs; e += 64) {
     const int qi3 = e / LP, p = e - qi3 * LP;
     const int q3 = q0 + qi3;
     if (q3 < d.Lq) {
@@ -1599,23 +1531,21 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
       // (a vector load of the level size here is one more dependent memory round trip at the end of the wave)
       const float Hf = pairs <= 64 ? float(keep_H) : float(int(shapes[2 * l]));
       const float Wf = pairs <= 64 ? float(keep_W) : float(int(shapes[2 * l + 1]));
+      // The stores of fp32 gradients: (x, y) as one 8-byte store, both gradients non-temporal.  Tried, measured, not adopted
+      // (round 4, cold, grad_loc kernel alone / whole backward): three plain 4-byte stores per sample (rounds 1-3)
+      // encoder-360p 75.5 / 170.7 us, the 8-byte store plain 75.6 / 171.2, this form 64.4 / 165.0; headline 11.4 / 26.6 ->
+      // 11.2 / 26.0; encoder-720p B = 5 623 -> 620.  The gradients are read much later, by the caller: streamed past the caches
+      // they no longer evict the rows this kernel gathers.  (Round 2 tried `nt` on the sample RECORDS as well, which the
+      // grad_value kernel reads right away: that lost; boxes and records stay plain.)
       if constexpr (!FUSED) {
-#if VNX_K1_P3 >= 1      // A/B: the (x, y) pair of a sample as one 8-byte store (fp32 gradients), 2: both gradients `nt`
         if constexpr (sizeof(TL) == 4) {
           const float2_t gxy = {Wf * r.x, Hf * r.y};      // cuh:157-158
-          if (VNX_K1_P3 >= 2) {
-            __builtin_nontemporal_store(gxy, reinterpret_cast<float2_t*>(grad_loc + 2 * wi));
-            __builtin_nontemporal_store(r.z, reinterpret_cast<float*>(grad_attn + wi));
-          } else {
-            *reinterpret_cast<float2_t*>(grad_loc + 2 * wi) = gxy;
-            *reinterpret_cast<float*>(grad_attn + wi) = r.z;      // cuh:156
-          }
-        } else
-#endif
-        {
-        store_loc<TL>(grad_loc + 2 * wi, Wf * r.x);       // cuh:157
-        store_loc<TL>(grad_loc + 2 * wi + 1, Hf * r.y);   // cuh:158
-        store_loc<TL>(grad_attn + wi, r.z);               // cuh:156
+          __builtin_nontemporal_store(gxy, reinterpret_cast<float2_t*>(grad_loc + 2 * wi));
+          __builtin_nontemporal_store(r.z, reinterpret_cast<float*>(grad_attn + wi));      // cuh:156
+        } else {
+          store_loc<TL>(grad_loc + 2 * wi, Wf * r.x);       // cuh:157
+          store_loc<TL>(grad_loc + 2 * wi + 1, Hf * r.y);   // cuh:158
+          store_loc<TL>(grad_attn + wi, r.z);               // cuh:156
         }
       } else {
         // chain rule through the prologue: d loc / d offset is a per-sample scale, the softmax
@@ -1630,16 +1560,13 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
           const int64_t rf = ((int64_t(b / fa.ref_div) * d.Lq + q3) * d.L + l) * 4;
           sx = fused_ref<TL>(fa, rf + 2) * 0.5f / float(d.P); sy = fused_ref<TL>(fa, rf + 3) * 0.5f / float(d.P);
         }
-#if VNX_K1_P3 >= 2 && !defined(VNX_K1_P3F_PLAIN)      // as in the unfused branch: one 8-byte store per (x, y), both gradients `nt`
-        if constexpr (sizeof(TL) == 4) {
+        if constexpr (sizeof(TL) == 4) {      // as in the unfused branch: one 8-byte store per (x, y), both gradients `nt`
           __builtin_nontemporal_store(float2_t{gx * sx, gy * sy}, reinterpret_cast<float2_t*>(grad_loc + 2 * wi));
           __builtin_nontemporal_store(a * (r.z - dot), reinterpret_cast<float*>(grad_attn + wi));
-        } else
-#endif
-        {
-        store_loc<TL>(grad_loc + 2 * wi, gx * sx);
-        store_loc<TL>(grad_loc + 2 * wi + 1, gy * sy);
-        store_loc<TL>(grad_attn + wi, a * (r.z - dot));
+        } else {
+          store_loc<TL>(grad_loc + 2 * wi, gx * sx);
+          store_loc<TL>(grad_loc + 2 * wi + 1, gy * sy);
+          store_loc<TL>(grad_attn + wi, a * (r.z - dot));
         }
         if (fa.grad_reference != nullptr) {
           float rx = gx, ry = gy;
@@ -1657,7 +1584,7 @@ msda_bwd_d32_body(const TV* __restrict__ value, const int64_t* __restrict__ shap
 }
 
 template <typename TV, typename TL, int QPW, int WPB, int LP_T, bool ATOMICS, bool FUSED = false, int LPR = 8>
-__global__ void VNX_K1_BOUNDS(64 * WPB)
+__global__ void __launch_bounds__(64 * WPB)
 msda_bwd_d32_kernel(const TV* __restrict__ value, const int64_t* __restrict__ shapes,
                     const int64_t* __restrict__ lsi, const TL* __restrict__ loc,
                     const TL* __restrict__ attn, const TV* __restrict__ grad_out,
@@ -1691,12 +1618,12 @@ static int launch_bwd_cfg(const void* value, const int64_t* shapes, const int64_
     set_error("msda_backward: %lld workgroups exceed the grid limit", (long long)blocks);
     return VNX_ERR_UNSUPPORTED;
   }
-  const size_t lds = size_t(WPB) * 3 * QPW * (LP + 1) * 16 + 128;    // + [WPB][4] tile word pairs (tile mode)
+  const size_t lds = size_t(WPB) * 3 * QPW * (LP + 1) * 16 + 128;    // (+ 128: the [WPB][4] tile word pairs of the retired per-workgroup tile boxes; unused now)
   // the unit ranges sit behind the records in the workspace (gv_unit_ids_offset); only the P == 4
   // grad_value kernel reads them
   void* unit_ids = (records != nullptr && d.P == 4) ? (void*)((char*)records + gv_unit_ids_offset(d)) : nullptr;
   const int units_min = gv_units_min(d, tile_summary != nullptr, gv_units);
-  constexpr int kLpr = (sizeof(TV) == 2 || VNX_K1_F32_LPR4(WPB)) ? 4 : 8;    // 16-bit rows as 4 lanes x 16 B; fp32: VNX_K1_F32_LPR4
+  constexpr int kLpr = sizeof(TV) == 2 ? 4 : 8;    // 16-bit rows as 4 lanes x 16 B
 #define VNX_BWD_ARGS (const TV*)value, shapes, lsi, (const TL*)loc, (const TL*)attn, (const TV*)grad_out, (float*)gv, (TL*)grad_loc, \
                      (TL*)grad_attn, d, tiles_per_batch, (uint4_t*)records, (uint32_t*)unit_ids,                \
                      (uint32_t*)tile_summary, units_min,                                                          \
@@ -1743,17 +1670,12 @@ static int launch_bwd(const void* value, const int64_t* shapes, const int64_t* l
 constexpr int kPairWaves = 8;
 // samples whose tap loads a grad_loc wave has in flight: three CUs' worth of workgroups need <= 80 VGPRs (the stand-alone kernel
 // takes 4 = 16 loads: 92 VGPRs; fp32 3 + 3 + 2: 76; 16-bit rows, 4 samples per group: 2 + 2)
-#ifndef VNX_PAIR_BATCH_F32
-#define VNX_PAIR_BATCH_F32 3
-#endif
-template <typename TV> constexpr int kPairBatch = sizeof(TV) == 2 ? 2 : VNX_PAIR_BATCH_F32;
+template <typename TV> constexpr int kPairBatch = sizeof(TV) == 2 ? 2 : 3;
 template <int QPW> constexpr int kPairGlWaveLds = 3 * QPW * 17 * 16 + 128;      // the one-wave configuration's LDS (L*P == 16)
 
+constexpr int kPairWgsPerCu = 3;
 template <typename TV, typename TL, int QPW, int LPR>
-#ifndef VNX_PAIR_WGS_PER_CU
-#define VNX_PAIR_WGS_PER_CU 3
-#endif
-__global__ void __launch_bounds__(64 * kPairWaves, VNX_PAIR_WGS_PER_CU * kPairWaves / 4)
+__global__ void __launch_bounds__(64 * kPairWaves, kPairWgsPerCu * kPairWaves / 4)
 msda_bwd_pair_kernel(const TV* __restrict__ value, const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
                      const TL* __restrict__ loc, const TL* __restrict__ attn, const TV* __restrict__ grad_out,
                      TV* __restrict__ grad_value, TL* __restrict__ grad_loc, TL* __restrict__ grad_attn, MsdaDims d,
@@ -1812,17 +1734,13 @@ static int launch_pair(const void* value, const int64_t* shapes, const int64_t* 
   const int64_t gl_blocks = int64_t(d.B) * tiles_per_batch * d.M;
   const int64_t gl_groups = (gl_blocks + int64_t(kPairWaves) * d.M - 1) / (int64_t(kPairWaves) * d.M);      // of M workgroups each
   const int rows = gvd_rows_max(d.S);
-#ifdef VNX_PAIR_UT      // A/B: units per level at least, forced
-  const int ut = VNX_PAIR_UT;
-#else
   const int ut = gvd_units_min(d.S, d.L, d.B * d.M, rows, gl_groups * d.M);      // (the small levels are cut only if BOTH roles then fit about one round)
-#endif
   const int64_t gv_blocks = ((int64_t(d.B) * msda_gvdirect_units_bound(d, ut, rows) + 1) & ~int64_t(1)) * d.M;
   // Role order (see the kernel): with everything resident in ONE round of three workgroups per CU the grad_value groups go
   // first -- their units are the longest workgroups (T = 5 call, 735 workgroups: 19.5 us against 20.7 with the grad_loc groups
   // first); with more rounds the grad_loc groups (B = 10: 33.4 against 39.2 us).  order < 0: this choice.
   if (order < 0)
-    order = int64_t(d.B) * d.M * gvd_units_estimate(d.S, d.L, rows) + gl_groups * d.M <= VNX_GVD_ONE_ROUND ? 0 : 1;
+    order = int64_t(d.B) * d.M * gvd_units_estimate(d.S, d.L, rows) + gl_groups * d.M <= kGvdOneRound ? 0 : 1;
   const int64_t blocks = gv_blocks + gl_groups * d.M;
   if (blocks >= (int64_t(1) << 31)) {
     set_error("msda_backward: %lld workgroups exceed the grid limit", (long long)blocks);
@@ -2118,7 +2036,7 @@ static int launch_bwd_slab(const void* value, const int64_t* shapes, const int64
 
 int msda_bwd_tile_queries(const MsdaDims& d, FwdCfg forced) {      // forced: the grad_loc launcher's (KernelVariant::gl_cfg)
   const FwdCfg c = pick_fwd_cfg(d, forced);
-  return kTilePerWave ? c.qpw : c.qpw * c.wpb;
+  return c.qpw;
 }
 
 bool msda_d32_bwd_supported(int vdt, int ldt, const MsdaDims& d) {
@@ -2183,7 +2101,7 @@ static int launch_bwd_fused_cfg(const void* value, const int64_t* shapes, const 
   const size_t lds = size_t(WPB) * 3 * QPW * 17 * 16 + 128;
   void* unit_ids = (records != nullptr && d.P == 4) ? (void*)((char*)records + gv_unit_ids_offset(d)) : nullptr;
   const int units_min = gv_units_min(d, tile_summary != nullptr, gv_units);
-  constexpr int kLpr = (sizeof(TV) == 2 || VNX_K1_F32_LPR4(WPB)) ? 4 : 8;
+  constexpr int kLpr = sizeof(TV) == 2 ? 4 : 8;
   hipLaunchKernelGGL((msda_bwd_d32_kernel<TV, TL, QPW, WPB, 16, false, true, kLpr>), dim3(uint32_t(blocks)), dim3(64 * WPB),
                      lds, stream, (const TV*)value, shapes, lsi, (const TL*)raw_off, (const TL*)raw_logit,
                      (const TV*)grad_out, (float*)nullptr, (TL*)grad_off, (TL*)grad_logit, d, tiles_per_batch,

@@ -22,10 +22,10 @@
 // `sampling_loc`) and stages all of its head's grad_out rows, so the traffic from L2 grows with the number of units.  The
 // first form of the round had 24 units of <= 320 rows per (batch, head), rows in registers as in msda_d32_gvrec.hip:
 // 18.9 us at the T = 5 decoder call, 6.5 us of it the loads (92 MB from L2 for 3.8 MB of inputs; timing ablations,
-// DESIGN.md section 3.3e).  Units of up to VNX_GVD_ROWS rows need ten.
+// DESIGN.md section 3.3e).  Units of up to kGvdRows rows need ten.
 // Every level receives the same number of taps whatever its size: a row of a coarse level (80 taps at the 60-pixel level
 // of a 300-query call) is spread over 1 << gshift adjacent groups whose partial sums meet through lane shuffles.
-// A pass stages at most VNX_GVD_QC queries; calls with more run several passes, the later ones adding onto the rows the
+// A pass stages at most kGvdQc queries; calls with more run several passes, the later ones adding onto the rows the
 // first stored (same owner, same lanes: no atomics).  Levels must be packed (checked on the device; capi.hip).
 // Reference semantics: ms_deform_im2col_cuda.cuh:87-159 (the scatter this replaces), :253-298 (index decode).
 #include "msda_d32_gvdirect_body.h"
@@ -35,7 +35,7 @@ namespace vnx {
 namespace rec {
 
 template <typename TV, typename TL, int P_T>
-__global__ void __launch_bounds__(kThreads, VNX_GVD_UNITS_PER_CU * kWaves / 4)
+__global__ void __launch_bounds__(kThreads, kGvdUnitsPerCu * kWaves / 4)
 msda_bwd_gv_direct_kernel(const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
                           const TL* __restrict__ loc, const TL* __restrict__ attn, const TV* __restrict__ grad_out,
                           TV* __restrict__ grad_value, MsdaDims d, int ut, int rows_max, int compact, unsigned long long* stamps) {
@@ -74,29 +74,18 @@ bool msda_d32_gvdirect_supported(int vdt, int ldt, const MsdaDims& d) {
   if (d.Lq >= (1 << 24) || d.M * 32 >= (1 << 24) || d.M * d.L * d.P >= (1 << 24)) return false;
   if (int64_t(d.Lq) * d.M * d.L * d.P * 8 >= (int64_t(1) << 31) || int64_t(d.Lq) * d.M * 32 * 4 >= (int64_t(1) << 31)) return false;
   // (the grid of either launcher: at most 2 L more units per (batch, head) than S / rows + L with the smallest rows in use)
-  const int64_t blocks = (int64_t(d.B) * (d.S / VNX_GVD_ROWS_LARGE + 3 * d.L) + 1) * d.M;
+  const int64_t blocks = (int64_t(d.B) * (d.S / kGvdRowsLarge + 3 * d.L) + 1) * d.M;
   return blocks < (int64_t(1) << 30);
 }
 
 template <typename TV, typename TL>
 static int launch_gvdirect(const int64_t* shapes, const int64_t* lsi, const void* loc, const void* attn, const void* grad_out,
                            void* grad_value, const MsdaDims& d, int compact, hipStream_t stream) {
-#ifdef VNX_GVD_ROWS_ALONE      // A/B: rows per unit of the stand-alone launch
-  const int rows = VNX_GVD_ROWS_ALONE;
-#else
   const int rows = gvd_rows_max(d.S);
-#endif
-#ifdef VNX_GVD_UT_ALONE
-  const int ut = VNX_GVD_UT_ALONE;
-#else
   const int ut = gvd_units_min(d.S, d.L, d.B * d.M, rows);
-#endif
   const int64_t blocks = ((int64_t(d.B) * msda_gvdirect_units_bound(d, ut, rows) + 1) & ~int64_t(1)) * d.M;   // (unit, batch) pairs: even (gv_decode_block)
   // more than 64 KiB of LDS per workgroup: the limit is raised once per kernel (and device: the attribute is per function)
-#ifndef VNX_GVD_LDS_ALONE      // A/B: LDS bytes the stand-alone launch asks for (more than the kernel needs = fewer units per CU)
-#define VNX_GVD_LDS_ALONE rec::kGvdLdsBytes
-#endif
-  const size_t lds = VNX_GVD_LDS_ALONE;
+  const size_t lds = rec::kGvdLdsBytes;
 #define VNX_LAUNCH(PT)                                                                                                    \
   do {                                                                                                                    \
     static thread_local int raised_on = -1;                                                                               \

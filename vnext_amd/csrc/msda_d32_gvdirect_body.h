@@ -9,27 +9,6 @@
 namespace vnx {
 namespace rec {
 
-#ifndef VNX_GVD_UNITS_PER_CU
-#define VNX_GVD_UNITS_PER_CU 3
-#endif
-// Channel parts a unit's rows are staged and walked in: 1 = whole 128-B rows (rounds 5's form: 80 KB of LDS, two units per
-// CU), 2 = two passes of 16 channels over ONE sorted tap list (52 KB: three units per CU, see the walk below)
-#ifndef VNX_GVD_PARTS
-#define VNX_GVD_PARTS 2
-#endif
-#ifndef VNX_GVD_AUX
-#define VNX_GVD_AUX 0             // cache policy of the location / weight loads (2 = nt)
-#endif
-// Timing ablations (A/B builds of the development library only; wrong grad_value by construction): 1 = return after the
-// level table, 2 = no taps (loads, decode and barriers only), 3 = rows stored without their sums, 4 = no store
-#ifndef VNX_GVD_ABL
-#define VNX_GVD_ABL 0
-#endif
-#ifndef VNX_GVD_FULL_BARRIERS
-#define VNX_GVD_FULL_BARRIERS 0   // A/B: __syncthreads() (waits for the rows in flight) where the kernel has LDS-only barriers
-#endif
-
-
 // Development aid (-DVNX_GVD_STAMPS, development library only): per-workgroup phase timestamps in constant-rate wall-clock
 // ticks, 8 per workgroup -- 0 start, 1 level table read, 2 loads issued, 3 decoded + ranked (the loads have arrived),
 // 4 first barrier, 5 offsets + second barrier, 6 scattered + rows staged + third barrier, 7 rows walked and stored.
@@ -40,19 +19,22 @@ static __device__ unsigned long long g_gvd_stamps[4096 * 8];      // (per transl
 #define VNX_GVD_STAMP(k) do { } while (0)
 #endif
 
-constexpr int kGvdQc = VNX_GVD_QC;
-constexpr int kGvdRows = VNX_GVD_ROWS;
+// (The kernel's time by parts and by phase -- timing ablations of rounds 5 and 6, since removed from the source, and the phase
+//  stamps above: DESIGN.md sections 3.3e and 3.3g.)
+constexpr int kGvdUnitsPerCu = 3;                                       // what the LDS of a unit is sized for
 constexpr int kGvdSamples = kGvdQc * 4;                                 // samples of a level per pass, at most
 constexpr int kGvdSpt = (kGvdSamples + kThreads - 1) / kThreads;        // ... per thread
 constexpr int kGvdCap = 4 * kGvdSamples;                                // taps per pass, at most: the sorted list holds them all
-constexpr int kGvdParts = VNX_GVD_PARTS;                                // channel parts of a row (see VNX_GVD_PARTS)
+// Channel parts a unit's rows are staged and walked in: 1 = whole 128-B rows (rounds 5's form: 80 KB of LDS, two units per
+// CU), 2 = two passes of 16 channels over ONE sorted tap list (52 KB: three units per CU, see the walk below)
+constexpr int kGvdParts = 2;
 constexpr int kGvdPartPieces = 8 / kGvdParts;                           // 16-B pieces (4 fp32 channels) of a row part
 constexpr int kGvdRowPieces = (kGvdQc * kGvdPartPieces + kThreads - 1) / kThreads;   // pieces of a part's staged rows per thread and pass
 // LDS of a unit: one part of the staged rows, the sorted tap list (weights + query slots), one word per row of the unit
 // (taps | first tap << 16), the allocation word and the level table
 constexpr size_t kGvdLdsBytes = size_t(kGvdQc) * 16 * kGvdPartPieces + size_t(kGvdCap) * 6 + size_t(kGvdRows) * 4 + 16 + 4 * kLevelsMax * 4;
 static_assert(kGvdParts == 1 || kGvdParts == 2, "whole rows or halves");
-static_assert(kGvdLdsBytes * VNX_GVD_UNITS_PER_CU <= 160 * 1024, "the units that share a CU must fit its LDS");
+static_assert(kGvdLdsBytes * kGvdUnitsPerCu <= 160 * 1024, "the units that share a CU must fit its LDS");
 static_assert(kGvdCap < 65536 && kGvdQc < 65536, "tap ranks and query slots fit 16 bits");
 
 // The kernel's body as a device function of the workgroup's index `vblock` and its LDS: msda_bwd_gv_direct_kernel below is this
@@ -78,8 +60,7 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
   // units are numbered from the last (coarsest) level back; head <-> XCD map rotating with the batch element: as in
   // msda_d32_gvrec.hip / msda_gv_common.h
   int rest, b, m;
-  if (kGvPair16 && sizeof(TV) == 2 && (d.M & 1) == 0) gv_decode_block<true>(vblock, d.M, d.B, rest, b, m);
-  else gv_decode_block<false>(vblock, d.M, d.B, rest, b, m);
+  gv_decode_block(vblock, d.M, d.B, rest, b, m);
   const int unit = rest / d.B;
   VNX_GVD_STAMP(0);
 
@@ -166,7 +147,6 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
   lvl = __builtin_amdgcn_readfirstlane(lvl); r0 = __builtin_amdgcn_readfirstlane(r0); r1 = __builtin_amdgcn_readfirstlane(r1);
   Hl = __builtin_amdgcn_readfirstlane(Hl); Wl = __builtin_amdgcn_readfirstlane(Wl); start = __builtin_amdgcn_readfirstlane(start);
   gshift = __builtin_amdgcn_readfirstlane(gshift);
-  if (VNX_GVD_ABL == 1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
   const int rows = r1 - r0;
   VNX_GVD_STAMP(1);
 
@@ -196,7 +176,8 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
   auto do_pass = [&](const int pass, auto single_tag) {
     constexpr bool kSingle = decltype(single_tag)::value;
     const int q_lo = pass * qc;
-    // ---- this pass's samples: up to kGvdSpt per thread, slot j * 512 + tid -> (query slot, point) -------------------
+    // ---- this pass's samples: up to kGvdSpt per thread, slot j * 512 + tid -> (query slot, point); default cache policy
+    //      (`nt` on these loads was an A/B build, not adopted) -------------------
     float sx[kGvdSpt], sy[kGvdSpt], sa[kGvdSpt];
     uint32_t svalid = 0;               // bit j: slot j holds a sample
     {
@@ -210,12 +191,12 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
         svalid |= uint32_t(valid) << j;
         const uint32_t si = valid ? __umul24(uint32_t(q_lo) + ql, s_stride) + k : kOutOfRange;
         if constexpr (sizeof(TL) == 4) {
-          const uint2_t xy = __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(loc_src, int(si * 8u), 0, VNX_GVD_AUX));
+          const uint2_t xy = __builtin_bit_cast(uint2_t, __builtin_amdgcn_raw_buffer_load_b64(loc_src, int(si * 8u), 0, 0));
           sx[j] = __uint_as_float(xy.x); sy[j] = __uint_as_float(xy.y);
-          sa[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(attn_src, int(si * 4u), 0, VNX_GVD_AUX));
+          sa[j] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(attn_src, int(si * 4u), 0, 0));
         } else {
-          const uint32_t xy = __builtin_amdgcn_raw_buffer_load_b32(loc_src, int(si * 4u), 0, VNX_GVD_AUX);
-          const uint32_t a16 = __builtin_amdgcn_raw_buffer_load_b16(attn_src, int(si * 2u), 0, VNX_GVD_AUX);
+          const uint32_t xy = __builtin_amdgcn_raw_buffer_load_b32(loc_src, int(si * 4u), 0, 0);
+          const uint32_t a16 = __builtin_amdgcn_raw_buffer_load_b16(attn_src, int(si * 2u), 0, 0);
           sx[j] = to_acc(__builtin_bit_cast(TL, uint16_t(xy & 0xffffu))); sy[j] = to_acc(__builtin_bit_cast(TL, uint16_t(xy >> 16)));
           sa[j] = to_acc(__builtin_bit_cast(TL, uint16_t(a16)));
         }
@@ -249,7 +230,6 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
         }
       }
       sy[j] = lh; sx[j] = lw;          // (sx, sy) now hold the fractions; sa the attention weight
-      if (VNX_GVD_ABL == 2) mj = (lh + lw == 12345.f) ? mj : 0u;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
         if (mj & (1u << t)) {
@@ -259,7 +239,7 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
       mask |= mj << (4 * j);
     }
     if (pass == 0) VNX_GVD_STAMP(3);
-    if (VNX_GVD_FULL_BARRIERS) __syncthreads(); else lds_barrier();      // (the rows stay in flight)
+    lds_barrier();      // LDS only: the rows stay in flight (__syncthreads() would wait for them)
     if (pass == 0) VNX_GVD_STAMP(4);
 
     // ---- row counts -> segment offsets: DPP wave scan + one LDS allocation per wave and 512 rows ------------------------------
@@ -274,7 +254,7 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
       base = uint32_t(__builtin_amdgcn_readfirstlane(int(base)));
       if (r < rows) cnt[r] = my_cnt | ((base + incl - my_cnt) << 16);
     }
-    if (VNX_GVD_FULL_BARRIERS) __syncthreads(); else lds_barrier();
+    lds_barrier();
     if (pass == 0) VNX_GVD_STAMP(5);
 
     // ---- scatter {query slot, weight} into the rows' segments --------------------------------------------------------------
@@ -318,11 +298,11 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
     constexpr int kPieces = kGvdPartPieces / kLpr;
     constexpr int kGrp = kThreads / kLpr;              // groups per workgroup = slots per round
     // slots = rows << gshift <= kGvdRows: rows <= rows_max <= kGvdRows, and gvd_level_split takes the taps of ONE pass (at most
-    // kGvdCap), so gshift > 0 only where n << gshift <= kGvdCap / 8, and it lowers gshift until rpu << gshift <= VNX_GVD_ROWS.
+    // kGvdCap), so gshift > 0 only where n << gshift <= kGvdCap / 8, and it lowers gshift until rpu << gshift <= kGvdRows.
     // A row whose slot lies past the last round is never summed nor stored.
     constexpr int kSlotsMax = kGvdRows > kGvdCap / 8 ? kGvdRows : kGvdCap / 8;
     constexpr int kIters = (kSlotsMax + kGrp - 1) / kGrp;
-    static_assert(kIters * kGrp >= kSlotsMax && kSlotsMax >= VNX_GVD_ROWS, "the walk covers every slot gvd_level_split allows");
+    static_assert(kIters * kGrp >= kSlotsMax && kSlotsMax >= kGvdRows, "the walk covers every slot gvd_level_split allows");
     float4_t held[kGvdParts == 2 ? kIters : 1][kPieces];
     auto walk = [&](auto cp_tag) {
       constexpr int cp = decltype(cp_tag)::value;
@@ -352,7 +332,7 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
         uint32_t n = 0, o = 0;
         if (slot < n_slots) {
           const uint32_t w = cnt[row];
-          n = VNX_GVD_ABL == 3 ? 0u : (w & 0xffffu); o = w >> 16;
+          n = w & 0xffffu; o = w >> 16;
         }
         float4_t a0[kPieces];      // (one set of sums, two taps' rows in flight: a second set cost 8 registers the held sums need)
 #pragma unroll
@@ -395,7 +375,6 @@ __device__ __forceinline__ void msda_bwd_gv_direct_body(const int64_t* __restric
           for (int h = 0; h < kPieces; ++h) held[it][h] = a0[h];
           continue;
         }
-        if (VNX_GVD_ABL == 4) continue;
         // several passes: the later ones add onto what the first stored (the same lanes wrote it: program order).  Non-temporal
         // stores in every case: written with plain stores the 26 MB of rows of a T = 5 call stay dirty in L2 until the
         // end-of-kernel write-back, which then takes 10 us (kernel 18.0 us; 7.8 without any store; 14.8 with `nt`) -- and a

@@ -323,12 +323,7 @@ msda_bwd_gv_rec_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
 // decoder backward 27.6 vs 27.9-28.2 us, but the encoder shape LOSES even with the kernel templated back to 128 for
 // large calls (225.5 vs 217.9 us at 360p, 492 vs 452 us at 720p B = 2: the step loop no longer unrolls into the old
 // schedule).  Not kept.
-// Timing ablations of the selection kernel (A/B builds of the development library only; wrong grad_value by construction):
-// 1 = no chunks (set-up + selection + final store), 2 = chunks without taps (no rank atomics / scatter / apply), 3 = no apply,
-// 4 = no selection either (returns after the level table: launch + set-up)
-#ifndef VNX_SEL_ABL
-#define VNX_SEL_ABL 0
-#endif
+// (The kernel's time by parts -- timing ablations of round 4, since removed from the source: DESIGN.md section 3.3d.)
 constexpr int kWin = 2048;                        // samples per selection window
 constexpr int kWinQueries = kWin / 4;
 constexpr int kSelRounds = kWin / kThreads;       // 4
@@ -338,7 +333,7 @@ constexpr size_t kSelLdsBytes = size_t(kQcMax) * 128 + size_t(kThreads) * 32 + s
                                 size_t(kSelParts) * 16 + 64;
 
 template <typename TV, bool NT>
-__global__ void __launch_bounds__(kThreads, VNX_SEL_UNITS_PER_CU * kWaves / 4)
+__global__ void __launch_bounds__(kThreads, kSelUnitsPerCu * kWaves / 4)
 msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
                        const uint4_t* __restrict__ records, const uint32_t* __restrict__ unit_ids,
                        const TV* __restrict__ grad_out, TV* __restrict__ grad_value, MsdaDims d, int units_min,
@@ -367,8 +362,7 @@ msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
   // one for a fine-level unit, 12-15 us against 6-7 -- start first instead of last (they used to start up
   // to 7 us into the kernel and set its end: 20 us for 8.5 us of mean work per workgroup).
   int rest, b, m;                                  // head <-> XCD map: gv_decode_block (msda_gv_common.h)
-  if (kGvPair16 && sizeof(TV) == 2 && (d.M & 1) == 0) gv_decode_block<true>(blockIdx.x, d.M, d.B, rest, b, m);
-  else gv_decode_block<false>(blockIdx.x, d.M, d.B, rest, b, m);
+  gv_decode_block(blockIdx.x, d.M, d.B, rest, b, m);
   const int unit = rest / d.B;
   VNX_STAMP(0);
 
@@ -421,7 +415,6 @@ msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
   // level land in a unit, so selecting them buys nothing and costs the unit its longest latency chain (tag loads, ballots,
   // scan: 3.4 us of the 12-15 us a coarse unit of the T=5 decoder call takes -- the kernel's critical path).  Such a unit
   // takes every sample of a window in order: identity tables, no loads, no ballots, no scan.
-  if (VNX_SEL_ABL == 4) return;
   const bool dense = __builtin_amdgcn_readfirstlane(lvl_units) <= 2;
   const int rows = r1 - r0;
   constexpr int kRpg = (kRowsMax + kGroups - 1) / kGroups;
@@ -515,7 +508,7 @@ msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
       }
     }
     }   // !dense
-    const int n_chunks = VNX_SEL_ABL == 1 ? 0 : (n_q + kQcMax - 1) / kQcMax;
+    const int n_chunks = (n_q + kQcMax - 1) / kQcMax;
     if (tid == 0) cs[n_chunks] = uint32_t(n_sel);
     __syncthreads();
     if (win0 == 0) VNX_SEL_STAMP(4);
@@ -568,7 +561,6 @@ msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
         row00 = p00 - r0;
         wt[0] = a * (hh * hw); wt[1] = a * (hh * lw); wt[2] = a * (lh * hw); wt[3] = a * (lh * lw);
       }
-      if (VNX_SEL_ABL == 2) mask = (wt[0] + wt[1] + wt[2] + wt[3] == 12345.f) ? mask : 0u;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
         if (mask & (1u << t))
@@ -598,7 +590,6 @@ msda_bwd_gv_sel_kernel(const int64_t* __restrict__ shapes, const int64_t* __rest
         rn[k] = row < rows ? cnt[row] : 0u;
         ro[k] = row < rows ? offs[row] : 0u;
         if (row < rows) cnt_next[row] = 0;
-        if (VNX_SEL_ABL == 3) rn[k] = rn[k] == 0x7fffffffu ? 1u : 0u;
       }
       const float4_t* g4 = grows + ch4;
 #pragma unroll

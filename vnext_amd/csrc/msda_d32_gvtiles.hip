@@ -32,38 +32,27 @@
 namespace vnx {
 namespace rec {
 
-#ifndef VNX_TILE_ROUNDS
-#define VNX_TILE_ROUNDS 2
-#endif
-#ifndef VNX_TILE_UNITS_PER_CU
-#define VNX_TILE_UNITS_PER_CU 4
-#endif
-// Timing ablations (A/B builds of the development library only; wrong grad_value by construction): 1 = no chunks at all
-// (what set-up + tile selection + the final store cost), 2 = chunks without taps (staging, prefetch and decode only: no
-// rank atomics, no scatter, nothing to apply), 3 = everything but the apply loop.
-#ifndef VNX_GVT_ABL
-#define VNX_GVT_ABL 0
-#endif
-// Workgroup order: 0 = the batch element minor (all B batch elements of a unit on neighbouring workgroups), 1 = major
-// (gv_decode_block_bm).  Round 6, measured both ways (kbench cold + FETCH_SIZE): major fetches less -- 619 against 722 MB per 720p
+// (The kernel's time by parts -- timing ablations of round 4, since removed from the source: DESIGN.md section 3.3c.)
+// Workgroup order: the batch element minor (all B batch elements of a unit on neighbouring workgroups), not major (all units
+// of a batch element before the next one's).  Round 6, measured both ways (kbench cold + FETCH_SIZE): major fetches less --
+// 619 against 722 MB per 720p
 // B = 5 launch, 68.5 against 95.3 at 360p (counter units as reported) -- and is SLOWER: encoder-360p backward 185.5 against
 // 150.9 us, 720p B = 5 716.5 against 575.9, B = 2 308.8 against 257.5, bf16 165.8 against 130.8.  The kernel is bound by issue and
 // LDS, not by what it fetches, and with one batch element resident per XCD its ~90 units all read the same tile words and the
-// same stretch of decoded samples at the same time.  Minor stays.
-#ifndef VNX_GVT_BATCH_MAJOR
-#define VNX_GVT_BATCH_MAJOR 0
-#endif
+// same stretch of decoded samples at the same time.  Minor stays (`units_pb` below is what the
+// batch-major map read and is unused now).
 constexpr int kTileRowsMax = kGvTileRowsMax;      // 256 rows per unit: 4 per 8-lane group
-constexpr int kTileRounds = VNX_TILE_ROUNDS;
+constexpr int kTileRounds = 2;
+constexpr int kTileUnitsPerCu = 4;
 constexpr int kTileWin = kTileRounds * kThreads;  // tile words examined per selection round: 1 024
 constexpr int kTileParts = kTileRounds * kWaves;  // (round, wave) pieces per selection
 constexpr int kTileLevels = 4;                    // the tile words exist for 4 levels x 4 points only (msda_d32.hip, tile mode)
 constexpr size_t kTilesLdsBytes = size_t(kQcMax) * 128 + size_t(kThreads) * 32 + size_t(kTileRowsMax) * 12 + 16 +
                                   8 * kTileLevels * 4 + size_t(kTileWin) * 2 + size_t(kTileParts) * 8 + 16;
-static_assert(kTilesLdsBytes * VNX_TILE_UNITS_PER_CU <= 160 * 1024, "the units that share a CU must fit its LDS");
+static_assert(kTilesLdsBytes * kTileUnitsPerCu <= 160 * 1024, "the units that share a CU must fit its LDS");
 
 template <typename TV, typename TL>
-__global__ void __launch_bounds__(kThreads, VNX_TILE_UNITS_PER_CU * kWaves / 4)
+__global__ void __launch_bounds__(kThreads, kTileUnitsPerCu * kWaves / 4)
 msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
                          const TL* __restrict__ loc, const TL* __restrict__ attn,
                          const uint2_t* __restrict__ summaries, const TV* __restrict__ grad_out,
@@ -84,21 +73,11 @@ msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __re
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // dispatch order = batch element, then cost order (units numbered from the last level back); head <-> XCD map rotating
-  // with the batch element: gv_decode_block_bm (msda_gv_common.h)
-  int unit, b, m;
-#if VNX_GVT_BATCH_MAJOR
-  if (kGvPair16 && sizeof(TV) == 2 && (d.M & 1) == 0) gv_decode_block_bm<true>(blockIdx.x, d.M, units_pb, unit, b, m);
-  else gv_decode_block_bm<false>(blockIdx.x, d.M, units_pb, unit, b, m);
-  if (b >= d.B) return;      // uniform: the padding workgroup of an odd grid
-#else
-  {
-    int rest;
-    if (kGvPair16 && sizeof(TV) == 2 && (d.M & 1) == 0) gv_decode_block<true>(blockIdx.x, d.M, d.B, rest, b, m);
-    else gv_decode_block<false>(blockIdx.x, d.M, d.B, rest, b, m);
-    unit = rest / d.B;
-  }
-#endif
+  // dispatch order = cost order (units numbered from the last level back), the batch element minor; head <-> XCD map
+  // rotating with the batch element: gv_decode_block (msda_gv_common.h)
+  int rest, b, m;
+  gv_decode_block(blockIdx.x, d.M, d.B, rest, b, m);
+  const int unit = rest / d.B;
 
   if (tid < d.L) {     // level table: {H, W, start, workgroups, query pieces, block width, blocks per row, block height}
     const int H = int(shapes[2 * tid]), W = int(shapes[2 * tid + 1]);
@@ -231,7 +210,7 @@ msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __re
     __syncthreads();
 
     // ---- chunks of 128 queries (whole tiles) over the kept tiles ---------------------------------
-    const int n_chunks = (VNX_GVT_ABL == 1 || VNX_GVT_ABL == 4 || VNX_GVT_ABL == 5) ? 0 : ((n_hit << tile_shift) + kQcMax - 1) / kQcMax;
+    const int n_chunks = ((n_hit << tile_shift) + kQcMax - 1) / kQcMax;
     float nx = 0.f, ny = 0.f, na = 0.f;
     bool nvalid = false;
     float4_t pg0 = {0.f, 0.f, 0.f, 0.f}, pg1 = pg0;
@@ -297,7 +276,6 @@ msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __re
           wt[0] = a * (hh * hw); wt[1] = a * (hh * lw); wt[2] = a * (lh * hw); wt[3] = a * (lh * lw);
         }
       }
-      if (VNX_GVT_ABL == 2) mask = (wt[0] + wt[1] + wt[2] + wt[3] == 12345.f) ? mask : 0u;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
         if (mask & (1u << t))
@@ -326,7 +304,6 @@ msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __re
         rn[k] = row < rows ? cnt[row] : 0u;
         ro[k] = row < rows ? offs[row] : 0u;
         if (row < rows) cnt_next[row] = 0;
-        if (VNX_GVT_ABL == 3) rn[k] = rn[k] == 0x7fffffffu ? 1u : 0u;
       }
       const float4_t* g4 = grows + ch4;
 #pragma unroll
@@ -357,8 +334,6 @@ msda_bwd_gv_tiles_kernel(const int64_t* __restrict__ shapes, const int64_t* __re
   const int grp = te >> 3, ch4 = te & 7;
   const uint32_t inv = (65536u + uint32_t(pitch) - 1u) / uint32_t(pitch);      // row / pitch exactly for row < 256
   const int64_t level_elem = ((int64_t(b) * d.S + start) * d.M + m) * D;
-  if (VNX_GVT_ABL == 5) return;                      // (ablation: no final store at all)
-  if (VNX_GVT_ABL == 4 && qsplit > 1) return;        // (ablation: no store of the query pieces' partial rows)
   if (qsplit > 1) {   // a piece of a query-split level: its rows go to its own slab of fp32 partial rows (plain stores, read
                       // back right away by gv_split_finish_kernel, which adds the pieces and writes grad_value)
     float* part = partials + ((int64_t(b) * d.M + m) * gv_partial_rows_bound(d.S, d.L, d.B * d.M) + pbase + int64_t(qpiece) * (Hl * Wl)) * D;
@@ -448,11 +423,9 @@ size_t msda_gvtiles_partial_bytes(const MsdaDims& d) {
 // vnx_debug_gvtiles_units on random pyramids -- and
 // 4 * (pieces - 1) for the query pieces of levels of at most four units.  Workgroups past the real count exit at once;
 // they are the LAST of the grid (units are numbered from the coarsest level back) and overlap the real ones: forcing the
-// exact count (42 per (batch, head) at 360p, the bound is 124) changes nothing, 300 costs 4 us (tools/r3_call28.sh).
+// exact count (42 per (batch, head) at 360p, the bound is 124) changes nothing, 300 costs 4 us (round 3, an A/B
+// build that forced the bound).
 int msda_gvtiles_units_bound(const MsdaDims& d, int units_min) {
-#ifdef VNX_TILES_BOUND_FORCE      // A/B build: what the workgroups past the real unit count cost (valid for ONE shape only)
-  return VNX_TILES_BOUND_FORCE;
-#endif
   const int qs = gv_query_splits(1, d.Lq, d.P, true, d.B * d.M);
   return d.L * (units_min + 2) + 3 * ((d.S + rec::kTileRowsMax - 1) / rec::kTileRowsMax) + d.L * 4 * (qs - 1);
 }

@@ -56,27 +56,15 @@ template <typename TV> __device__ __forceinline__ void store4(TV* p, float4_t v)
 template <> __device__ __forceinline__ void store4<float>(float* p, float4_t v) {
   // grad_value is written once and read by another kernel much later: `nt` (decoder-360p backward 33.8 -> 31.4 us)
   // (same WRITE_SIZE / FETCH_SIZE per launch as plain stores; rocprofv3 18.9 vs 20.0 us for this kernel)
-#if defined(VNX_GV_STORE_POLICY) && VNX_GV_STORE_POLICY == 1      // A/B (round 6): cache policy of the row stores, for the step (fwd behind bwd)
-  asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" : : "v"(p), "v"(v) : "memory");
-#elif defined(VNX_GV_STORE_POLICY) && VNX_GV_STORE_POLICY == 2
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" : : "v"(p), "v"(v) : "memory");
-#elif defined(VNX_GV_STORE_POLICY) && VNX_GV_STORE_POLICY == 3
-  asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
-#elif defined(VNX_GV_STORE_POLICY) && VNX_GV_STORE_POLICY == 4
-  *reinterpret_cast<float4_t*>(p) = v;
-#else
+  // Tried, measured, not adopted (round 6, the bench's fwd + bwd step: does the forward behind a backward run faster if the rows
+  // are written through?): `sc1 nt` / `sc0 sc1 nt` / `sc0 sc1` 7.25 / 7.25 / 6.60 against 7.46 Gpoints/s
   __builtin_nontemporal_store(v, reinterpret_cast<float4_t*>(p));
-#endif
 }
 template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, float4_t v) {
   uint2_t r;
   r.x = f32x2_to_bf16x2(v.x, v.y);
   r.y = f32x2_to_bf16x2(v.z, v.w);
-#if defined(VNX_GV_STORE16_PLAIN) || (defined(VNX_GV_PAIR16) && !defined(VNX_GV_PAIR16_NT))      // A/B builds (tools/r3_call23.sh, r3_call33.sh)
-  *reinterpret_cast<uint2_t*>(p) = r;
-#else
   __builtin_nontemporal_store(r, reinterpret_cast<uint2_t*>(p));
-#endif
 }
 template <> __device__ __forceinline__ void store4<f16_t>(f16_t* p, float4_t v) {
   uint2_t r;
@@ -85,54 +73,21 @@ template <> __device__ __forceinline__ void store4<f16_t>(f16_t* p, float4_t v) 
   __builtin_nontemporal_store(r, reinterpret_cast<uint2_t*>(p));
 }
 
-// Workgroup -> (unit x batch index `rest`, head).  fp32: blockIdx % M picks the head (= the XCD when M == 8), rotated
-// by the batch element (msda_d32.hip).  16-bit values (VNX_GV_PAIR16): a row is 64 B, HALF a cache line, the other half
-// is the next head's row -- written by another XCD each half is a partial-line write (grad_value kernel at decoder-720p:
-// 36.5 us in bf16 against 32.1 in fp32 for half the bytes, no extra traffic by PMC).  So a PAIR of heads shares an XCD
-// (XCDs x and x + M/2 split the units of the pair between them), neighbouring workgroups of an XCD take the two heads of
-// one unit, and the rows are written with plain stores: the two halves meet in that XCD's L2 and leave as one line.
-template <bool PAIR>
+// Workgroup -> (unit x batch index `rest`, head): blockIdx % M picks the head (= the XCD when M == 8), rotated by the batch
+// element (msda_d32.hip).
+// Tried, measured, not adopted (round 3), for 16-bit values: a row is 64 B, HALF a cache line, the other half is the next
+// head's row -- written by another XCD each half is a partial-line write (grad_value kernel at decoder-720p: 36.5 us in bf16
+// against 32.1 in fp32 for half the bytes, no extra traffic by PMC).  The A/B forms -- plain stores, and a PAIR of heads
+// sharing an XCD so that the halves meet in that XCD's L2 -- took 53.3 / 49.4-55.2 us per decoder-720p backward against
+// 48.9: the cause was the conversion arithmetic, not partial-line writes.
+// Also not adopted: the same map with the BATCH ELEMENT major in the tile-fed kernel (round 6: 23 % slower, DESIGN.md
+// section 3.3h).
 __device__ __forceinline__ void gv_decode_block(uint32_t block, int M, int B, int& rest, int& b, int& m) {
-  const int x = int(block % uint32_t(M)), j = int(block / uint32_t(M));
-  if constexpr (PAIR) {
-    const int half = M >> 1;
-    const int xh = x % half, side = x / half;
-    rest = (j >> 1) * 2 + side;
-    b = rest % B;
-    m = 2 * ((xh + b) % half) + (j & 1);
-  } else {
-    rest = j;
-    b = rest % B;
-    m = (x + b) % M;
-  }
+  const int x = int(block % uint32_t(M));
+  rest = int(block / uint32_t(M));
+  b = rest % B;
+  m = (x + b) % M;
 }
-// The same map with the BATCH ELEMENT major (round 6; the tile-fed kernel): workgroup -> (batch element, unit), all
-// `units_pb` units of a batch element before the next one's.  The workgroups resident on an XCD at one time then belong to
-// one or two batch elements, whose grad_out rows, decoded samples and tile words of the XCD's head class (6 MB per batch
-// element at 720p) are re-read from that XCD's 4-MB L2 by neighbouring units instead of from memory: with the batch element
-// minor every resident group of units spans all B of them (the change that cut the slab forward's reads 929 -> 379 MB).
-// b may come out as B for the padding workgroup of an odd grid: the caller leaves.
-template <bool PAIR>
-__device__ __forceinline__ void gv_decode_block_bm(uint32_t block, int M, int units_pb, int& unit, int& b, int& m) {
-  const int x = int(block % uint32_t(M)), j = int(block / uint32_t(M));
-  if constexpr (PAIR) {
-    const int half = M >> 1;
-    const int xh = x % half, side = x / half;
-    const int rest = (j >> 1) * 2 + side;
-    b = rest / units_pb;
-    unit = rest - b * units_pb;
-    m = 2 * ((xh + b) % half) + (j & 1);
-  } else {
-    b = j / units_pb;
-    unit = j - b * units_pb;
-    m = (x + b) % M;
-  }
-}
-#ifdef VNX_GV_PAIR16
-constexpr bool kGvPair16 = true;
-#else
-constexpr bool kGvPair16 = false;
-#endif
 
 // The value again, but opaque to the optimiser: what is derived from the result is recomputed where it is used instead of
 // being hoisted out of the loops and then SPILLED (the selection kernel kept `tid | 0x200`, `tid >> 2`, `tid * 4`, ... live
@@ -167,9 +122,7 @@ constexpr int kRowsMax = kGvRowsMax;        // 320 rows: 40 KiB as an LDS slab
 constexpr int kQcMax = 128;                 // queries per chunk (16 KiB of grad_out rows in LDS)
 constexpr int kLevelsMax = 64;
 
-#ifndef VNX_SEL_UNITS_PER_CU
-#define VNX_SEL_UNITS_PER_CU 3
-#endif
+constexpr int kSelUnitsPerCu = 3;          // workgroups of the selection kernel a CU holds (its launch bounds)
 
 }  // namespace rec
 }  // namespace vnx

@@ -1,5 +1,5 @@
 // msda_units.h -- the MSDA kernels' shared host/device definitions: the call's sizes, the grad_value unit geometry with its
-// tuning macros, and the fused prologue's arguments.  Included by msda_launchers.h and msda_gv_common.h; nothing outside the
+// tuning constants, and the fused prologue's arguments.  Included by msda_launchers.h and msda_gv_common.h; nothing outside the
 // MSDA files needs it.
 #pragma once
 #include "vnx_common.h"
@@ -47,18 +47,10 @@ __device__ __forceinline__ float fused_ref(const FusedArgs& fa, int64_t i) {
 // grad_loc kernel zeroed.  NOT at the decoder shape: there the kernel lasts 15 us, the contended,
 // L2-bypassing atomics cost each piece 12-25 us, and the backward went from 32 to 49 us.
 // fp32 grad_value and 4 points per level only (the selection kernel); 1 = no split.
-#ifndef VNX_QS_COARSE
-#define VNX_QS_COARSE 4         // query pieces of a coarse level (<= 2 row-units) at most, from 32 (batch, head) pairs up
-#endif
-#ifndef VNX_QS_COARSE_SMALL
-#define VNX_QS_COARSE_SMALL 16  // ... with fewer pairs (the grid does not fill the chip: more, shorter pieces)
-#endif
-#ifndef VNX_QS_MID
-#define VNX_QS_MID 2
-#endif
-#ifndef VNX_QS_CHUNKS
-#define VNX_QS_CHUNKS 10      // a piece is given about this many chunks of 128 queries
-#endif
+constexpr int kQsCoarse = 4;        // query pieces of a coarse level (<= 2 row-units) at most, from 32 (batch, head) pairs up
+constexpr int kQsCoarseSmall = 16;  // ... with fewer pairs (the grid does not fill the chip: more, shorter pieces)
+constexpr int kQsMid = 2;
+constexpr int kQsChunks = 10;       // a piece is given about this many chunks of 128 queries
 // batch_heads = B x M: with fewer than 32 (batch, head) pairs the grid leaves workgroup slots empty, and the middle
 // levels are split further: 8 pieces instead of 2 (round 2: 4 -- encoder backward at B = 2 123 -> 109 us at 360p, 450 ->
 // 412 us at 720p; round 3, tile-fed path: 8 pieces 322 -> 288 us at 720p B = 2, 234 -> 192 us at B = 1, 360p unchanged; 16
@@ -109,31 +101,21 @@ __host__ __device__ inline GvSplit gv_level_split(int n, int units_min, int rows
 
 // Units of the self-decoding grad_value kernel (msda_d32_gvdirect.hip; calls below 1 024 queries -- the decoders').  A unit is
 // a pixel range of one level and reads + decodes the level's samples of ALL queries itself, so what the kernel fetches grows
-// with the number of units (every one of them stages all grad_out rows of its head): units are LARGE -- up to VNX_GVD_ROWS
+// with the number of units (every one of them stages all grad_out rows of its head): units are LARGE -- up to kGvdRows
 // rows, 10 per (batch, head) at 360p -- and hold no rows in registers: after one sort an 8-lane group walks its rows one
 // after the other and stores each at once.  Every level receives the same number of taps (4 x points x queries) whatever
 // its size, so a row of a coarse level (80 taps at the 60-pixel level of a 300-query call) is spread over 1 << gshift
 // adjacent groups whose partial sums meet in registers; `ut` (gvd_units_min) cuts such a level in two when the grid has room.
-#ifndef VNX_GVD_QC
-#define VNX_GVD_QC 304            // queries staged per pass (all 300 of a decoder call): 19 KiB of grad_out row halves in LDS
-#endif
-#ifndef VNX_GVD_ROWS
-#define VNX_GVD_ROWS 768          // rows of a unit at most (what the kernel's LDS holds); the launchers choose <= this per call (gvd_rows_max)
-#endif
-#ifndef VNX_GVD_ROWS_LARGE
-#define VNX_GVD_ROWS_LARGE 640    // ... for pyramids above VNX_GVD_SMALL_S pixels
-#endif
-#ifndef VNX_GVD_SMALL_S
-#define VNX_GVD_SMALL_S 8192
-#endif
-#ifndef VNX_GVD_ONE_ROUND
-#define VNX_GVD_ONE_ROUND 832     // workgroups resident at once -- 3 per CU x 256 CUs = 768 -- plus a twelfth: the T = 5 decoder call with
+constexpr int kGvdQc = 304;         // queries staged per pass (all 300 of a decoder call): 19 KiB of grad_out row halves in LDS
+constexpr int kGvdRows = 768;       // rows of a unit at most (what the kernel's LDS holds); the launchers choose <= this per call (gvd_rows_max)
+constexpr int kGvdRowsLarge = 640;  // ... for pyramids above kGvdSmallS pixels
+constexpr int kGvdSmallS = 8192;
+constexpr int kGvdOneRound = 832;   // workgroups resident at once -- 3 per CU x 256 CUs = 768 -- plus a twelfth: the T = 5 decoder call with
                                   // its small levels cut in two is 440 + 375 = 815 workgroups, and in the bench's fwd + bwd step that
                                   // is the best split measured (round 6, the product library built each way, same box: 7.73-7.76
                                   // Gpoints/s against 7.45-7.47 uncut -- the uncut call's longest units, whole coarse levels, end the
                                   // launch alone on their CUs and hold the next launch back -- 6.80 with three units per level, 6.45
                                   // with four; backward-only sequences prefer the uncut call, 19.5 against 21.5 us)
-#endif
 struct GvdSplit { int units, rpu, gshift; };
 // Units per level at least.  A level that fits one unit (the 240- and 60-pixel levels at 360p) receives as many taps as a
 // whole fine level, so its unit is the call's longest: when the grid has room for it in ONE round of resident workgroups such
@@ -144,8 +126,8 @@ struct GvdSplit { int units, rpu, gshift; };
 // first, 19.5 with the grad_value groups first once everything is resident in one round; B = 10 35.4 -> 33.1), 640 at the
 // 720p pyramid (S = 19 560: 35.1 against 40.3 us with 768 -- there a unit's time is its rows' stores).
 __host__ __device__ inline int gvd_rows_max(int S) {
-  const int r = S <= VNX_GVD_SMALL_S ? VNX_GVD_ROWS : VNX_GVD_ROWS_LARGE;
-  return r < VNX_GVD_ROWS ? r : VNX_GVD_ROWS;
+  const int r = S <= kGvdSmallS ? kGvdRows : kGvdRowsLarge;
+  return r < kGvdRows ? r : kGvdRows;
 }
 // Units per (batch, head) the launchers expect (an estimate for tuning choices: the host knows S and L, not the level sizes;
 // pyramids whose levels shrink four-fold need S / rows + L - 1)
@@ -154,7 +136,7 @@ __host__ __device__ inline int gvd_units_min(int S, int L, int batch_heads, int 
   // (the host knows S and L, not the level sizes: S / ROWS + L bounds the units of the 640-row split; the levels that gain a
   //  unit are the one or two smallest -- a heuristic for a tuning choice, any value is correct)
   //  `other_workgroups`: what shares the round with the units -- the grad_loc workgroups of the paired kernel, msda_d32.hip)
-  return int64_t(batch_heads) * (gvd_units_estimate(S, L, rows) + 2) + other_workgroups <= VNX_GVD_ONE_ROUND ? 2 : 1;
+  return int64_t(batch_heads) * (gvd_units_estimate(S, L, rows) + 2) + other_workgroups <= kGvdOneRound ? 2 : 1;
 }
 __host__ __device__ inline GvdSplit gvd_level_split(int n, int ut, int Lq, int P, int rows_max) {
   GvdSplit s{0, 1, 0};
@@ -165,15 +147,15 @@ __host__ __device__ inline GvdSplit gvd_level_split(int n, int ut, int Lq, int P
   s.rpu = (n + units - 1) / units;
   s.units = (n + s.rpu - 1) / s.rpu;
   // taps a row expects: 4 x points x (queries of a pass) / pixels of the level; from 16 up a row takes 2 groups, 32: 4, 64: 8.
-  // A pass stages min(VNX_GVD_QC, 4 * VNX_GVD_QC / P) queries (the kernel's qc), so taps <= 16 * VNX_GVD_QC = kGvdCap; a
+  // A pass stages min(kGvdQc, 4 * kGvdQc / P) queries (the kernel's qc), so taps <= 16 * kGvdQc = kGvdCap; a
   // gshift g >= 1 means taps >= (8 << g) * n, so rpu << g <= n << g <= kGvdCap / 8 -- inside the walk's kIters rounds.  (Taken
-  // over the whole call, 4 x P x min(Lq, VNX_GVD_QC), it overcounted a pass from 5 points up: rows past slot 768 were lost.)
-  const int qc = VNX_GVD_QC < 4 * VNX_GVD_QC / P ? VNX_GVD_QC : 4 * VNX_GVD_QC / P;
+  // over the whole call, 4 x P x min(Lq, kGvdQc), it overcounted a pass from 5 points up: rows past slot 768 were lost.)
+  const int qc = kGvdQc < 4 * kGvdQc / P ? kGvdQc : 4 * kGvdQc / P;
   const int64_t taps = int64_t(4) * P * (Lq < qc ? Lq : qc);
   while (s.gshift < 3 && taps >= (int64_t(16) << s.gshift) * n) ++s.gshift;
-  // the walk covers VNX_GVD_ROWS slots of a unit (rows << gshift): fewer groups on a row is always correct, a row past the
+  // the walk covers kGvdRows slots of a unit (rows << gshift): fewer groups on a row is always correct, a row past the
   // last slot is never stored
-  while (s.gshift > 0 && (s.rpu << s.gshift) > VNX_GVD_ROWS) --s.gshift;
+  while (s.gshift > 0 && (s.rpu << s.gshift) > kGvdRows) --s.gshift;
   return s;
 }
 
@@ -189,20 +171,16 @@ __host__ __device__ inline GvdSplit gvd_level_split(int n, int ut, int Lq, int P
 // Very flat levels (H < 8) get wider blocks so that the unit count stays ~ n / rows_max.  At least units_min units per
 // level when it has the rows.
 // Unit u of a level: block (u % nbx, u / nbx), pixels [bx * bw, ..) x [by * bh, ..), clipped to the level.
-#ifndef VNX_GV_BLOCK_MINW
-#define VNX_GV_BLOCK_MINW 32
-#endif
-#ifndef VNX_GV_BLOCK_W
-#define VNX_GV_BLOCK_W 32
-#endif
+constexpr int kGvBlockMinW = 32;
+constexpr int kGvBlockW = 32;
 struct GvGrid { int nbx, nby, bw, bh; };
 __host__ __device__ inline GvGrid gv_level_grid(int H, int W, int units_min, int rows_max) {
   GvGrid g{1, 1, 1, 1};
   if (H <= 0 || W <= 0) { g.nbx = g.nby = 0; return g; }
-  if (W < VNX_GV_BLOCK_MINW && W <= rows_max) {
+  if (W < kGvBlockMinW && W <= rows_max) {
     g.nbx = 1; g.bw = W;
   } else {
-    const int target = H >= rows_max / VNX_GV_BLOCK_W ? VNX_GV_BLOCK_W : rows_max / H;       // flat levels: wider blocks
+    const int target = H >= rows_max / kGvBlockW ? kGvBlockW : rows_max / H;       // flat levels: wider blocks
     g.nbx = (W + target - 1) / target;
     g.bw = (W + g.nbx - 1) / g.nbx;
     g.nbx = (W + g.bw - 1) / g.bw;
@@ -233,11 +211,11 @@ __host__ __device__ inline int gv_level_units(int H, int W, int units_min, bool 
 __host__ __device__ inline int gv_query_splits(int row_units, int Lq, int P, bool f32, int batch_heads) {
   if (!f32 || P != 4 || row_units > 4 || Lq < 1024) return 1;
   const int chunks = (Lq + 127) / 128;
-  const int qs = (chunks + VNX_QS_CHUNKS - 1) / VNX_QS_CHUNKS;
+  const int qs = (chunks + kQsChunks - 1) / kQsChunks;
   // round 4, pieces meeting in partial rows (no atomics): coarse cap 8 -> 4 from 32 pairs up (encoder-720p B = 5 611 -> 600 us;
   // 360p has 4 pieces either way), 8 -> 16 below (720p B = 2 272.7 -> 263.9 us; 16 at B = 5: 628 us, 4 at B = 2: 332 us)
-  const int mid = batch_heads < 32 ? 4 * VNX_QS_MID : VNX_QS_MID;
-  const int coarse = batch_heads < 32 ? VNX_QS_COARSE_SMALL : VNX_QS_COARSE;
+  const int mid = batch_heads < 32 ? 4 * kQsMid : kQsMid;
+  const int coarse = batch_heads < 32 ? kQsCoarseSmall : kQsCoarse;
   const int cap = row_units > 2 ? mid : coarse;          // middle levels: 3-4 row-units (960 pixels at 360p)
   return qs < 1 ? 1 : (qs > cap ? cap : qs);
 }
@@ -251,19 +229,19 @@ __host__ __device__ inline int gv_query_splits(int row_units, int Lq, int P, boo
 // split level l in order, qs_l pieces x n_l pixels x 32 floats, starting at row  sum_{l' < l} qs_l' n_l'.
 // A split level has at most 4 units of at most kGvTileRowsMax pixels (gv_query_splits), at most this many pieces:
 __host__ __device__ inline int gv_split_pieces_max(int batch_heads) {          // = the caps of gv_query_splits
-  const int mid = batch_heads < 32 ? 4 * VNX_QS_MID : VNX_QS_MID;
-  const int coarse = batch_heads < 32 ? VNX_QS_COARSE_SMALL : VNX_QS_COARSE;
+  const int mid = batch_heads < 32 ? 4 * kQsMid : kQsMid;
+  const int coarse = batch_heads < 32 ? kQsCoarseSmall : kQsCoarse;
   return mid > coarse ? mid : coarse;
 }
 // A split level is either coarse (<= 2 units: <= 2 x 256 pixels, `coarse` pieces) or middle (3-4 units: <= 4 x 256 pixels,
 // `mid` pieces), never both: a level contributes at most max(512 coarse, 1024 mid) rows, and all of them at most S x the
 // larger piece count.  (Until round 4 the bound was min(S, 1024 L) x max(mid, coarse): twice this, 134 MB at B = 2 for the
 // ~25 MB the pieces write, allocated by every backward call -- ADVICE r4.)
-static_assert(VNX_QS_MID <= VNX_QS_COARSE && 4 * VNX_QS_MID <= VNX_QS_COARSE_SMALL,
+static_assert(kQsMid <= kQsCoarse && 4 * kQsMid <= kQsCoarseSmall,
               "msda_gvtiles_units_bound counts the extra workgroups of the split levels with the COARSE cap");
 __host__ __device__ inline int64_t gv_partial_rows_bound(int S, int L, int batch_heads) {      // partial rows per (batch, head), an upper bound
-  const int64_t mid = batch_heads < 32 ? 4 * VNX_QS_MID : VNX_QS_MID;
-  const int64_t coarse = batch_heads < 32 ? VNX_QS_COARSE_SMALL : VNX_QS_COARSE;
+  const int64_t mid = batch_heads < 32 ? 4 * kQsMid : kQsMid;
+  const int64_t coarse = batch_heads < 32 ? kQsCoarseSmall : kQsCoarse;
   const int64_t per_level_c = int64_t(2) * kGvTileRowsMax * coarse, per_level_m = int64_t(4) * kGvTileRowsMax * mid;
   const int64_t by_levels = int64_t(L) * (per_level_c > per_level_m ? per_level_c : per_level_m);
   const int64_t by_pixels = int64_t(S) * (coarse > mid ? coarse : mid);

@@ -197,7 +197,7 @@ struct KernelVariant {
   int rec_stamps = 0, rec_form = 0;  // the record-fed kernel's phase stamps (debug mode) and form (launch_gvrec's mode)
   bool tile_copy = false;            // tile path: the grad_loc kernel leaves a compact copy of the locations / weights
   bool fork = false, no_pair = false;      // self-decoding path: grad_value on the side stream, as VNX_MSDA_FORK asks; two launches where the paired kernel would run
-  int pair_order = -1;               // the paired kernel's role order; -1 = VNX_PAIR_ORDER
+  int pair_order = -1;               // the paired kernel's role order (msda_d32.hip); -1 = the launcher's choice
   // the gather form of the grad_loc kernel where the slab form would run; the slab form of the fused one (measured, not the product path)
   bool no_slab_backward = false, fused_slab_backward = false;
   // the mask head's forward (mask_head.hip)
