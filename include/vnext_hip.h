@@ -942,6 +942,48 @@ int vnx_resize_ingest_frames(const void* pixels, size_t pixel_bytes, const void*
                              float mean1, float mean2, float std0, float std1, float std2, int channels_last,
                              int interleaved, void* x, void* mask, void* hip_stream);
 
+/*
+ * Training-time augmentation on the device (augment.hip): crop, Pillow's bilinear resize and a horizontal flip of uint8
+ * source frames into x and mask, and the same geometry applied to the ground-truth masks straight from their COCO run
+ * lengths, with the masks' boxes.  ADDITIVE: three symbols, no existing signature changed, so VNX_ABI_VERSION stays 17.
+ *
+ * vnx_augment_frames: the arguments, outputs and guarantees of vnx_resize_ingest_frames (the same device code), with wider
+ * rows.  src_table: int32 device [batch][8] = {byte offset, h, w, x0, y0, cw, ch, flip}: the crop window of cw x ch pixels
+ * at (x0, y0) inside the h x w frame, and flip != 0 for a horizontal flip of the RESIZED window (output column x takes
+ * resized column nw - 1 - x, as np.flip(resized, axis=1)).  The rows of pixels keep the pitch w (CHW: plane stride h * w).
+ * coeffs: its first 8 * batch words are a row per frame: the two triples of vnx_resize_ingest_frames, for (cw -> nw) and
+ * (ch -> nh), then the word offsets of the frame's two NEAREST index tables, int32 [nw] of (cw -> nw) and int32 [nh] of
+ * (ch -> nh) (read by vnx_augment_masks only).  A window that leaves the frame makes an empty frame, like every other
+ * malformed row.  A row with the full window and flip 0 gives what vnx_resize_ingest_frames gives, bit for bit.
+ *
+ * vnx_augment_masks: n_masks (instance, frame) masks of a step.  ends: int32 device [n_ends], the masks' run END positions
+ * back to back: per mask the cumulative sums of its COCO counts (column-major positions p = x * h + y; runs of zeros and
+ * ones alternate, zeros first; zero-length runs are legal).  mask_rows: int32 device [n_masks][4] = {offset of the mask's
+ * ends, n_runs, frame index, byte offset of the mask's output inside masks}.  src_table, dst_table, coeffs: the tables of
+ * vnx_augment_frames for the n_frames frames (dst_table [n_frames][3] = {0, nh, nw}).  height, width: the padded size,
+ * multiples of 32 (it sizes the launch; nh <= height, nw <= width).  Output pixel (y, x) of a mask is the value of source
+ * pixel (y0 + ytab[y], x0 + xtab[flip ? nw - 1 - x : x]): the parity of the number of ends <= xs * h + ys.  The nearest
+ * tables are Pillow's, which accumulates them in double (tab[i] = int(xo); xo += n_in / n_out, from xo = 0.5 * n_in /
+ * n_out): the host makes them; the kernel only reads them, clamped to the window.
+ *   masks uint8 / bool, mask_bytes bytes: mask m is [nh][nw] of its frame at its row's byte offset; every byte of it written.
+ *   boxes fp32 [n_masks][4] = {min x, min y, max x + 1, max y + 1} over the mask's set pixels; nonempty uint8 [n_masks].
+ *   An empty mask gives a zero box and nonempty 0.
+ * n_runs == 1 is the empty mask.  Runs outside ends, or whose last end is not h * w, are taken as the empty mask; a row that
+ * names no frame, a malformed frame or an output range outside masks writes no mask bytes and gives a zero box.  No read
+ * leaves a buffer whatever the tables hold.  workspace: vnx_augment_masks_workspace(n_masks, height, width) bytes, 16-byte
+ * aligned (16 bytes per (mask, 32 x 32 tile): the tiles' boxes; every slot is written, no memset).  Two launches; no
+ * atomics, no allocation, no synchronisation: capturable, and bit-identical run to run.  n_masks == 0: VNX_OK, no launch.
+ */
+int vnx_augment_frames(const void* pixels, size_t pixel_bytes, const void* src_table, const void* dst_table,
+                       const void* coeffs, size_t coeff_words, int batch, int height, int width, float mean0, float mean1,
+                       float mean2, float std0, float std1, float std2, int channels_last, int interleaved, void* x,
+                       void* mask, void* hip_stream);
+size_t vnx_augment_masks_workspace(int n_masks, int height, int width);
+int vnx_augment_masks(const void* ends, size_t n_ends, const void* mask_rows, int n_masks, const void* src_table,
+                      const void* dst_table, const void* coeffs, size_t coeff_words, int n_frames, int height, int width,
+                      void* masks, size_t mask_bytes, void* boxes, void* nonempty, void* workspace, size_t workspace_bytes,
+                      void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

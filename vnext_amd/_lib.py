@@ -101,6 +101,9 @@ SIGNATURES = {
                                ctypes.POINTER(_vp), _vp]),
     "vnx_resize_ingest_frames": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i] + [ctypes.c_float] * 6 +
                                  [_i, _i, _vp, _vp, _vp]),
+    "vnx_augment_frames": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i] + [ctypes.c_float] * 6 + [_i, _i, _vp, _vp, _vp]),
+    "vnx_augment_masks_workspace": (_sz, [_i, _i, _i]),
+    "vnx_augment_masks": (_i, [_vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

@@ -33,240 +33,9 @@
 // the horizontal pass of the rows they share: at 720 -> 360 a tile stages 66 source rows for 64 of its own, 3 % recomputed
 // (99 for 96 at 3x); neighbouring columns share source bytes (through the caches) but no arithmetic.
 // Every element of x and mask is written by exactly one thread: no memset, no atomics, plain vector stores.
-#include "vnx_common.h"
-
-#pragma clang fp contract(off)
-
-namespace vnx {
-namespace {
-
-constexpr int kResizeThreads = 256;
-constexpr int kTile = 32;                  // output rows and columns of a workgroup
-constexpr int kMaxKsize = 17;              // VNX_RESIZE_MAX_KSIZE
-constexpr int kMaxRows = 272;              // staged source rows of a tile: (kTile + 1) * 8 + 1 at the limit, rounded up
-
-typedef uint32_t rsz_u4 __attribute__((ext_vector_type(4)));
-
-struct ResizeArgs {
-  const unsigned char* pixels;
-  long long pixel_bytes;
-  const int32_t* src_table;
-  const int32_t* dst_table;
-  const int32_t* coeffs;
-  long long coeff_words;
-  float* x;
-  unsigned char* mask;
-  int B, H, W, channels_last, interleaved;
-  float mean[3], std[3];
-};
-
-struct AxisTab { int bounds, kk, ksize; };      // ksize 0: the pass is skipped
-
-struct ResizeGeom {
-  int off, h, w, nh, nw;      // nh == 0: the empty frame
-  AxisTab hor, ver;
-};
-
-// one axis of a frame's coefficient row: inside the buffer for n_out rows of bounds and weights, or a skipped pass
-__device__ __forceinline__ bool axis_ok(const AxisTab t, int n_in, int n_out, long long words) {
-  if (t.ksize == 0) return n_in == n_out;
-  return t.ksize >= 1 && t.ksize <= kMaxKsize && t.bounds >= 0 && t.kk >= 0 && (long long)t.bounds + 2ll * n_out <= words &&
-         (long long)t.kk + (long long)n_out * t.ksize <= words;
-}
-
-// frame `b` as the tables describe it, or the empty frame
-__device__ __forceinline__ ResizeGeom resize_geom(const ResizeArgs& a, int b) {
-  ResizeGeom g;
-  g.off = a.src_table[3 * b]; g.h = a.src_table[3 * b + 1]; g.w = a.src_table[3 * b + 2];
-  const int zero = a.dst_table[3 * b];
-  g.nh = a.dst_table[3 * b + 1]; g.nw = a.dst_table[3 * b + 2];
-  const int32_t* row = a.coeffs + 6 * size_t(b);      // (the host checked 6 * B <= coeff_words)
-  g.hor = AxisTab{row[0], row[1], row[2]};
-  g.ver = AxisTab{row[3], row[4], row[5]};
-  const bool ok = g.off >= 0 && g.h >= 1 && g.w >= 1 && (long long)g.off + 3ll * g.h * g.w <= a.pixel_bytes && zero >= 0 &&
-                  g.nh >= 1 && g.nw >= 1 && g.nh <= a.H && g.nw <= a.W && axis_ok(g.hor, g.w, g.nw, a.coeff_words) &&
-                  axis_ok(g.ver, g.h, g.nh, a.coeff_words);
-  if (!ok) g.nh = g.nw = 0;
-  return g;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// byte `at` (inside the buffer) through the aligned word around it; `cur` / `word` remember the last word fetched
-__device__ __forceinline__ uint32_t source_byte(const unsigned char* __restrict__ pixels, long long pixel_bytes, long long at,
-                                                long long& cur, uint32_t& word) {
-  const long long lo = at & ~3ll;
-  if (lo != cur) {
-    cur = lo;
-    if (lo + 4 <= pixel_bytes) {      // `pixels` is 4-byte aligned
-      word = *reinterpret_cast<const uint32_t*>(pixels + lo);
-    } else {                          // the buffer's last bytes
-      word = 0;
-      for (int j = 0; j < 4; ++j)
-        if (lo + j < pixel_bytes) word |= uint32_t(pixels[lo + j]) << (8 * j);
-    }
-  }
-  return (word >> (8 * int(at & 3))) & 0xffu;
-}
-
-__global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char rows[3][kMaxRows][kTile];
-  __shared__ uint32_t kh[kTile][kMaxKsize], kv[kTile][kMaxKsize];
-  __shared__ int bh[kTile][2], bv[kTile][2];      // {first source column, taps}; {first staged row, taps}
-
-  const int H = a.H, W = a.W, tid = threadIdx.x;
-  const int tiles_x = W / kTile, tiles_y = H / kTile;
-  const int tx = blockIdx.x % tiles_x;
-  const int rest = blockIdx.x / tiles_x;
-  const int ty = rest % tiles_y, b = rest / tiles_y;
-  const int ox0 = tx * kTile, oy0 = ty * kTile;
-  const ResizeGeom g = resize_geom(a, b);                  // workgroup-uniform
-  const bool live = oy0 < g.nh && ox0 < g.nw;              // the tile holds pixels of the frame
-
-  if (live) {
-    const int rows_out = min(kTile, g.nh - oy0), cols_out = min(kTile, g.nw - ox0);
-    // the source rows this tile's output rows reach: [r0, r1)
-    int r0, r1;
-    if (g.ver.ksize == 0) {
-      r0 = oy0; r1 = oy0 + rows_out;                       // nh == h
-    } else {
-      const int32_t* bnd = a.coeffs + g.ver.bounds;
-      const int last = oy0 + rows_out - 1;
-      r0 = clampi(bnd[2 * oy0], 0, g.h);
-      r1 = clampi(clampi(bnd[2 * last], 0, g.h) + clampi(bnd[2 * last + 1], 0, g.ver.ksize), r0, g.h);
-      if (r1 - r0 > kMaxRows) r1 = r0 + kMaxRows;
-    }
-    // ---- stage the tile's bounds and weights ----
-    if (tid < kTile) {
-      int first = 0, cnt = 0;
-      if (tid < cols_out) {
-        if (g.hor.ksize == 0) { first = ox0 + tid; cnt = 1; }
-        else {
-          const int32_t* bnd = a.coeffs + g.hor.bounds + 2 * (ox0 + tid);
-          first = clampi(bnd[0], 0, g.w);
-          cnt = clampi(bnd[1], 0, min(g.hor.ksize, g.w - first));
-        }
-      }
-      bh[tid][0] = first; bh[tid][1] = cnt;
-    } else if (tid < 2 * kTile) {
-      const int r = tid - kTile;
-      int first = 0, cnt = 0;
-      if (r < rows_out) {
-        if (g.ver.ksize == 0) { first = r; cnt = 1; }
-        else {
-          const int32_t* bnd = a.coeffs + g.ver.bounds + 2 * (oy0 + r);
-          const int y = clampi(bnd[0], r0, r1);
-          first = y - r0;
-          cnt = clampi(bnd[1], 0, min(g.ver.ksize, r1 - y));
-        }
-      }
-      bv[r][0] = first; bv[r][1] = cnt;
-    }
-    for (int i = tid; i < 2 * kTile * kMaxKsize; i += kResizeThreads) {
-      const bool vert = i >= kTile * kMaxKsize;
-      const int j = vert ? i - kTile * kMaxKsize : i;
-      const int r = j / kMaxKsize, t = j - r * kMaxKsize;
-      const AxisTab tab = vert ? g.ver : g.hor;
-      const int idx = (vert ? oy0 : ox0) + r;
-      const bool have = r < (vert ? rows_out : cols_out) && t < tab.ksize;
-      const uint32_t k = have ? uint32_t(a.coeffs[tab.kk + (long long)idx * tab.ksize + t]) : 0u;
-      (vert ? kv : kh)[r][t] = k;
-    }
-    __syncthreads();
-
-    // ---- phase H: source rows [r0, r1) at the tile's columns -> bytes in LDS ----
-    const int col = tid & (kTile - 1), sub = tid >> 5;      // 8 rows at a time
-    const int first = bh[col][0], cnt = bh[col][1];
-    const int n_rows = r1 - r0;
-    const long long plane = (long long)g.h * g.w;
-    const int step = a.interleaved ? 3 : 1;
-    for (int c = 0; c < 3; ++c) {
-      for (int r = sub; r < n_rows; r += kResizeThreads / kTile) {
-        uint32_t u = 0;
-        if (col < cols_out) {
-          const long long px = (long long)(r0 + r) * g.w + first;      // pixel index of the first tap inside the frame
-          long long at = g.off + (a.interleaved ? px * 3 + c : c * plane + px);
-          long long cur = -4;
-          uint32_t word = 0;
-          if (g.hor.ksize == 0) {
-            u = source_byte(a.pixels, a.pixel_bytes, at, cur, word);
-          } else {
-            uint32_t acc = 1u << 21;
-            for (int t = 0; t < cnt; ++t, at += step)
-              acc += __umul24(kh[col][t], source_byte(a.pixels, a.pixel_bytes, at, cur, word));
-            u = min(acc >> 22, 255u);
-          }
-        }
-        rows[c][r][col] = (unsigned char)u;
-      }
-    }
-    __syncthreads();
-  }
-
-  // ---- phase V and the stores: 4 pixels of one output row per thread ----
-  {
-    const int ly = tid >> 3, lx = (tid & 7) << 2;
-    const int y = oy0 + ly, x0 = ox0 + lx;
-    float val[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) val[c][j] = 0.f;
-    }
-    if (live && y < g.nh && x0 < g.nw) {
-      const int first = bv[ly][0], cnt = bv[ly][1];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        uint32_t bytes;
-        if (g.ver.ksize == 0) {
-          bytes = *reinterpret_cast<const uint32_t*>(&rows[c][first][lx]);
-        } else {
-          uint32_t acc[4] = {1u << 21, 1u << 21, 1u << 21, 1u << 21};
-          for (int t = 0; t < cnt; ++t) {
-            const uint32_t k = kv[ly][t];
-            const uint32_t wd = *reinterpret_cast<const uint32_t*>(&rows[c][first + t][lx]);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] += __umul24(k, (wd >> (8 * j)) & 0xffu);
-          }
-          bytes = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bytes |= min(acc[j] >> 22, 255u) << (8 * j);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (x0 + j < g.nw) val[c][j] = (float((bytes >> (8 * j)) & 0xffu) - a.mean[c]) / a.std[c];
-      }
-    }
-    const size_t row = size_t(b) * H + y;
-    if (a.channels_last) {
-      float* out = a.x + (row * W + x0) * 3;
-      *reinterpret_cast<vnx_f4*>(out) = vnx_f4{val[0][0], val[1][0], val[2][0], val[0][1]};
-      *reinterpret_cast<vnx_f4*>(out + 4) = vnx_f4{val[1][1], val[2][1], val[0][2], val[1][2]};
-      *reinterpret_cast<vnx_f4*>(out + 8) = vnx_f4{val[2][2], val[0][3], val[1][3], val[2][3]};
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        *reinterpret_cast<vnx_f4*>(a.x + ((size_t(b) * 3 + c) * H + y) * W + x0) =
-            vnx_f4{val[c][0], val[c][1], val[c][2], val[c][3]};
-    }
-  }
-  // ---- the mask: 16 pixels per thread, 64 threads ----
-  if (tid < 2 * kTile) {
-    const int y = oy0 + (tid >> 1), x0 = ox0 + ((tid & 1) << 4);
-    rsz_u4 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) word |= uint32_t(y >= g.nh || x0 + 4 * k + j >= g.nw) << (8 * j);
-      v[k] = word;
-    }
-    *reinterpret_cast<rsz_u4*>(a.mask + ((size_t(b) * H + y) * W + x0)) = v;
-  }
-}
-
-}  // namespace
-}  // namespace vnx
+// The kernel itself stands in resize_body.h, shared with augment.hip: this file instantiates it without
+// a crop window and without a flip -- both compile-time constants, so the code below carries none of their arithmetic.
+#include "resize_body.h"
 
 using namespace vnx;
 
@@ -274,48 +43,7 @@ extern "C" int vnx_resize_ingest_frames(const void* pixels, size_t pixel_bytes, 
                                         const void* coeffs, size_t coeff_words, int batch, int height, int width,
                                         float mean0, float mean1, float mean2, float std0, float std1, float std2,
                                         int channels_last, int interleaved, void* x, void* mask, void* hip_stream) {
-  const char* fn = "vnx_resize_ingest_frames";
-  if (batch < 0 || height < 32 || width < 32 || height % 32 != 0 || width % 32 != 0) {
-    set_error("%s: bad sizes (batch %d, padded %d x %d: multiples of 32)", fn, batch, height, width);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (batch == 0) return VNX_OK;
-  if (!pixels || !src_table || !dst_table || !coeffs || !x || !mask) {
-    set_error("%s: null pointer argument", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if ((reinterpret_cast<uintptr_t>(pixels) & 3) != 0 || (reinterpret_cast<uintptr_t>(src_table) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(dst_table) & 3) != 0 || (reinterpret_cast<uintptr_t>(coeffs) & 3) != 0 ||
-      (reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(mask) & 15) != 0) {
-    set_error("%s: pixels, the tables and coeffs must be 4-byte aligned, x and mask 16-byte aligned", fn);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (coeff_words < 6 * size_t(batch)) {
-    set_error("%s: coeffs holds %zu words: less than the %d frames' rows of 6", fn, coeff_words, batch);
-    return VNX_ERR_INVALID_ARGUMENT;
-  }
-  if (pixel_bytes > size_t(0x7fffffff) || coeff_words > size_t(0x7fffffff)) {      // the tables' offsets are int32
-    set_error("%s: %zu bytes of pixels, %zu words of coefficients: the tables address 2^31 - 1 at most", fn, pixel_bytes,
-              coeff_words);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  const long long blocks = (long long)batch * (height / kTile) * (width / kTile);
-  if (blocks > 0x7fffffffll) {
-    set_error("%s: %d frames of %d x %d are more than one launch addresses", fn, batch, height, width);
-    return VNX_ERR_UNSUPPORTED;
-  }
-  ResizeArgs a;
-  a.pixels = (const unsigned char*)pixels;
-  a.pixel_bytes = (long long)pixel_bytes;
-  a.src_table = (const int32_t*)src_table;
-  a.dst_table = (const int32_t*)dst_table;
-  a.coeffs = (const int32_t*)coeffs;
-  a.coeff_words = (long long)coeff_words;
-  a.x = (float*)x;
-  a.mask = (unsigned char*)mask;
-  a.B = batch; a.H = height; a.W = width; a.channels_last = channels_last != 0; a.interleaved = interleaved != 0;
-  a.mean[0] = mean0; a.mean[1] = mean1; a.mean[2] = mean2;
-  a.std[0] = std0; a.std[1] = std1; a.std[2] = std2;
-  hipLaunchKernelGGL(resize_ingest_kernel, dim3(unsigned(blocks)), dim3(kResizeThreads), 0, (hipStream_t)hip_stream, a);
-  return check_launch(fn);
+  const float mean[3] = {mean0, mean1, mean2}, std[3] = {std0, std1, std2};
+  return launch_resize_ingest<false>("vnx_resize_ingest_frames", pixels, pixel_bytes, src_table, dst_table, coeffs, coeff_words,
+                                     batch, height, width, mean, std, channels_last, interleaved, x, mask, hip_stream);
 }

@@ -1,0 +1,120 @@
+"""What is left of a training mapper when the augmentation runs on the device (vnext_amd/ops/augment.py):
+read the frames, draw the random numbers, put the annotations in slot order.
+
+`sample_plan(cfg, sizes, num_frames, rng) -> [FramePlan]`: the draws of the reference's `build_augmentation(cfg, True)` for one
+clip whose source frames have `sizes` [(h, w)]:
+  * INPUT.CROP.ENABLED: ONE coin per clip picks the list with the crop or the list without it (the mapper's
+    `np.random.rand() > 0.5` -> no crop);
+  * detectron2's RandomCrop("absolute_range", (lo, hi)), PER FRAME: ch in [min(h, lo), min(h, hi)], cw likewise, then the
+    origin y0 in [0, h - ch], x0 in [0, w - cw] -- four integers, in that order;
+  * ResizeShortestEdge(MIN_SIZE_TRAIN, MAX_SIZE_TRAIN, MIN_SIZE_TRAIN_SAMPLING) on the CROPPED size: "choice" / "range" draw
+    a short edge per frame, "choice_by_clip" / "range_by_clip" once per clip; the target through `resize.shortest_edge_size`;
+  * INPUT.RANDOM_FLIP: "horizontal" a coin (p = 0.5) per frame, "flip_by_clip" once per clip, "none" never.
+It reproduces the SAME DISTRIBUTIONS, not the same random stream: the reference draws from numpy's global generator inside
+detectron2's transform classes, which cannot be replayed (or checked) without detectron2; `rng` is a `numpy.random.Generator`.
+Keys absent from `cfg.INPUT` take detectron2's defaults.  A cfg that asks for what the device route does not build
+(INPUT.AUGMENTATIONS, a vertical flip, another crop type) raises: such a config keeps the host mapper.
+
+`stage_clip(frames, annotations, plan, num_classes) -> dict`: the mapper's bookkeeping that has nothing to do with pixels --
+one slot per instance id of the clip (ids in order of first appearance; the reference iterates a `set`), in every frame the
+dummy annotation (class `num_classes`, id -1, an empty mask) where an instance is absent, `iscrowd` annotations dropped (their
+slot stays, filled with the dummy, as in the reference).  The entry of `batched_inputs` it returns holds "image" (the SOURCE
+frames), "augment" (the plan) and "instances": per frame a dict with gt_classes int64 [n], gt_ids int64 [n], gt_rle (the
+masks' COCO counts at SOURCE resolution, a list per slot) and image_size = (nh, nw).  A model with `device_augment` fills
+gt_masks, gt_boxes and the filtered gt_ids from one `augment_masks` call for the whole step.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..ops import resize
+from ..ops.augment import FramePlan
+from ..utils.ytvis_json import string_to_counts
+
+
+def _get(node, key, default):
+    if node is None:
+        return default
+    return node.get(key, default) if isinstance(node, dict) else getattr(node, key, default)
+
+
+def sample_plan(cfg, sizes, num_frames, rng):
+    """-> a FramePlan per frame of one clip; see the module docstring"""
+    inp = cfg.INPUT
+    assert len(sizes) == num_frames
+    if _get(inp, "AUGMENTATIONS", None):
+        raise ValueError("sample_plan: INPUT.AUGMENTATIONS %r are not built on the device" % (inp.AUGMENTATIONS,))
+    crop = _get(inp, "CROP", None)
+    crop_on = bool(_get(crop, "ENABLED", False))
+    if crop_on and _get(crop, "TYPE", "relative_range") != "absolute_range":
+        raise ValueError("sample_plan: only RandomCrop('absolute_range') is built on the device")
+    lo, hi = (int(v) for v in _get(crop, "SIZE", (384, 600))) if crop_on else (0, 0)
+    short = _get(inp, "MIN_SIZE_TRAIN", (800,))
+    short = (int(short),) if isinstance(short, int) else tuple(int(s) for s in short)
+    max_size = int(_get(inp, "MAX_SIZE_TRAIN", 1333))
+    style = _get(inp, "MIN_SIZE_TRAIN_SAMPLING", "choice")
+    flip_mode = _get(inp, "RANDOM_FLIP", "horizontal")
+    if style not in ("choice", "range", "choice_by_clip", "range_by_clip"):
+        raise ValueError("sample_plan: MIN_SIZE_TRAIN_SAMPLING %r" % (style,))
+    if flip_mode not in ("none", "horizontal", "flip_by_clip"):
+        raise ValueError("sample_plan: RANDOM_FLIP %r is not built on the device" % (flip_mode,))
+    if "range" in style:
+        assert len(short) == 2, "MIN_SIZE_TRAIN must be two values with a 'range' sampling"
+
+    use_crop = crop_on and not rng.random() > 0.5      # the coin per clip
+    plan, size, flip = [], None, False
+    for i, (h, w) in enumerate(sizes):
+        x0, y0, cw, ch = 0, 0, int(w), int(h)
+        if use_crop:
+            ch = int(rng.integers(min(h, lo), min(h, hi) + 1))
+            cw = int(rng.integers(min(w, lo), min(w, hi) + 1))
+            y0 = int(rng.integers(h - ch + 1))
+            x0 = int(rng.integers(w - cw + 1))
+        if size is None or "by_clip" not in style:
+            size = int(rng.integers(short[0], short[1] + 1)) if "range" in style else int(rng.choice(short))
+        if flip_mode != "none" and (i == 0 or flip_mode == "horizontal"):
+            flip = bool(rng.random() < 0.5)
+        nh, nw = resize.shortest_edge_size(ch, cw, size, max_size)
+        plan.append(FramePlan(x0, y0, cw, ch, nh, nw, flip))
+    return plan
+
+
+def _counts(segmentation):
+    """an annotation's mask as COCO counts: a count list, an RLE dict with a count list or a compressed string, or a string"""
+    if isinstance(segmentation, dict):
+        segmentation = segmentation["counts"]
+    if isinstance(segmentation, bytes):
+        segmentation = segmentation.decode("ascii")
+    if isinstance(segmentation, str):
+        return [int(c) for c in string_to_counts(segmentation)]
+    segmentation = list(segmentation)
+    if not segmentation or any(isinstance(c, (list, tuple, np.ndarray)) for c in segmentation):
+        raise ValueError("stage_clip: polygons go through frPyObjects to RLE first")
+    return [int(c) for c in segmentation]
+
+
+def stage_clip(frames, annotations, plan, num_classes, layout: str = "chw"):
+    """frames: the clip's uint8 SOURCE frames; annotations: per frame a list of dicts with "id", "category_id",
+    "segmentation" (COCO counts: a list, a compressed string, or an RLE dict of either) and optionally "iscrowd"
+    -> the clip's entry of `batched_inputs`; see the module docstring."""
+    assert len(frames) == len(annotations) == len(plan)
+    slots = {}
+    for annos in annotations:
+        for a in annos:
+            slots.setdefault(a["id"], len(slots))
+    instances = []
+    for f, annos, p in zip(frames, annotations, plan):
+        h, w = resize.frame_size(f, layout)
+        classes, ids, rles = [num_classes] * len(slots), [-1] * len(slots), [[h * w] for _ in slots]      # the dummy
+        for a in annos:
+            if a.get("iscrowd", 0) != 0:
+                continue
+            s = slots[a["id"]]
+            classes[s], ids[s], rles[s] = int(a["category_id"]), int(a["id"]), _counts(a["segmentation"])
+        instances.append({"gt_classes": torch.tensor(classes, dtype=torch.int64), "gt_ids": torch.tensor(ids, dtype=torch.int64),
+                          "gt_rle": rles, "image_size": (p.nh, p.nw)})
+    entry = {"image": list(frames), "augment": list(plan), "instances": instances}
+    if layout != "chw":
+        entry["image_layout"] = layout
+    return entry

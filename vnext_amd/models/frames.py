@@ -5,6 +5,8 @@ tail (`_clip_trunk_tail`, `_chunk_trunk`, `_train_trunk`), and nothing here asks
   pad_normalise            a same-sized float stack -> (x, mask): the expression the training and inference graphs capture
   pad_normalise_list       float frames of unequal sizes -> (x, mask), frame by frame
   ingest_staged / resize_staged      staged uint8 frames / resize sources -> (x, mask, table): one launch of the op
+  augment_staged, augment_step, host_augmented       `device_augment`: a training step's source frames and run-length ground
+                           truth -> (x, mask, table) and filled instance dicts; the host route of the same plan
   preprocess               a list of frames -> (x, mask) or (x, mask, table): what both `_preprocess` are
   level_inputs             the pyramid levels' padding masks and sine positions
   stage_chunk              the frames of one inference call -> `StagedFrames`, or None for the eager list path
@@ -16,11 +18,12 @@ from __future__ import annotations
 
 from typing import Callable, NamedTuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import ingest, resize
+from ..ops import augment, ingest, resize
 from ..ops.fused_norm import step_scope
 from ..ops.ingest import sine_position
 
@@ -90,6 +93,79 @@ def resize_staged(pixels, src_table, dst_table, coeffs, B, H, W, layout, stats):
     x, mask = resize.resize_ingest_frames(pixels, src_table, dst_table, coeffs, B, H, W, *stats, channels_last=False,
                                           layout=layout)
     return x, mask, dst_table
+
+
+def augment_staged(staged, stats, backbone):
+    """one step's staged SOURCE frames (`augment.stage_step`) -> (x, mask, table) of the frames cropped, resized and flipped
+    as their plan says: one launch; channels-last where `ingest_staged` would be (a training step); the table is the
+    destination geometry `level_inputs` hands to the level launch"""
+    asks = getattr(backbone, "wants_channels_last", None)
+    nhwc = bool(staged.pixels.is_cuda and asks is not None and asks())
+    x, mask = augment.augment_frames(staged, *stats, channels_last=nhwc)
+    return x, mask, staged.dst_table
+
+
+def host_augmented(batched_inputs):
+    """The host route of the same plan: every clip's frames and ground truth through `augment.reference_augment_*` on the CPU
+    -> `batched_inputs` as a mapper of the reference would have made them (CHW uint8 frames at their targets; gt_masks,
+    gt_boxes, the filtered gt_ids).  What a model with `device_augment` takes when `augment.applies` says no, and what the
+    tests compare the device route with."""
+    out = []
+    for clip in batched_inputs:
+        layout, plan = clip.get("image_layout", "chw"), clip["augment"]
+        frames = augment.reference_augment_frames(clip["image"], plan, layout)
+        frames = [f if layout == "chw" else f.permute(2, 0, 1).contiguous() for f in frames]
+        sizes = [resize.frame_size(f, layout) for f in clip["image"]]
+        instances = []
+        for i, fr in enumerate(clip["instances"]):
+            masks, boxes, flags = augment.reference_augment_masks([(i, c) for c in fr["gt_rle"]], sizes, plan)
+            nh, nw = fr["image_size"]
+            gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, nh, nw, dtype=torch.bool)
+            keep = torch.from_numpy(flags)
+            instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": gm,
+                              "gt_boxes": torch.from_numpy(boxes), "gt_ids": torch.where(keep, fr["gt_ids"], -1)})
+        out.append({**{k: v for k, v in clip.items() if k not in ("augment", "image_layout")}, "image": frames,
+                    "instances": instances})
+    return out
+
+
+def augment_step(model, batched_inputs):
+    """`device_augment` for one training step.  -> (batched_inputs, pre):
+      the switch is off, the model is not training, or a clip carries no "augment": the inputs untouched, pre None;
+      the plan is in the kernels' range: pre = (x, mask, table) from ONE `augment_frames` call, and the clips' instance dicts
+        (copies) filled with gt_masks, gt_boxes and gt_ids from ONE `augment_masks` call for the whole step -- views of its
+        outputs; gt_ids = nonempty ? id : -1 (`filter_empty_instances`: with boxes taken from masks its box test and its
+        mask test are the same test).  The clips' "image" entries stay the source frames: nothing reads their pixels again;
+      beyond it (`augment.applies`): `host_augmented` inputs, pre None -- the path without the switch."""
+    if not (getattr(model, "device_augment", False) and model.training
+            and all("augment" in clip for clip in batched_inputs)):
+        return batched_inputs, None
+    layout = batched_inputs[0].get("image_layout", "chw")
+    frames = [f for clip in batched_inputs for f in clip["image"]]
+    plan = [p for clip in batched_inputs for p in clip["augment"]]
+    if any(clip.get("image_layout", "chw") != layout for clip in batched_inputs) or \
+            not augment.applies(frames, plan, model.device, layout):
+        return host_augmented(batched_inputs), None
+    listed, ids, f = [], [], 0
+    for clip in batched_inputs:
+        for fr in clip["instances"]:
+            listed += [(f, c) for c in fr["gt_rle"]]
+            ids += fr["gt_ids"].tolist()
+            f += 1
+    staged = augment.stage_step(frames, plan, listed, model.device, layout, ids)
+    pre = augment_staged(staged, model._pixel_stats, model.detr.detr.backbone)
+    masks, boxes, nonempty = augment.augment_masks(staged)
+    gt_ids = torch.where(nonempty, staged.ids, -1).to(torch.int64)
+    views, out, f = staged.mask_views(masks), [], 0
+    for clip in batched_inputs:
+        instances = []
+        for fr in clip["instances"]:
+            first, k = staged.groups[f][:2]
+            instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": views[f],
+                              "gt_boxes": boxes[first:first + k], "gt_ids": gt_ids[first:first + k]})
+            f += 1
+        out.append({**clip, "instances": instances})
+    return out, pre
 
 
 def takes_bytes(frames, device_ingest, device) -> bool:

@@ -35,7 +35,7 @@ from ..heads import dynamic_mask_head, loss_reid
 from ..registry import META_ARCH_REGISTRY
 from .criterion import box_cxcywh_to_xyxy, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from .idol_criterion import IDOLCriterion, OTAMatcher, reid_terms, reid_terms_fused, sample_aux_masks, select_pos_neg_masks
-from .frames import (TrainTrunk, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
+from .frames import (TrainTrunk, augment_step, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
                      replay_captured, stage_chunk)
 from .idol_transformer import DeformableTransformer
 from .resnet import build_backbone
@@ -112,6 +112,9 @@ class IDOL(nn.Module):
         # eval mode, uint8 video frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel
         # that also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
         self.device_resize = False
+        # training mode, clips staged by `data.clip_mapper.stage_clip`: crop, resize and flip of the source frames AND of their
+        # run-length ground truth on the device (vnext_amd/ops/augment.py; opt-in: train.enable_device_augment)
+        self.device_augment = False
         self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 480)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
@@ -215,10 +218,14 @@ class IDOL(nn.Module):
 
     def losses(self, batched_inputs):
         """CondInst_segm.forward (segmentation_condInst.py:78-231) + SetCriterion."""
+        batched_inputs, pre = augment_step(self, batched_inputs)      # `device_augment`: pre = (x, mask, table), else None
         det_t, ref_t = self.prepare_targets(batched_inputs)
         frames = [f for video in batched_inputs for f in video["image"]]
         sizes = [tuple(f.shape[-2:]) for f in frames][0::2]
-        if self.graph_training and frames[0].is_cuda and all(f.shape == frames[0].shape for f in frames):
+        if pre is not None:      # the frames are still the sources: the network saw their targets
+            sizes = [tuple(fr["image_size"]) for video in batched_inputs for fr in video["instances"]][0::2]
+            hs, logits, boxes, ref_xy, ref_last, feats, ref_logits, embeds = self._train_trunk(*pre)
+        elif self.graph_training and frames[0].is_cuda and all(f.shape == frames[0].shape for f in frames):
             hs, logits, boxes, ref_xy, ref_last, feats, ref_logits, embeds = self._graphed_train_trunk(
                 torch.stack([f.to(self.device, torch.float32) for f in frames]))
         else:

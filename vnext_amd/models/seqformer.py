@@ -32,7 +32,7 @@ from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
 from ..registry import META_ARCH_REGISTRY
-from .frames import (TrainTrunk, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
+from .frames import (TrainTrunk, augment_step, front_end, front_end_state, graphed_callable, level_inputs, plan_resize, preprocess,
                      replay_captured, stage_chunk, takes_bytes)
 from .resnet import FrozenBatchNorm2d, ResNet50Trunk, build_backbone, conv_bn  # noqa: F401
 from .seqformer_transformer import DeformableTransformer, inverse_sigmoid
@@ -159,6 +159,9 @@ class SeqFormer(nn.Module):
         # eval mode, uint8 frames at their decoded size: ResizeShortestEdge(MIN_SIZE_TEST, MAX_SIZE_TEST) by the kernel that
         # also ingests them, byte for byte Pillow's (vnext_amd/ops/resize.py; opt-in: train.enable_device_resize)
         self.device_resize = False
+        # training mode, clips staged by `data.clip_mapper.stage_clip`: crop, resize and flip of the source frames AND of their
+        # run-length ground truth on the device (vnext_amd/ops/augment.py; opt-in: train.enable_device_augment)
+        self.device_augment = False
         self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 360)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
@@ -205,8 +208,9 @@ class SeqFormer(nn.Module):
             coords.append(tmp.sigmoid())
         return torch.stack(classes), torch.stack(coords)
 
-    def _run(self, batched_inputs, want_refs=False):
-        pre = self._preprocess(batched_inputs)
+    def _run(self, batched_inputs, want_refs=False, pre=None):
+        """pre: (x, mask, table) the front end already made (`device_augment`)"""
+        pre = self._preprocess(batched_inputs) if pre is None else pre
         x = pre[0]
         srcs, masks, poss = self._features(*pre)
         hs, hs_box, memory, init_ref, inter_refs, inter_boxes, _, _ = self.detr.detr.transformer(
@@ -279,14 +283,15 @@ class SeqFormer(nn.Module):
 
     def losses(self, batched_inputs):
         """CondInst_segm.forward (segmentation_condInst.py:69-207) + SetCriterion."""
+        batched_inputs, pre = augment_step(self, batched_inputs)      # `device_augment`: pre = (x, mask, table), else None
         targets = self.prepare_targets(batched_inputs)
         frames = [f for clip in batched_inputs for f in clip["image"]]
-        if self.graph_training and frames[0].is_cuda and all(f.shape == frames[0].shape for f in frames):
+        if pre is None and self.graph_training and frames[0].is_cuda and all(f.shape == frames[0].shape for f in frames):
             hs, logits, boxes, ref0, ref_rest, feats = self._graphed_train_trunk(
                 torch.stack([f.to(self.device, torch.float32) for f in frames]))
             refs = [ref0] + list(ref_rest[:hs.shape[0] - 1])
         else:
-            x, srcs, hs, memory, logits, boxes, refs = self._run(batched_inputs, want_refs=True)
+            x, srcs, hs, memory, logits, boxes, refs = self._run(batched_inputs, want_refs=True, pre=pre)
             feats = self._mask_features(srcs, memory)
         return self._losses_after_trunk(targets, hs, logits, boxes, refs, feats)
 

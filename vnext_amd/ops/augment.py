@@ -1,0 +1,296 @@
+"""Training-time augmentation on the device: crop, resize, horizontal flip of uint8 source frames AND of their ground-truth
+masks, with the masks' boxes (vnext_amd/csrc/augment.hip).
+
+The reference trains every config with RandomCrop("absolute_range") (IDOL), ResizeShortestEdge and RandomFlip, applied by
+Pillow and numpy in a data-loader worker to the frames and, mask by mask, to the decoded ground truth.  Here the host only
+draws the random numbers (`vnext_amd/data/clip_mapper.py`); frames cross the bus as decoded bytes and masks as their COCO run
+lengths, and a few launches produce (x, mask) and every mask, box and `nonempty` flag.
+
+`FramePlan(x0, y0, cw, ch, nh, nw, flip)`: one frame's draw: the crop window inside the source, the target size, the flip.
+`nearest_table(n_in, n_out) -> int32 [n_out]`: Pillow's `resize(..., NEAREST)` source indices.  Pillow takes its affine path
+for NEAREST and ACCUMULATES in double -- xo = 0.5 * a, then tab[i] = int(xo); xo += a with a = n_in / n_out -- which is not
+`floor((i + 0.5) * n_in / n_out)` (they differ on about a fifth of the size pairs).  Python floats, cached per pair.
+`reference_augment_frames(frames, plan, layout)`: numpy slicing, `resize.reference_resize`, `np.flip` -> uint8 frames.
+`reference_augment_masks(masks, sizes, plan)`: `rle_decode`, slicing, the index tables, `np.flip`, then the box as
+`BitMasks.get_bounding_boxes` computes it.  Both are the CPU route of the ops and the oracle of the GPU tests.
+`stage_step(frames, plan, masks, device, layout) -> Staged`: the tables, the coefficients (each distinct bilinear and nearest
+table once), the masks' run END positions (one cumsum each), their rows and ids, and the frame bytes in ONE pinned buffer and
+one `non_blocking` copy.
+`augment_frames(staged, mean, std, channels_last) -> (x, mask)`: one launch; the outputs of `resize.resize_ingest_frames`.
+`augment_masks(staged) -> (masks uint8 [bytes], boxes fp32 [m, 4], nonempty bool [m])`: two launches; `staged.mask_views(masks)`
+gives each frame's bool [n_inst, nh, nw] as a view.
+
+The bilinear range is the resize kernel's (ksize <= 17 on both axes, of the WINDOW to the target); `applies` says so and the
+caller takes the host route beyond.  `CALLS` counts the launches made here.
+"""
+from __future__ import annotations
+
+import functools
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..utils.ytvis_json import counts_to_string, rle_decode
+from . import ingest, resize
+
+CALLS = {"augment_frames": 0, "augment_masks": 0}      # calls through the C ABI (tests: the ops ran / did not run)
+SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS = 8, 8, 4
+
+
+class FramePlan(NamedTuple):
+    x0: int
+    y0: int
+    cw: int
+    ch: int
+    nh: int
+    nw: int
+    flip: bool
+
+
+def full_plan(h: int, w: int, nh: int, nw: int, flip: bool = False) -> FramePlan:
+    """the whole frame as the window"""
+    return FramePlan(0, 0, int(w), int(h), int(nh), int(nw), bool(flip))
+
+
+@functools.lru_cache(maxsize=256)
+def _nearest(n_in: int, n_out: int):
+    a = n_in / n_out
+    xo = a * 0.5
+    tab = np.empty(n_out, dtype=np.int32)
+    for i in range(n_out):
+        tab[i] = int(xo)
+        xo += a
+    np.minimum(tab, n_in - 1, out=tab)      # (Pillow skips a sample outside the image; none is on these tables)
+    tab.setflags(write=False)
+    return tab
+
+
+def nearest_table(n_in: int, n_out: int):
+    """-> int32 [n_out], read-only, cached per (n_in, n_out); see the module docstring"""
+    return _nearest(int(n_in), int(n_out))
+
+
+def _inside(p: FramePlan, h: int, w: int) -> bool:
+    return p.x0 >= 0 and p.y0 >= 0 and p.cw >= 1 and p.ch >= 1 and p.x0 + p.cw <= w and p.y0 + p.ch <= h
+
+
+# ---- the CPU route and oracle -----------------------------------------------------------------------------------------------
+def reference_augment_frames(frames, plan, layout: str = "chw"):
+    """uint8 frames (tensors or arrays of `layout`) -> the cropped, resized and flipped frames, same kind and layout"""
+    ah, aw = resize._hw_axes(layout)
+    out = []
+    for f, p in zip(frames, plan):
+        is_tensor = torch.is_tensor(f)
+        a = f.detach().cpu().numpy() if is_tensor else np.asarray(f)
+        assert _inside(p, a.shape[ah], a.shape[aw])
+        sl = [slice(None)] * 3
+        sl[ah], sl[aw] = slice(p.y0, p.y0 + p.ch), slice(p.x0, p.x0 + p.cw)
+        a = resize.reference_resize(np.ascontiguousarray(a[tuple(sl)]), p.nh, p.nw, layout)
+        if p.flip:
+            a = np.flip(a, axis=aw)
+        a = np.ascontiguousarray(a)
+        out.append(torch.from_numpy(a) if is_tensor else a)
+    return out
+
+
+def mask_box(m):
+    """`BitMasks.get_bounding_boxes` of one bool [h, w] array -> ([x0, y0, x1 + 1, y1 + 1] float32, nonempty)"""
+    xs, ys = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
+    if xs.size == 0:
+        return np.zeros(4, dtype=np.float32), False
+    return np.array([xs[0], ys[0], xs[-1] + 1, ys[-1] + 1], dtype=np.float32), True
+
+
+def reference_augment_masks(masks, sizes, plan):
+    """masks: [(frame index, COCO counts)]; sizes: the frames' source (h, w); plan: the frames' FramePlan
+    -> ([bool array [nh, nw] per mask], boxes float32 [m, 4], nonempty bool [m]).  Counts that do not sum to h * w are the
+    empty mask."""
+    outs, boxes, flags = [], np.zeros((len(masks), 4), dtype=np.float32), np.zeros(len(masks), dtype=bool)
+    for i, (f, counts) in enumerate(masks):
+        (h, w), p = sizes[f], plan[f]
+        counts = [int(c) for c in counts]
+        if sum(counts) == h * w and min(counts) >= 0:
+            dense = rle_decode({"size": [h, w], "counts": counts_to_string(counts)}).astype(bool)
+        else:
+            dense = np.zeros((h, w), dtype=bool)
+        crop = dense[p.y0:p.y0 + p.ch, p.x0:p.x0 + p.cw]
+        m = crop[nearest_table(p.ch, p.nh)][:, nearest_table(p.cw, p.nw)]
+        if p.flip:
+            m = np.flip(m, axis=1)
+        m = np.ascontiguousarray(m)
+        outs.append(m)
+        boxes[i], flags[i] = mask_box(m)
+    return outs, boxes, flags
+
+
+# ---- staging ----------------------------------------------------------------------------------------------------------------
+def supported(p: FramePlan) -> bool:
+    return resize.supported(p.ch, p.cw, p.nh, p.nw)
+
+
+def applies(frames, plan, device, layout: str = "chw") -> bool:
+    """All frames are uint8 CPU tensors of `layout`, every window lies inside its frame and every (window, target) pair is in
+    the kernel's range"""
+    ah, aw = resize._hw_axes(layout)
+    if not frames or len(frames) != len(plan):
+        return False
+    for f, p in zip(frames, plan):
+        if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[3 - ah - aw] == 3 and not f.is_cuda):
+            return False
+        if not (_inside(p, f.shape[ah], f.shape[aw]) and supported(p)):
+            return False
+    return True
+
+
+def padded_size(plan):
+    return resize.padded_size([(p.nh, p.nw) for p in plan])
+
+
+def _coeff_words(plan):
+    """the `coeffs` buffer of a step as one int32 array: a row of 8 per frame, then each distinct bilinear table and each
+    distinct nearest table once"""
+    n = len(plan)
+    head = np.zeros((n, COEFF_WORDS), dtype=np.int32)
+    parts, at, bil, near = [], COEFF_WORDS * n, {}, {}
+    for i, p in enumerate(plan):
+        for j, pair in enumerate(((p.cw, p.nw), (p.ch, p.nh))):
+            if pair[0] != pair[1]:           # else ksize 0: the pass is skipped
+                if pair not in bil:
+                    bounds, kk = resize.pillow_coeffs(*pair)
+                    bil[pair] = (at, at + bounds.size, kk.shape[1])
+                    parts += [bounds.reshape(-1), kk.reshape(-1)]
+                    at += bounds.size + kk.size
+                head[i, 3 * j:3 * j + 3] = bil[pair]
+            if pair not in near:
+                near[pair] = at
+                parts.append(nearest_table(*pair))
+                at += pair[1]
+            head[i, 6 + j] = near[pair]
+    return np.concatenate([head.reshape(-1)] + parts)
+
+
+class Staged(NamedTuple):
+    pixels: torch.Tensor        # uint8 [bytes]
+    src_table: torch.Tensor     # int32 [n, 8] = {byte offset, h, w, x0, y0, cw, ch, flip}
+    dst_table: torch.Tensor     # int32 [n, 3] = {0, nh, nw}: what `ingest.level_constants` takes
+    coeffs: torch.Tensor        # int32 [words]
+    ends: torch.Tensor          # int32 [sum of runs] (at least one word)
+    mask_rows: torch.Tensor     # int32 [m, 4] = {ends offset, n_runs, frame index, output byte offset}
+    ids: torch.Tensor           # int32 [m]: the masks' instance ids
+    size: tuple                 # (H, W) the step is padded to
+    layout: str
+    mask_bytes: int
+    groups: tuple               # per frame (first mask, masks, nh, nw): the masks of a frame are consecutive
+
+    def mask_views(self, masks):
+        """the flat output of `augment_masks` -> per frame bool [n_inst, nh, nw] (views)"""
+        rows, out, off = masks.view(torch.bool), [], 0
+        for _, k, nh, nw in self.groups:
+            out.append(rows[off:off + k * nh * nw].view(k, nh, nw))
+            off += k * nh * nw
+        return out
+
+
+def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None) -> Staged:
+    """frames: uint8 CPU tensors of `layout`; plan: a FramePlan per frame; masks: [(frame index, COCO counts)] with the masks
+    of a frame CONSECUTIVE and the frames ascending; ids: the masks' instance ids (default 0).  See the module docstring."""
+    device = torch.device(device)
+    n, m = len(frames), len(masks)
+    sizes = [resize.frame_size(f, layout) for f in frames]
+    src, off = np.zeros((n, SRC_WORDS), dtype=np.int32), 0
+    for i, ((h, w), p) in enumerate(zip(sizes, plan)):
+        src[i] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
+        off += ingest._align16(3 * h * w)
+    dst = np.array([(0, p.nh, p.nw) for p in plan], dtype=np.int32).reshape(n, 3)
+    words = _coeff_words(plan)
+    rows, ends, e_at, o_at = np.zeros((m, MASK_ROW_WORDS), dtype=np.int32), [], 0, 0
+    groups, last = [[0, 0, p.nh, p.nw] for p in plan], -1
+    for i, (f, counts) in enumerate(masks):
+        assert f >= last, "stage_step: the masks of a frame are consecutive, the frames ascending"
+        if f != last:
+            groups[f][0] = i
+        last = f
+        groups[f][1] += 1
+        e = np.cumsum(np.asarray(counts, dtype=np.int64))
+        assert e.size >= 1 and e[-1] <= 0x7fffffff
+        rows[i] = (e_at, e.size, f, o_at)
+        ends.append(e.astype(np.int32))
+        e_at += e.size
+        o_at += plan[f].nh * plan[f].nw
+    for g in groups:                         # a frame without masks: its (empty) group starts where the next one does
+        if g[1] == 0:
+            g[0] = 0
+    ends = np.concatenate(ends) if ends else np.zeros(1, dtype=np.int32)
+    idv = np.zeros(m, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(m)
+    small = [src.reshape(-1), dst.reshape(-1), words, ends, rows.reshape(-1), idv]
+    cuts = np.cumsum([0] + [s.size for s in small])
+    head = ingest._align16(4 * int(cuts[-1]))
+    buf = torch.empty(head + off, dtype=torch.uint8, pin_memory=device.type == "cuda")
+    buf[:4 * int(cuts[-1])].view(torch.int32).copy_(torch.from_numpy(np.concatenate(small)))
+    for f, row in zip(frames, src.tolist()):
+        o, h, w = row[:3]
+        buf[head + o:head + o + 3 * h * w].view(f.shape).copy_(f)
+    whole = buf.to(device, non_blocking=True)
+    ints = whole[:4 * int(cuts[-1])].view(torch.int32)
+    part = [ints[int(a):int(b)] for a, b in zip(cuts[:-1], cuts[1:])]
+    return Staged(whole[head:], part[0].view(n, SRC_WORDS), part[1].view(n, 3), part[2], part[3],
+                  part[4].view(m, MASK_ROW_WORDS), part[5], padded_size(plan), layout, int(o_at),
+                  tuple(tuple(g) for g in groups))
+
+
+def _plan_of(staged: Staged):
+    return [FramePlan(x0, y0, cw, ch, nh, nw, bool(fl)) for (_, _, _, x0, y0, cw, ch, fl), (_, nh, nw)
+            in zip(staged.src_table.tolist(), staged.dst_table.tolist())]
+
+
+# ---- the ops ----------------------------------------------------------------------------------------------------------------
+def augment_frames(staged: Staged, mean, std, channels_last: bool = False):
+    """-> (x fp32 [B, 3, H, W], mask bool [B, H, W]) of the augmented frames; one launch"""
+    pixels, layout, (H, W) = staged.pixels, staged.layout, staged.size
+    B = staged.src_table.shape[0]
+    if not pixels.is_cuda:
+        frames = [pixels[o:o + 3 * h * w].view((3, h, w) if layout == "chw" else (h, w, 3))
+                  for o, h, w in (r[:3] for r in staged.src_table.tolist())]
+        out = [f if layout == "chw" else f.permute(2, 0, 1).contiguous()
+               for f in reference_augment_frames(frames, _plan_of(staged), layout)]
+        return ingest.ingest_frames(*ingest.stage_frames(out, "cpu"), B, H, W, mean, std, channels_last)
+    fmt = torch.channels_last if channels_last else torch.contiguous_format
+    x = torch.empty((B, 3, H, W), dtype=torch.float32, device=pixels.device, memory_format=fmt)
+    mask = torch.empty((B, H, W), dtype=torch.bool, device=pixels.device)
+    with torch.cuda.device(pixels.device):
+        _lib.check(_lib.lib().vnx_augment_frames(
+            pixels.data_ptr(), pixels.numel(), staged.src_table.data_ptr(), staged.dst_table.data_ptr(),
+            staged.coeffs.data_ptr(), staged.coeffs.numel(), B, H, W, *ingest._stats(mean), *ingest._stats(std),
+            int(bool(channels_last)), int(layout == "hwc"), x.data_ptr(), mask.data_ptr(), _lib.current_stream(pixels)))
+    CALLS["augment_frames"] += 1
+    return x, mask
+
+
+def augment_masks(staged: Staged):
+    """-> (masks uint8 [mask_bytes], boxes fp32 [m, 4], nonempty bool [m]); two launches (none for m == 0)"""
+    m, dev = staged.mask_rows.shape[0], staged.ends.device
+    if not staged.ends.is_cuda:
+        ends, rows = staged.ends.numpy(), staged.mask_rows.tolist()
+        listed = [(f, np.diff(ends[o:o + k], prepend=0)) for o, k, f, _ in rows]
+        sizes = [tuple(r[1:3]) for r in staged.src_table.tolist()]
+        outs, boxes, flags = reference_augment_masks(listed, sizes, _plan_of(staged))
+        flat = np.concatenate([o.reshape(-1) for o in outs]) if outs else np.zeros(0, dtype=bool)
+        return torch.from_numpy(flat.astype(np.uint8)), torch.from_numpy(boxes), torch.from_numpy(flags)
+    H, W = staged.size
+    masks = torch.empty(max(staged.mask_bytes, 1), dtype=torch.uint8, device=dev)[:staged.mask_bytes]
+    boxes = torch.empty((m, 4), dtype=torch.float32, device=dev)
+    nonempty = torch.empty(m, dtype=torch.bool, device=dev)
+    if m == 0:
+        return masks, boxes, nonempty
+    lib = _lib.lib()
+    work = torch.empty(int(lib.vnx_augment_masks_workspace(m, H, W)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.vnx_augment_masks(
+            staged.ends.data_ptr(), staged.ends.numel(), staged.mask_rows.data_ptr(), m, staged.src_table.data_ptr(),
+            staged.dst_table.data_ptr(), staged.coeffs.data_ptr(), staged.coeffs.numel(), staged.src_table.shape[0], H, W,
+            masks.data_ptr(), masks.numel(), boxes.data_ptr(), nonempty.data_ptr(), work.data_ptr(), work.numel(),
+            _lib.current_stream(staged.ends)))
+    CALLS["augment_masks"] += 1
+    return masks, boxes, nonempty

@@ -365,6 +365,20 @@ def enable_device_resize(model, on: bool = True) -> None:
     model.device_resize = bool(on)
 
 
+def enable_device_augment(model, on: bool = True) -> None:
+    """Opt in to the training-time augmentation on the device (`SeqFormer.device_augment` / `IDOL.device_augment`,
+    vnext_amd/ops/augment.py): in training mode, clips that `vnext_amd.data.clip_mapper.stage_clip` made -- SOURCE frames as
+    decoded bytes, the drawn plan under "augment", ground-truth masks as their COCO run lengths -- are cropped, resized and
+    flipped by one kernel that also normalises, pads and masks them (byte for byte Pillow's bilinear resize), and gt_masks,
+    gt_boxes and gt_ids of the whole step come from one more call, straight from the run lengths with Pillow's NEAREST
+    tables: what the reference's mapper computes with Pillow and numpy per frame and per mask on the host.  Clips without
+    "augment", eval mode and the captured training trunks are unchanged; a plan beyond the kernels' range takes the host
+    route of the same arithmetic.  Raises for a model without the switch."""
+    if not hasattr(model, "device_augment"):
+        raise ValueError("enable_device_augment: %s has no device_augment switch" % type(model).__name__)
+    model.device_augment = bool(on)
+
+
 def enable_fused_mask_loss(model, on: bool = True) -> None:
     """Opt in to the fused mask losses (`criterion.fused_mask_loss`, vnext_amd/ops/mask_loss.py): focal + dice of the
     matched instances' mask logits in one kernel pass each way, the ground truth read in place at image resolution --
