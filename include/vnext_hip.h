@@ -771,6 +771,44 @@ int vnx_swin_merge_norm_backward(int x_dtype, int n_dtype, const void* grad_n, c
                                  size_t partial_bytes, int batch, int height, int width, int channels, void* hip_stream);
 
 /*
+ * The element-wise glue of the ResNet trunk (resnet_glue.hip): what follows a convolution whose frozen batch norm is folded
+ * into its filters -- the shift, the ReLU, the residual add; the stem's shift, ReLU and max-pool.  ADDITIVE: three symbols, no
+ * existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * dtype names every array of a call, the shifts included: VNX_F32, VNX_BF16 or VNX_F16.  layout: VNX_LAYOUT_NCHW (the channel
+ * of flat element i is (i / hw) % c) or VNX_LAYOUT_NHWC (i % c); arrays are dense in that layout.  All sizes are 64-bit and
+ * so is every index; a size above 2^31 or more than 2^46 elements is VNX_ERR_INVALID_ARGUMENT.
+ *
+ * vnx_conv_epilogue_forward:  y <- relu((y + bias[ch]) + (res + res_bias[ch])), in place on the convolution's output y
+ * [n][c][hw].  res (y's shape) and res_bias [c] may each be null (res_bias only with res): without res it is the shift + ReLU
+ * after a block's first two convolutions, with res the block's tail -- an identity shortcut passes no res_bias, a projection
+ * shortcut the raw output of its convolution and that convolution's shift.  res is only read and must not overlap y.  fp32:
+ * the additions run in exactly that order, so the result is the eager chain's bit for bit.  16-bit: operands widened, the
+ * sum formed in fp32 and rounded ONCE.  NaN and +-inf propagate as in clamp_min.  16-byte accesses where the pointers are
+ * 16-byte aligned; the shift is one value per access where hw (NCHW) is a multiple of the 16-byte width, a 16-byte load
+ * where c (NHWC) is, and looked up element by element otherwise (plane heads and tails, an odd c); an unaligned pointer and
+ * the array's tail take element accesses.
+ *
+ * vnx_conv_epilogue_backward:  grad_in[i] = y[i] > 0 ? grad_y[i] : 0 over `count` elements (y: the forward's result, all
+ * three arrays in one layout).  The one tensor is the gradient of the convolution's output AND of res; the shifts are
+ * constants of a frozen norm.
+ *
+ * vnx_stem_pool_forward:  out = max_pool2d(relu(conv_out + bias[ch]), kernel 3, stride 2, padding 1): conv_out [n][c][h][w]
+ * (or [n][h][w][c]) is read once and only out [n][c][oh][ow], oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1, is written.  A NaN
+ * in a window is that window's result, as in ATen.  16-bit: the rounding of the fp32 result.  Forward only.
+ *
+ * One launch each.  No allocation, no synchronisation: capturable in a hipGraph.
+ */
+#define VNX_LAYOUT_NCHW 0
+#define VNX_LAYOUT_NHWC 1
+int vnx_conv_epilogue_forward(int dtype, int layout, void* y, const void* bias, const void* res, const void* res_bias,
+                              long long n, long long c, long long hw, void* hip_stream);
+int vnx_conv_epilogue_backward(int dtype, const void* grad_y, const void* y, void* grad_in, long long count,
+                               void* hip_stream);
+int vnx_stem_pool_forward(int dtype, int layout, const void* conv_out, const void* bias, void* out, long long n, long long c,
+                          long long h, long long w, void* hip_stream);
+
+/*
  * Detection selection of a batch of images (det_select.hip): best class per query, score threshold, class-aware greedy
  * box NMS and the top-k over (kept query, class) -- IDOL's per-frame candidate selection and its COCO-pretrain inference.
  * ADDITIVE: two symbols, no existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the

@@ -29,6 +29,7 @@ REID_LOSS_MAX_ROWS = 1024                                  # VNX_REID_LOSS_MAX_R
 CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_INSTANCES, VNX_CLIP_LINK_MAX_FRAMES
 INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
 RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                            # VNX_LAYOUT_NCHW, VNX_LAYOUT_NHWC
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 
@@ -91,6 +92,9 @@ SIGNATURES = {
     "vnx_swin_residual_norm_backward": (_i, [_i] * 3 + [_vp] * 11 + [_sz, _ll, _i, _ll, _vp]),
     "vnx_swin_merge_norm_forward": (_i, [_i] * 2 + [_vp] * 5 + [_i] * 4 + [ctypes.c_float, _vp]),
     "vnx_swin_merge_norm_backward": (_i, [_i] * 2 + [_vp] * 8 + [_sz] + [_i] * 4 + [_vp]),
+    "vnx_conv_epilogue_forward": (_i, [_i, _i] + [_vp] * 4 + [_ll] * 3 + [_vp]),
+    "vnx_conv_epilogue_backward": (_i, [_i] + [_vp] * 3 + [_ll, _vp]),
+    "vnx_stem_pool_forward": (_i, [_i, _i] + [_vp] * 3 + [_ll] * 4 + [_vp]),
     "vnx_clip_link_state_bytes": (_sz, [_vp]),
     "vnx_clip_link_workspace_bytes": (_sz, [_vp]),
     "vnx_clip_link_reset": (_i, [_vp, _vp, _vp]),

@@ -55,8 +55,18 @@ def _ns(**kw):
 
 def _backbone_ns():
     """MODEL.BACKBONE: NAME "D2SwinTransformer" builds the Swin backbone (vnext_amd/models/swin.py); anything else (the
-    default, detectron2's "build_resnet_backbone") the ResNet-50 trunk."""
+    default, detectron2's "build_resnet_backbone") the ResNet trunk MODEL.RESNETS describes, frozen up to FREEZE_AT."""
     return _ns(NAME="build_resnet_backbone", FREEZE_AT=2)
+
+
+def _resnets_ns():
+    """MODEL.RESNETS: detectron2's keys with the values every ResNet config of the reference sets (configs/base_ytvis.yaml,
+    IDOL's configs/*_r50.yaml; the R101 configs override DEPTH) -- not detectron2's own defaults, which differ in
+    OUT_FEATURES (["res4"]) and STRIDE_IN_1X1 (True).  vnext_amd/models/resnet.py reads DEPTH, STRIDE_IN_1X1 and OUT_FEATURES and
+    refuses any other value of the rest."""
+    return _ns(DEPTH=50, STRIDE_IN_1X1=False, OUT_FEATURES=["res2", "res3", "res4", "res5"], NORM="FrozenBN",
+               RES5_DILATION=1, NUM_GROUPS=1, WIDTH_PER_GROUP=64, RES2_OUT_CHANNELS=256, STEM_OUT_CHANNELS=64,
+               DEFORM_ON_PER_STAGE=[False, False, False, False], DEFORM_MODULATED=False, DEFORM_NUM_GROUPS=1)
 
 
 def _swin_ns():
@@ -73,7 +83,7 @@ def get_seqformer_cfg(**overrides):
     cfg = _ns(
         MODEL=_ns(META_ARCHITECTURE="SeqFormer", DEVICE="cuda",
                   PIXEL_MEAN=[123.675, 116.280, 103.530], PIXEL_STD=[58.395, 57.120, 57.375],
-                  MASK_ON=True, BACKBONE=_backbone_ns(), SWIN=_swin_ns(),
+                  MASK_ON=True, BACKBONE=_backbone_ns(), RESNETS=_resnets_ns(), SWIN=_swin_ns(),
                   SeqFormer=_ns(NUM_CLASSES=40, MASK_WEIGHT=2.0, DICE_WEIGHT=5.0, GIOU_WEIGHT=2.0, L1_WEIGHT=5.0,
                                 CLASS_WEIGHT=2.0, DEEP_SUPERVISION=True, MASK_STRIDE=4, MATCH_STRIDE=4,
                                 FOCAL_ALPHA=0.25, SET_COST_CLASS=2, SET_COST_BOX=5, SET_COST_GIOU=2,
@@ -99,7 +109,7 @@ def get_idol_cfg(**overrides):
     cfg = _ns(
         MODEL=_ns(META_ARCHITECTURE="IDOL", DEVICE="cuda",
                   PIXEL_MEAN=[123.675, 116.280, 103.530], PIXEL_STD=[58.395, 57.120, 57.375], MASK_ON=True,
-                  BACKBONE=_backbone_ns(), SWIN=_swin_ns(),
+                  BACKBONE=_backbone_ns(), RESNETS=_resnets_ns(), SWIN=_swin_ns(),
                   IDOL=_ns(NUM_CLASSES=40, MASK_WEIGHT=2.0, DICE_WEIGHT=5.0, GIOU_WEIGHT=2.0, L1_WEIGHT=5.0,
                            CLASS_WEIGHT=2.0, REID_WEIGHT=2.0, DEEP_SUPERVISION=True, MASK_STRIDE=4, MATCH_STRIDE=4,
                            FOCAL_ALPHA=0.25, SET_COST_CLASS=2, SET_COST_BOX=5, SET_COST_GIOU=2,

@@ -446,6 +446,24 @@ def enable_fused_swin_glue(model, on: bool = True) -> None:
         m.fused_glue = bool(on)
 
 
+def enable_fused_resnet_glue(model, on: bool = True) -> None:
+    """Opt in to the fused element-wise glue of the ResNet trunk (`ResNetTrunk.fused_glue`, vnext_amd/ops/resnet_glue.py):
+    on CUDA the trunk's convolutions run without a bias and one HIP pass per site adds the folded batch norm's shift,
+    applies the ReLU and, at a block's tail, adds the shortcut (with the projection's own shift) -- three launches per
+    bottleneck instead of seven or eight; with a frozen stem or without grad, the stem's shift, ReLU and max-pool are one
+    pass that writes only the pooled map.  fp32 results are the eager chain's wherever the convolution itself does not
+    round its bias differently; under autocast each site rounds once instead of once per step -- except that a 16-bit
+    TRAINING step keeps the eager chain at a block's tail (two fused sites per block: results bit-identical to the switch
+    off).  Same modules and state-dict names.  CPU tensors and tensors in neither memory format keep the eager chain.  Raises for a model without
+    a ResNet trunk (the Swin backbone)."""
+    from .models.resnet import ResNetTrunk
+    mods = [m for m in model.modules() if isinstance(m, ResNetTrunk)]
+    if not mods:
+        raise ValueError("enable_fused_resnet_glue: %s has no ResNet trunk" % type(model).__name__)
+    for m in mods:
+        m.fused_glue = bool(on)
+
+
 def build_optimizer(model, base_lr=2e-4, backbone_multiplier=0.1, weight_decay=1e-4):
     """AdamW, backbone at base_lr * multiplier (train_net.py:85-113)."""
     backbone, rest = [], []
