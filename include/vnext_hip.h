@@ -1022,6 +1022,68 @@ int vnx_augment_masks(const void* ends, size_t n_ends, const void* mask_rows, in
                       void* masks, size_t mask_bytes, void* boxes, void* nonempty, void* workspace, size_t workspace_bytes,
                       void* hip_stream);
 
+/*
+ * Clipped AdamW step (optim.hip): the full-model gradient norm, clip_grad_norm_'s coefficient and the decoupled AdamW
+ * update of EVERY parameter tensor of a model in three launches, whatever the number of tensors.  ADDITIVE: two symbols, no
+ * existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.
+ *
+ * The kernels work from three tables in device memory.
+ *   tensors: vnx_adamw_tensor [n_tensors], 16-byte aligned, one row per parameter tensor: the fp32 device pointers p, g, m, v
+ *     (numel elements each, walked as flat memory), the index of the tensor's row in groups, flags, and the tensor's two
+ *     bias corrections 1 - beta1^step and sqrt(1 - beta2^step) of the step being taken, computed by the caller in double.
+ *     g == NULL: the tensor is skipped this step (nothing of it is read or written; it adds 0 to the norm).
+ *     VNX_ADAMW_UNALIGNED in flags: one of the four pointers is not 16-byte aligned; the tensor takes 4-byte accesses.  A
+ *     row WITHOUT the flag promises four 16-byte aligned pointers.
+ *   groups: vnx_adamw_group [n_groups], 16-byte aligned, doubles: lr, weight_decay, beta1, beta2, eps, and decay = 1 - lr *
+ *     weight_decay, 1 - beta1, 1 - beta2 as the caller computes them.
+ *   chunks: int64 [n_chunks][2] = {tensor index, element offset}: the tensors cut into pieces of VNX_ADAMW_CHUNK elements
+ *     (the last piece of a tensor may be shorter; offsets are multiples of VNX_ADAMW_CHUNK; no piece crosses a tensor).  The
+ *     list depends on the element counts alone; one workgroup handles one chunk.  A chunk that names no tensor or lies
+ *     outside its tensor is ignored (its partial is 0).
+ *
+ * vnx_adamw_grad_norm, two launches: every chunk's sum of g^2, accumulated in fp32, goes to its own slot of partials (fp32
+ * [n_chunks]; EVERY slot is written, no memset is needed), then one workgroup folds the slots in a fixed order in double
+ * and leaves total_norm = sqrt(sum) and coef = min(1, max_norm / (total_norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s
+ * expression for the L2 norm with error_if_nonfinite=False; a NaN norm gives a NaN coefficient, an infinite one 0 -- in
+ * norm, 16 bytes, 8-byte aligned: {float total_norm, float coef, double coef}.
+ *
+ * vnx_adamw_clipped_step, one launch: with g' = g * coef (coef read from norm in device memory: no host synchronisation)
+ *   p <- p * decay;  m <- m + (1 - beta1) (g' - m);  v <- beta2 v + (1 - beta2) g'^2;
+ *   p <- p - (lr / bc1) * m / (sqrt(v) / bc2_sqrt + eps)
+ * on fp32 tensors: torch.optim.AdamW (decoupled weight decay, no amsgrad, no maximize).  The multiply-adds of the three
+ * updates run in double and each result is rounded to fp32 once; the denominator is fp32, with a correctly rounded square root
+ * and divisions, from the new fp32 m and v.  The clipped gradients are NOT written back
+ * -- g is only read; this is the one difference from clip_grad_norm_ followed by AdamW.step, which leaves g rescaled in
+ * place.  Non-finite gradients get no special case: they propagate into m, v and p as the expression says.
+ *
+ * 16-byte loads and stores on tensors without VNX_ADAMW_UNALIGNED, 4-byte ones on the others and on a tensor's last numel % 4
+ * elements; no read or write outside [0, numel) of any tensor.  No atomics anywhere: two runs on the same inputs are
+ * bit-identical.  No workspace beyond partials, no allocation, no synchronisation.  n_chunks == 0: vnx_adamw_grad_norm
+ * still writes norm (total_norm 0, coef 1) in one launch; vnx_adamw_clipped_step returns VNX_OK without a launch.
+ */
+#define VNX_ADAMW_CHUNK 4096
+#define VNX_ADAMW_UNALIGNED 1
+typedef struct vnx_adamw_tensor {
+  void* p;
+  const void* g;
+  void* m;
+  void* v;
+  long long numel;
+  int group;
+  int flags;
+  float bias_correction1;      /* 1 - beta1^step */
+  float bias_correction2_sqrt; /* sqrt(1 - beta2^step) */
+  int reserved[2];
+} vnx_adamw_tensor;            /* 64 bytes */
+typedef struct vnx_adamw_group {
+  double lr, weight_decay, beta1, beta2, eps;
+  double decay, one_minus_beta1, one_minus_beta2;
+} vnx_adamw_group;             /* 64 bytes */
+int vnx_adamw_grad_norm(const void* tensors, int n_tensors, const void* chunks, long long n_chunks, double max_norm,
+                        void* partials, void* norm, void* hip_stream);
+int vnx_adamw_clipped_step(const void* tensors, int n_tensors, const void* groups, int n_groups, const void* chunks,
+                           long long n_chunks, const void* norm, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -1,6 +1,6 @@
 """Where a SeqFormer training step spends its wall time (synchronising between phases, so the sum
 exceeds the pipelined step).  python tools/step_breakdown.py [--graph] [--device-matching] [--fused-mask-loss]
-[--fused-set-loss] [--idol [--fused-reid-loss]]
+[--fused-set-loss] [--idol [--fused-reid-loss]] [--fused-optimizer] [--clips N]
 
 --device-matching: the same rows with SeqFormer's device-side matcher (train.enable_device_matching), so the "matching"
 row and the step can be read side by side with the host matcher's.
@@ -9,7 +9,11 @@ the "full forward" and "backward" rows carry the difference.
 --fused-set-loss: likewise with the criterion's class and box losses from the fused op (train.enable_fused_set_loss).
 --idol: the IDOL step instead (one 720 x 1280 pair, 8 objects: the bench's IDOL leg); its forward is one row, the trunk and
 the matching are not timed apart.
---fused-reid-loss: with --idol, both reid losses from the fused op (train.enable_fused_reid_loss); SeqFormer has none."""
+--fused-reid-loss: with --idol, both reid losses from the fused op (train.enable_fused_reid_loss); SeqFormer has none.
+--fused-optimizer: the clipped AdamW op (train.build_fused_optimizer) instead of clip_grad_norm_ + AdamW: the two tail rows
+become one.
+--clips N: SeqFormer clips per step (default 1; the bench's step has 2).
+The last line is the kernel launches of one whole train_step (torch.profiler), in a pass of its own."""
 import argparse
 import os
 import sys
@@ -29,6 +33,8 @@ ap.add_argument("--fused-mask-loss", action="store_true")
 ap.add_argument("--fused-set-loss", action="store_true")
 ap.add_argument("--fused-reid-loss", action="store_true")
 ap.add_argument("--idol", action="store_true")
+ap.add_argument("--fused-optimizer", action="store_true")
+ap.add_argument("--clips", type=int, default=1)
 ap.add_argument("--steps", type=int, default=8)
 a = ap.parse_args()
 dev = "cuda:0"
@@ -43,9 +49,9 @@ if a.fused_mask_loss:
     T.enable_fused_mask_loss(model)
 if a.fused_set_loss:
     T.enable_fused_set_loss(model)
-opt = T.build_optimizer(model)
+opt = T.build_fused_optimizer(model) if a.fused_optimizer else T.build_optimizer(model)
 clips = T.synthetic_clips(1, 2, 720, 1280, dev, seed=8, num_instances=8) if a.idol else \
-    T.synthetic_clips(1, 5, 360, 640, dev, seed=100, num_instances=4)
+    T.synthetic_clips(a.clips, 5, 360, 640, dev, seed=100, num_instances=4)
 for _ in range(3):
     T.train_step(model, opt, clips)
 
@@ -88,6 +94,10 @@ for _ in range(a.steps):
     opt.zero_grad(set_to_none=True)
     total.backward()
     t = tick("backward", t)
+    if a.fused_optimizer:
+        opt.step()
+        t = tick("clip_grad_norm + AdamW step (one op)", t)
+        continue
     params = [p for g in opt.param_groups for p in g["params"]]
     torch.nn.utils.clip_grad_norm_(params, 0.01)
     t = tick("clip_grad_norm", t)
@@ -95,3 +105,12 @@ for _ in range(a.steps):
     t = tick("AdamW step", t)
 for k, v in marks.items():
     print(f"{k:70s} {v / a.steps:8.2f} ms")
+
+from torch.profiler import ProfilerActivity, profile  # noqa: E402
+torch.cuda.synchronize()
+with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+    T.train_step(model, opt, clips)
+    torch.cuda.synchronize()
+names = [e.name.lower() for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+kernels = [n for n in names if not n.startswith(("memcpy", "memset", "optimizer.step#"))]
+print(f"{'kernel launches of one train_step':70s} {len(kernels):8d}    (+ {len(names) - len(kernels)} copies / memsets / annotations)")

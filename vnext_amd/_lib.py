@@ -30,6 +30,7 @@ CLIP_LINK_MAX_INSTANCES, CLIP_LINK_MAX_FRAMES = 16, 8      # VNX_CLIP_LINK_MAX_I
 INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVELS, VNX_INGEST_MAX_POS_FEATS
 RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                            # VNX_LAYOUT_NCHW, VNX_LAYOUT_NHWC
+OPT_CHUNK, ADAMW_UNALIGNED = 4096, 1                       # VNX_ADAMW_CHUNK, VNX_ADAMW_UNALIGNED
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 
@@ -108,6 +109,8 @@ SIGNATURES = {
     "vnx_augment_frames": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _i, _i, _i] + [ctypes.c_float] * 6 + [_i, _i, _vp, _vp, _vp]),
     "vnx_augment_masks_workspace": (_sz, [_i, _i, _i]),
     "vnx_augment_masks": (_i, [_vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "vnx_adamw_grad_norm": (_i, [_vp, _i, _vp, _ll, ctypes.c_double, _vp, _vp, _vp]),
+    "vnx_adamw_clipped_step": (_i, [_vp, _i, _vp, _i, _vp, _ll, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
@@ -157,6 +160,18 @@ class MaskLossClips(ctypes.Structure):
     kernels by value."""
     _fields_ = [("masks", _vp * MASK_LOSS_MAX_CLIPS), ("height", _i * MASK_LOSS_MAX_CLIPS),
                 ("width", _i * MASK_LOSS_MAX_CLIPS), ("first", _i * MASK_LOSS_MAX_CLIPS), ("count", _i), ("total", _i)]
+
+
+class AdamWTensor(ctypes.Structure):
+    """`vnx_adamw_tensor` of include/vnext_hip.h, field by field: a row of the tensor table in device memory (64 bytes)."""
+    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("numel", _ll), ("group", _i), ("flags", _i),
+                ("bias_correction1", ctypes.c_float), ("bias_correction2_sqrt", ctypes.c_float), ("reserved", _i * 2)]
+
+
+class AdamWGroup(ctypes.Structure):
+    """`vnx_adamw_group` of include/vnext_hip.h, field by field: a row of the group table in device memory (64 bytes)."""
+    _fields_ = [(k, ctypes.c_double) for k in ("lr", "weight_decay", "beta1", "beta2", "eps", "decay", "one_minus_beta1",
+                                              "one_minus_beta2")]
 
 
 _lib = None          # the product library
