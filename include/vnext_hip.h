@@ -1084,6 +1084,58 @@ int vnx_adamw_grad_norm(const void* tensors, int n_tensors, const void* chunks, 
 int vnx_adamw_clipped_step(const void* tensors, int n_tensors, const void* groups, int n_groups, const void* chunks,
                            long long n_chunks, const void* norm, void* hip_stream);
 
+/*
+ * Video mask IoU from run lengths: the integer sums of the YTVIS evaluator's IoU (YTVOSeval.computeIoU) and the decode of
+ * compressed COCO RLE strings into the run tables they are taken from (video_iou.hip; ABI 17, additive).
+ *
+ * A mask is a slice of two int32 arenas of run_slots elements each: ends[k] = the column-major pixel index at which run
+ * k ends (the cumulative sum of the COCO counts; run 0 counts zeros), ones[k] = the number of set pixels below ends[k].
+ * A pixel's bit is the parity of the upper bound of its index in ends, so zero-length runs are harmless.  rows int32
+ * [masks][4] = {arena offset, runs, pixel count h * w, area}, 16-byte aligned.
+ *
+ * vnx_rle_runs_measure / vnx_rle_runs_write turn strings in the format stated at vnx_mask_rle_* (a byte arena of
+ * arena_bytes, offsets and lengths int64 [masks]) into such tables.  A string has as many counts as it has bytes without
+ * the continuation bit (byte - 48) & 0x20: measure writes that number to runs int32 [masks]; the caller scans it into
+ * run_offsets int32 [masks] and passes both back to write with pixels int32 [masks] (h * w of each mask) and arenas of
+ * run_slots >= the sum.  write fills the slots, rows and status int32 [masks]: 0, or an OR of the VNX_RLE_RUNS_* bits --
+ * a byte outside 48..111; a string that ends inside a count; a negative count or one of more than 7 characters; runs
+ * that do not sum to the pixel count (an empty string included); a string outside the byte arena, a slot outside the
+ * run arenas or not of the measured size.  A mask with a non-zero status gets the empty table (runs 0, area 0; the
+ * contents of its own slot are unspecified).  Whatever the bytes are, no read leaves [offset, offset + length) of a
+ * string and no write leaves a mask's slot.  One wave per string; no atomics, no workspace, no allocation, no
+ * synchronisation.  masks == 0 is a no-op; run_slots >= 2^31 is VNX_ERR_UNSUPPORTED.
+ *
+ * vnx_video_iou_sums: frame_mask int32 [frame_slots] = the mask index per (track, frame), -1 where the track has no mask
+ * in that frame; tracks int32 [n_tracks][2] = {first, frames} into frame_mask; pairs int32 [n_pairs][2] = {detection
+ * track, ground-truth track} (both 8-byte aligned).  sums int64 [n_pairs][4] = {sum over the frames of the intersection,
+ * of the detection's area, of the ground truth's area, status}; an absent mask has area 0 and no intersection, so the
+ * IoU of the pair is I / (A_d + A_g - I) (0 when that is 0), formed by the caller in double.  status is non-zero, with
+ * zero sums, when the two tracks differ in frame count (VNX_VIDEO_IOU_FRAMES), a frame's two masks differ in pixel
+ * count (VNX_VIDEO_IOU_PIXELS) or an index or a row points outside its table (VNX_VIDEO_IOU_BAD_TABLE): nothing outside
+ * the tables the sizes describe is read.  One wave per pair, no atomics, no workspace: the output is a function of the
+ * input alone.  n_pairs == 0 is a no-op.
+ */
+enum {
+  VNX_RLE_RUNS_BAD_BYTE = 1,
+  VNX_RLE_RUNS_TRUNCATED = 2,
+  VNX_RLE_RUNS_NEGATIVE = 4,
+  VNX_RLE_RUNS_BAD_SUM = 8,
+  VNX_RLE_RUNS_BAD_SLOT = 16
+};
+enum {
+  VNX_VIDEO_IOU_FRAMES = 1,
+  VNX_VIDEO_IOU_PIXELS = 2,
+  VNX_VIDEO_IOU_BAD_TABLE = 4
+};
+int vnx_rle_runs_measure(const void* bytes, long long arena_bytes, const void* offsets, const void* lengths, int masks,
+                         void* runs, void* hip_stream);
+int vnx_rle_runs_write(const void* bytes, long long arena_bytes, const void* offsets, const void* lengths,
+                       const void* pixels, const void* run_offsets, const void* runs, int masks, void* ends, void* ones,
+                       long long run_slots, void* rows, void* status, void* hip_stream);
+int vnx_video_iou_sums(const void* ends, const void* ones, long long run_slots, const void* rows, int masks,
+                       const void* frame_mask, long long frame_slots, const void* tracks, int n_tracks,
+                       const void* pairs, long long n_pairs, void* sums, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -31,6 +31,9 @@ INGEST_MAX_LEVELS, INGEST_MAX_POS_FEATS = 8, 128           # VNX_INGEST_MAX_LEVE
 RESIZE_MAX_KSIZE = 17                                      # VNX_RESIZE_MAX_KSIZE
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1                            # VNX_LAYOUT_NCHW, VNX_LAYOUT_NHWC
 OPT_CHUNK, ADAMW_UNALIGNED = 4096, 1                       # VNX_ADAMW_CHUNK, VNX_ADAMW_UNALIGNED
+# VNX_RLE_RUNS_* status bits of vnx_rle_runs_write, VNX_VIDEO_IOU_* status values of vnx_video_iou_sums
+RLE_RUNS_BAD_BYTE, RLE_RUNS_TRUNCATED, RLE_RUNS_NEGATIVE, RLE_RUNS_BAD_SUM, RLE_RUNS_BAD_SLOT = 1, 2, 4, 8, 16
+VIDEO_IOU_FRAMES, VIDEO_IOU_PIXELS, VIDEO_IOU_BAD_TABLE = 1, 2, 4
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 
@@ -111,6 +114,9 @@ SIGNATURES = {
     "vnx_augment_masks": (_i, [_vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "vnx_adamw_grad_norm": (_i, [_vp, _i, _vp, _ll, ctypes.c_double, _vp, _vp, _vp]),
     "vnx_adamw_clipped_step": (_i, [_vp, _i, _vp, _i, _vp, _ll, _vp, _vp]),
+    "vnx_rle_runs_measure": (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp]),
+    "vnx_rle_runs_write": (_i, [_vp, _ll] + [_vp] * 5 + [_i, _vp, _vp, _ll, _vp, _vp, _vp]),
+    "vnx_video_iou_sums": (_i, [_vp, _vp, _ll, _vp, _i, _vp, _ll, _vp, _i, _vp, _ll, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {
