@@ -1136,6 +1136,47 @@ int vnx_video_iou_sums(const void* ends, const void* ones, long long run_slots, 
                        const void* frame_mask, long long frame_slots, const void* tracks, int n_tracks,
                        const void* pairs, long long n_pairs, void* sums, void* hip_stream);
 
+/*
+ * The greedy matching of the COCO-style AP evaluators (COCOeval.evaluateImg, YTVOSeval.evaluateVid) for every (image,
+ * category) problem of an evaluation, all area ranges and all IoU thresholds in one launch (ap_match.hip; host
+ * specification: vnext_amd/ops/ap_match.py match_host).  ADDITIVE: one symbol, no existing signature changed, so
+ * VNX_ABI_VERSION stays 17; a binding that needs it looks it up.
+ *
+ * table int64 [problems][5] = {D, G, detection offset, ground-truth offset, IoU offset}: problem p owns detections
+ * [offset, offset + D) of dt_area double [n_dt], ground truths [offset, offset + G) of gt_crowd uint8 [n_gt] and gt_area
+ * double [n_gt], and the row-major [D][G] matrix at its IoU offset in ious double [n_iou].  The detections stand in the
+ * order the reference visits them (by score, cut to the last maxDets), the ground truths in their given order.
+ * area_rng double [n_area][2] = {low, high}, thrs double [n_thrs].
+ *
+ * Per (area range a, threshold t, problem): a ground truth is ignored when it is a crowd or its area is < low or >
+ * high.  The detections take, one after the other, the ground truth of the highest IoU >= min(thrs[t], 1 - 1e-10)
+ * among those still free (a crowd stays free), the later one on a tie, where "later" is the reference's order: the
+ * ground truths that are not ignored in their given order, then the ignored ones, which are looked at only while the
+ * detection holds no match.  Outputs, in problem-local indices, -1 for none: dt_match int32 [n_area][n_thrs][n_dt] (the
+ * ground truth a detection took), dt_ignore uint8 [n_area][n_thrs][n_dt] (that ground truth's ignore flag; for a
+ * detection without a match, whether its area is < low or > high), gt_match int32 [n_area][n_thrs][n_gt] (the last
+ * detection that took it), gt_ignore uint8 [n_area][n_gt].  Ids are the caller's: it maps the indices.
+ *
+ * One wave64 per problem, one lane per (a, t), the lane's bit sets in LDS; no atomics, no workspace, every element
+ * written by one lane: the result is byte-identical run to run.  Elements no problem owns are not written.
+ * Limits: n_area * n_thrs <= VNX_AP_MATCH_MAX_LANES (VNX_ERR_UNSUPPORTED beyond) and G <= VNX_AP_MATCH_MAX_GT per problem.
+ * status int32 [1], zeroed by the caller: a row with G above the limit writes nothing and stores VNX_AP_MATCH_GT_LIMIT;
+ * a row with a negative entry or a range that leaves n_dt, n_gt or n_iou writes nothing, reads nothing beyond the row
+ * and stores VNX_AP_MATCH_BAD_TABLE (with several such rows one of their codes stays).  Rows that overlap each other
+ * are not detected.  problems == 0 is a no-op.  Not measured against a host implementation in C; the timings of
+ * profiles/coco_eval.json compare it with this package's numpy route.
+ */
+#define VNX_AP_MATCH_MAX_GT 512
+#define VNX_AP_MATCH_MAX_LANES 64
+enum {
+  VNX_AP_MATCH_BAD_TABLE = 1,
+  VNX_AP_MATCH_GT_LIMIT = 2
+};
+int vnx_ap_match(const void* table, long long problems, const void* ious, long long n_iou, const void* gt_crowd,
+                 const void* gt_area, long long n_gt, const void* dt_area, long long n_dt, const void* area_rng,
+                 int n_area, const void* thrs, int n_thrs, void* dt_match, void* dt_ignore, void* gt_match,
+                 void* gt_ignore, void* status, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

@@ -47,9 +47,12 @@ class YTVISEval:
     device: a CUDA device for the kernels; None = CUDA when this process has one and the library is built, else the
     numpy path; "cpu" = the numpy path.  iou_thrs, rec_thrs, max_dets, area_rng: the reference's Params (defaults: 0.5 :
     0.05 : 0.95, 0 : 0.01 : 1, [1, 10, 100], all / small / medium / large at 128^2 and 256^2).
+    device_matching: with a CUDA device, the matching of every (video, category) goes through the kernel of
+    ops/ap_match.py (one launch) instead of the Python loop of `_evaluate_vid`; the results are identical.
     """
 
-    def __init__(self, gt, device=None, iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100), area_rng=None):
+    def __init__(self, gt, device=None, iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100), area_rng=None,
+                 device_matching=False):
         if isinstance(gt, (str, os.PathLike)):
             with open(gt) as f:
                 gt = json.load(f)
@@ -76,6 +79,7 @@ class YTVISEval:
                     raise ValueError(f"YTVISEval: annotation {ann.get('id')} frame {f} is a polygon; only RLE ground "
                                      "truth is supported")
         self.records = []
+        self.device_matching = bool(device_matching) and self.device is not None
 
     def add(self, records):
         """records: what `model.ytvis_results(inputs)` returns ({"video_id", "score", "category_id", "segmentations"});
@@ -203,13 +207,16 @@ class YTVISEval:
                 else:
                     ious[v, c] = iou[at:at + D * G].reshape(D, G).copy()
                     at += D * G
-        eval_vids = [self._evaluate_vid(gts.get((v, c), []), dts.get((v, c), []), ious[v, c], v, c, a, max_det)
-                     for c in self.cat_ids for a in self.area_rng for v in self.vid_ids]
+        if self.device_matching:
+            eval_vids = self._evaluate_vids_device(groups, gts, dts, iou, max_det)
+        else:
+            eval_vids = [self._evaluate_vid(gts.get((v, c), []), dts.get((v, c), []), ious[v, c], v, c, a, max_det)
+                         for c in self.cat_ids for a in self.area_rng for v in self.vid_ids]
         t3 = time.perf_counter()
         out = self._accumulate(eval_vids)
         # host clock, seconds: run tables (decode included), pair sums (copies included), matching, accumulation
         self.timings = {"tables_s": t1 - t0, "sums_s": t2 - t1, "match_s": t3 - t2, "accumulate_s": time.perf_counter() - t3,
-                        "masks": len(tables), "pairs": len(pairs)}
+                        "masks": len(tables), "pairs": len(pairs), "device_matching": self.device_matching}
         out["stats"] = self._summarize(out["precision"], out["recall"])
         out.update({n: float(s) for n, s in zip(STAT_NAMES, out["stats"])})
         out["per_category"] = {}
@@ -264,6 +271,48 @@ class YTVISEval:
                 "dtIds": [d["id"] for d in dt], "gtIds": [g["id"] for g in gt], "dtMatches": dtm, "gtMatches": gtm,
                 "dtScores": [d["score"] for d in dt], "gtIgnore": gt_ig, "dtIgnore": dt_ig}
 
+    def _evaluate_vids_device(self, groups, gts, dts, iou, max_det):
+        """`_evaluate_vid` for every (category, area range, video) from one launch of the matching kernel: `groups` in
+        the order of the flat IoU array, the detections already in score order and cut to `max_det`."""
+        import torch
+        from ..ops import ap_match as M
+        rows, n_dt, n_gt, n_iou = {}, 0, 0, 0
+        for key in groups:
+            D, G = len(dts.get(key, [])), len(gts.get(key, []))
+            rows[key] = (D, G, n_dt, n_gt, n_iou)
+            n_dt, n_gt, n_iou = n_dt + D, n_gt + G, n_iou + D * G
+        all_g = [g for key in groups for g in gts.get(key, [])]
+        all_d = [d for key in groups for d in dts.get(key, [])]
+        dev = torch.device(self.device)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt))).to(dev)   # noqa: E731
+        table = np.array([rows[key] for key in groups], dtype=np.int64).reshape(-1, 5)
+        m = M.ap_match(up(table, np.int64), up(iou, np.float64).reshape(-1), up([g["iscrowd"] for g in all_g], np.uint8),
+                       up([g["avg_area"] for g in all_g], np.float64), up([d["avg_area"] for d in all_d], np.float64),
+                       up(self.area_rng, np.float64).reshape(-1, 2), up(self.iou_thrs, np.float64)).numpy()
+        out = []
+        for c in self.cat_ids:
+            for a, rng in enumerate(self.area_rng):
+                for v in self.vid_ids:
+                    if (v, c) not in rows:
+                        out.append(None)
+                        continue
+                    D, G, dof, gof, _ = rows[v, c]
+                    gt, dt = gts.get((v, c), []), dts.get((v, c), [])
+                    ig = m.gt_ignore[a, gof:gof + G].astype(np.int64)
+                    gtind = np.argsort(ig, kind="mergesort")            # the reference's order: ignored last, stable
+                    gt_ids = np.array([g["id"] for g in gt], dtype=np.float64)
+                    dt_ids = np.array([d["id"] for d in dt], dtype=np.float64)
+                    dm, gm = m.dt_match[a, :, dof:dof + D], m.gt_match[a, :, gof:gof + G]
+                    dtm = np.where(dm >= 0, gt_ids[np.maximum(dm, 0)], 0.0) if G else np.zeros(dm.shape)
+                    gtm = np.where(gm >= 0, dt_ids[np.maximum(gm, 0)], 0.0) if D else np.zeros(gm.shape)
+                    outside = np.array([d["avg_area"] < rng[0] or d["avg_area"] > rng[1] for d in dt]).reshape((1, D))
+                    dt_ig = np.logical_or(m.dt_ignore[a, :, dof:dof + D] != 0, np.logical_and(dtm == 0, outside))
+                    out.append({"video_id": v, "category_id": c, "aRng": rng, "maxDet": max_det,
+                                "dtIds": [d["id"] for d in dt], "gtIds": [gt[i]["id"] for i in gtind], "dtMatches": dtm,
+                                "gtMatches": gtm[:, gtind], "dtScores": [d["score"] for d in dt], "gtIgnore": ig[gtind],
+                                "dtIgnore": dt_ig})
+        return out
+
     # ---- YTVOSeval.accumulate -------------------------------------------------------------------------------------
     def _accumulate(self, eval_vids):
         T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.cat_ids), len(self.area_rng), len(self.max_dets)
@@ -307,30 +356,35 @@ class YTVISEval:
 
     # ---- YTVOSeval.summarize --------------------------------------------------------------------------------------
     def _summarize(self, precision, recall):
-        def one(ap=1, iou_thr=None, area="all", max_dets=100):
-            aind = [i for i, lbl in enumerate(AREA_LABELS) if lbl == area]
-            mind = [i for i, m in enumerate(self.max_dets) if m == max_dets]
-            s = precision if ap == 1 else recall
-            if iou_thr is not None:
-                s = s[np.where(iou_thr == self.iou_thrs)[0]]
-            s = s[:, :, :, aind, mind] if ap == 1 else s[:, :, aind, mind]
-            return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
-        md = self.max_dets
-        last = md[2] if len(md) > 2 else -1
-        stats = np.zeros((12,))
-        stats[0] = one(1)
-        stats[1] = one(1, iou_thr=.5, max_dets=last)
-        stats[2] = one(1, iou_thr=.75, max_dets=last)
-        stats[3] = one(1, area="small", max_dets=last)
-        stats[4] = one(1, area="medium", max_dets=last)
-        stats[5] = one(1, area="large", max_dets=last)
-        stats[6] = one(0, max_dets=md[0])
-        stats[7] = one(0, max_dets=md[1] if len(md) > 1 else -1)
-        stats[8] = one(0, max_dets=last)
-        stats[9] = one(0, area="small", max_dets=last)
-        stats[10] = one(0, area="medium", max_dets=last)
-        stats[11] = one(0, area="large", max_dets=last)
-        return stats
+        return summarize(precision, recall, self.iou_thrs, self.max_dets)
+
+
+def summarize(precision, recall, iou_thrs, max_dets):
+    """The 12 numbers of `summarize` from precision [T, R, K, A, M] and recall [T, K, A, M]; -1 where nothing is defined."""
+    def one(ap=1, iou_thr=None, area="all", max_det=100):
+        aind = [i for i, lbl in enumerate(AREA_LABELS) if lbl == area]
+        mind = [i for i, m in enumerate(max_dets) if m == max_det]
+        s = precision if ap == 1 else recall
+        if iou_thr is not None:
+            s = s[np.where(iou_thr == iou_thrs)[0]]
+        s = s[:, :, :, aind, mind] if ap == 1 else s[:, :, aind, mind]
+        return -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+    md = max_dets
+    last = md[2] if len(md) > 2 else -1
+    stats = np.zeros((12,))
+    stats[0] = one(1)
+    stats[1] = one(1, iou_thr=.5, max_det=last)
+    stats[2] = one(1, iou_thr=.75, max_det=last)
+    stats[3] = one(1, area="small", max_det=last)
+    stats[4] = one(1, area="medium", max_det=last)
+    stats[5] = one(1, area="large", max_det=last)
+    stats[6] = one(0, max_det=md[0])
+    stats[7] = one(0, max_det=md[1] if len(md) > 1 else -1)
+    stats[8] = one(0, max_det=last)
+    stats[9] = one(0, area="small", max_det=last)
+    stats[10] = one(0, area="medium", max_det=last)
+    stats[11] = one(0, area="large", max_det=last)
+    return stats
 
 
 class YTVISEvaluator:
