@@ -1177,6 +1177,49 @@ int vnx_ap_match(const void* table, long long problems, const void* ious, long l
                  int n_area, const void* thrs, int n_thrs, void* dt_match, void* dt_ignore, void* gt_match,
                  void* gt_ignore, void* status, void* hip_stream);
 
+/*
+ * COCO polygons to run tables: pycocotools' frPyObjects (rleFrPoly) + merge (the union) for one annotation per workgroup
+ * (poly_rle.hip; host specification, step by step: vnext_amd/ops/poly_rle.py object_counts_host, to which the kernel is held
+ * count for count).  ADDITIVE: one symbol, no existing signature changed, so VNX_ABI_VERSION stays 17.
+ *
+ * coords double [n_coords], 8-byte aligned: the polygons' x0, y0, x1, y1, ... back to back.  poly_rows int32 [n_polys][4],
+ * 16-byte aligned = {coordinate offset, vertices, object, 0}.  obj_rows int32 [n_objects][6] = {first polygon, polygons,
+ * run-slot offset, slot size, h, w}: object m owns polygons [first, first + polygons) of poly_rows (each must name m) and
+ * the words [offset, offset + slot size) of ends and ones, int32 [run_slots] each.  An object without polygons is the
+ * empty mask.  A box is passed as its 4-vertex polygon.
+ *
+ * Per object: ends[offset + k] = the k-th run end of the union of its polygons' even-odd masks (h * w the last),
+ * ones[offset + k] = the set pixels below it, rows int32 [n_objects][4] = {offset, runs, h * w, area} as
+ * vnx_rle_runs_write leaves them.  The caller sizes the slot from a bound (the sum over the object's polygons of 1 + the sum
+ * over the edges of min(|X[j+1] - X[j]| / 5 + 1, w), X = (int)(5 x + 0.5), plus 1); the words of the slot beyond the runs
+ * are padded with ends = h * w and ones = area (zero-length runs), so a consumer may take the slot size for the run count.
+ * The line expressions are evaluated in double as a product and two additions, without contraction, the divisions IEEE.
+ *
+ * status int32 [n_objects]: 0, or an OR of the VNX_POLY_RLE_* bits -- a coordinate that is not finite or beyond 2^24 in
+ * magnitude; a polygon of fewer than 3 vertices; h * w outside [1, 2^31); more than VNX_POLY_RLE_MAX_VERTICES vertices in a
+ * polygon, VNX_POLY_RLE_MAX_POINTS dense points (the sum over the edges of max(|dX|, |dY|) + 1) or VNX_POLY_RLE_MAX_POLYGONS
+ * polygons in an object, VNX_POLY_RLE_MAX_CROSSINGS crossings in a polygon or toggles in an object, or a slot of more than
+ * VNX_POLY_RLE_MAX_CROSSINGS + 1 words; a row, a polygon or a slot outside its table, a polygon that names another object,
+ * or a slot smaller than the runs.  A flagged object gets the empty table (runs 0, area 0) and, where its slot lies inside
+ * the arenas, a slot filled with ends = h * w (0 for a bad size) and ones = 0 up to the cap.  Whatever the tables hold, no
+ * read leaves a buffer and no write leaves the object's slot.  One wave64 per object; no atomics, no workspace, no
+ * allocation, no synchronisation: capturable, and bit-identical run to run.  n_objects == 0 is a no-op; run_slots or
+ * n_coords >= 2^31 is VNX_ERR_UNSUPPORTED.
+ */
+#define VNX_POLY_RLE_MAX_VERTICES 1024
+#define VNX_POLY_RLE_MAX_CROSSINGS 4096
+#define VNX_POLY_RLE_MAX_POINTS 262144
+#define VNX_POLY_RLE_MAX_POLYGONS 256
+enum {
+  VNX_POLY_RLE_BAD_COORD = 1,
+  VNX_POLY_RLE_FEW_VERTICES = 2,
+  VNX_POLY_RLE_BAD_SIZE = 4,
+  VNX_POLY_RLE_CAP = 8,
+  VNX_POLY_RLE_BAD_SLOT = 16
+};
+int vnx_poly_rle(const void* coords, long long n_coords, const void* poly_rows, int n_polys, const void* obj_rows,
+                 int n_objects, void* ends, void* ones, long long run_slots, void* rows, void* status, void* hip_stream);
+
 /* (The kernel-variant override of rounds 1-3 -- a process-wide A/B knob -- is no longer part of this library: it lives in
  *  the development build only, include/vnext_hip_dev.h.  Every call here selects its kernels from its own arguments.) */
 

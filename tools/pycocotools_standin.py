@@ -3,12 +3,15 @@
 is not installed here; tools/make_golden_ytvis_eval.py registers this module under its name to run the reference's
 evaluator.  An RLE object is {"size": [h, w], "counts": str or bytes}, as pycocotools has it.
 
-Only what that evaluator needs: no polygons, no boxes as input, no `iou`, no `encode` / `decode`.
+Only what that evaluator needs: no `iou`, no `encode` / `decode`.  `frPyObjects` also takes polygons and boxes, through
+this package's restatement of `rleFrPoly` (vnext_amd/ops/poly_rle.py poly_counts_host) -- a restatement, never compared with
+the compiled package.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from vnext_amd.ops.poly_rle import object_polygons, poly_counts_host
 from vnext_amd.utils.ytvis_json import counts_to_string, rle_counts, string_to_counts
 
 
@@ -51,13 +54,18 @@ def merge(rles, intersect=False):
 
 
 def frPyObjects(obj, h, w):
-    """uncompressed RLE ({"size", "counts": list}) -> RLE object; a list of them -> a list"""
+    """uncompressed RLE ({"size", "counts": list}) -> RLE object; a list of them -> a list.  A list of polygons or of boxes
+    -> a list of RLE objects, one per polygon / box (merge them for the annotation's mask); one flat polygon or one box
+    [x, y, w, h] -> one RLE object."""
     if isinstance(obj, list) and all(isinstance(o, dict) for o in obj):
         return [frPyObjects(o, h, w) for o in obj]
     if isinstance(obj, dict) and "counts" in obj:
         assert list(obj["size"]) == [h, w]
         return {"size": [int(h), int(w)], "counts": counts_to_string(obj["counts"])}
-    raise NotImplementedError("pycocotools stand-in: only uncompressed RLE input (no polygons, no boxes)")
+    if isinstance(obj, (list, tuple, np.ndarray)) and len(obj):
+        rles = [{"size": [int(h), int(w)], "counts": counts_to_string(poly_counts_host(p, h, w))} for p in object_polygons(obj)]
+        return rles if isinstance(obj[0], (list, tuple, np.ndarray)) else rles[0]
+    raise NotImplementedError("pycocotools stand-in: uncompressed RLE, polygons or boxes")
 
 
 def toBbox(rles):

@@ -36,6 +36,9 @@ RLE_RUNS_BAD_BYTE, RLE_RUNS_TRUNCATED, RLE_RUNS_NEGATIVE, RLE_RUNS_BAD_SUM, RLE_
 VIDEO_IOU_FRAMES, VIDEO_IOU_PIXELS, VIDEO_IOU_BAD_TABLE = 1, 2, 4
 AP_MATCH_MAX_GT, AP_MATCH_MAX_LANES = 512, 64              # VNX_AP_MATCH_MAX_GT, VNX_AP_MATCH_MAX_LANES
 AP_MATCH_BAD_TABLE, AP_MATCH_GT_LIMIT = 1, 2               # VNX_AP_MATCH_* status values of vnx_ap_match
+# VNX_POLY_RLE_MAX_* caps and VNX_POLY_RLE_* status bits of vnx_poly_rle
+POLY_RLE_MAX_VERTICES, POLY_RLE_MAX_CROSSINGS, POLY_RLE_MAX_POINTS, POLY_RLE_MAX_POLYGONS = 1024, 4096, 262144, 256
+POLY_RLE_BAD_COORD, POLY_RLE_FEW_VERTICES, POLY_RLE_BAD_SIZE, POLY_RLE_CAP, POLY_RLE_BAD_SLOT = 1, 2, 4, 8, 16
 
 _vp, _i, _sz, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong
 
@@ -120,6 +123,7 @@ SIGNATURES = {
     "vnx_rle_runs_write": (_i, [_vp, _ll] + [_vp] * 5 + [_i, _vp, _vp, _ll, _vp, _vp, _vp]),
     "vnx_video_iou_sums": (_i, [_vp, _vp, _ll, _vp, _i, _vp, _ll, _vp, _i, _vp, _ll, _vp, _vp]),
     "vnx_ap_match": (_i, [_vp, _ll, _vp, _ll, _vp, _vp, _ll, _vp, _ll, _vp, _i, _vp, _i] + [_vp] * 6),
+    "vnx_poly_rle": (_i, [_vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _ll, _vp, _vp, _vp]),
 }
 # measurement aids of include/vnext_hip_debug.h (bench.py, tools/): not part of the drop-in boundary
 DEBUG_SIGNATURES = {

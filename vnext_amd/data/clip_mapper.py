@@ -22,6 +22,12 @@ slot stays, filled with the dummy, as in the reference).  The entry of `batched_
 frames), "augment" (the plan) and "instances": per frame a dict with gt_classes int64 [n], gt_ids int64 [n], gt_rle (the
 masks' COCO counts at SOURCE resolution, a list per slot) and image_size = (nh, nw).  A model with `device_augment` fills
 gt_masks, gt_boxes and the filtered gt_ids from one `augment_masks` call for the whole step.
+
+`stage_clip(..., polygons=True)` keeps an annotation whose `segmentation` is a list (polygons or boxes, as `frPyObjects`
+takes them) as it is: the frame dict then also holds gt_poly, a list per slot -- the polygon list, or None where the slot is
+RLE, whose gt_rle entry is None where the slot is a polygon -- and the dummy slot is the reference's polygon [0.0] * 6
+(`_get_dummy_anno`).  The model transforms the coordinates on the host and rasterises them at the target size on the device
+(vnext_amd/ops/poly_rle.py).
 """
 from __future__ import annotations
 
@@ -94,10 +100,16 @@ def _counts(segmentation):
     return [int(c) for c in segmentation]
 
 
-def stage_clip(frames, annotations, plan, num_classes, layout: str = "chw"):
+def _is_polygons(segmentation):
+    """a list of polygons or of boxes (a FLAT list of numbers stays what it was: COCO counts; one box goes in as [[x, y, w, h]])"""
+    return isinstance(segmentation, (list, tuple)) and (
+        len(segmentation) == 0 or isinstance(segmentation[0], (list, tuple, np.ndarray)))
+
+
+def stage_clip(frames, annotations, plan, num_classes, layout: str = "chw", polygons: bool = False):
     """frames: the clip's uint8 SOURCE frames; annotations: per frame a list of dicts with "id", "category_id",
-    "segmentation" (COCO counts: a list, a compressed string, or an RLE dict of either) and optionally "iscrowd"
-    -> the clip's entry of `batched_inputs`; see the module docstring."""
+    "segmentation" (COCO counts: a list, a compressed string, or an RLE dict of either; with `polygons=True` also a list of
+    polygons or boxes) and optionally "iscrowd" -> the clip's entry of `batched_inputs`; see the module docstring."""
     assert len(frames) == len(annotations) == len(plan)
     slots = {}
     for annos in annotations:
@@ -107,13 +119,22 @@ def stage_clip(frames, annotations, plan, num_classes, layout: str = "chw"):
     for f, annos, p in zip(frames, annotations, plan):
         h, w = resize.frame_size(f, layout)
         classes, ids, rles = [num_classes] * len(slots), [-1] * len(slots), [[h * w] for _ in slots]      # the dummy
+        polys = [None] * len(slots)
+        if polygons:                         # the reference's dummy is a polygon
+            rles, polys = [None] * len(slots), [[[0.0] * 6] for _ in slots]
         for a in annos:
             if a.get("iscrowd", 0) != 0:
                 continue
             s = slots[a["id"]]
-            classes[s], ids[s], rles[s] = int(a["category_id"]), int(a["id"]), _counts(a["segmentation"])
+            classes[s], ids[s] = int(a["category_id"]), int(a["id"])
+            if polygons and _is_polygons(a["segmentation"]):
+                rles[s], polys[s] = None, a["segmentation"]
+            else:
+                rles[s], polys[s] = _counts(a["segmentation"]), None
         instances.append({"gt_classes": torch.tensor(classes, dtype=torch.int64), "gt_ids": torch.tensor(ids, dtype=torch.int64),
                           "gt_rle": rles, "image_size": (p.nh, p.nw)})
+        if polygons:
+            instances[-1]["gt_poly"] = polys
     entry = {"image": list(frames), "augment": list(plan), "instances": instances}
     if layout != "chw":
         entry["image_layout"] = layout

@@ -30,6 +30,7 @@ import numpy as np
 from .. import _lib
 from ..ops import ap_match as M
 from ..ops import video_iou as V
+from ..ops.poly_rle import polygons_to_runs
 from .ytvis_eval import AREA_LABELS, STAT_NAMES, _default_device, summarize
 
 MATCHING = ("device", "vectorised", "host")
@@ -75,7 +76,11 @@ class COCOEval:
     summarize.
 
     gt: the annotation JSON (a dict or a path): `images`, `categories`, `annotations` with `bbox` (xywh), `area`,
-    `iscrowd` and, for "segm", `segmentation` as an RLE dict (compressed or not); polygons raise ValueError.
+    `iscrowd` and, for "segm", `segmentation` as an RLE dict (compressed or not).  polygons: False (the default) = a
+    polygon segmentation raises ValueError; True = a list segmentation (polygons or boxes, as frPyObjects takes them) is
+    rasterised at its image's `height` x `width` by `ops.poly_rle.polygons_to_runs`, on the evaluator's device (the
+    kernel) or on the host, and joins the RLE ground truth in one table.  `area` stays what the annotation states (COCO's
+    polygon areas differ from pixel counts, and COCOeval uses the stated one); "bbox" ignores the segmentation.
     iou_type: "bbox" or "segm".  device: a CUDA device for the kernels; None = CUDA when this process has one and the
     library is built; "cpu" = numpy and `match_host`.  matching: "device" / "vectorised" / "host" overrides the route of
     the matching alone.  iou_thrs, rec_thrs, max_dets, area_rng: COCOeval's Params (0.5 : 0.05 : 0.95, 0 : 0.01 : 1,
@@ -83,7 +88,7 @@ class COCOEval:
     """
 
     def __init__(self, gt, iou_type, device=None, iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100), area_rng=None,
-                 matching=None):
+                 matching=None, polygons=False):
         if isinstance(gt, (str, os.PathLike)):
             with open(gt) as f:
                 gt = json.load(f)
@@ -92,6 +97,7 @@ class COCOEval:
         if iou_type not in ("bbox", "segm"):
             raise ValueError(f"COCOEval: iou_type {iou_type!r} (bbox or segm; keypoints are out of scope)")
         self.gt, self.iou_type = gt, iou_type
+        self.polygons = bool(polygons)
         self.device = _default_device() if device is None else (None if str(device) == "cpu" else device)
         if matching is None:
             matching = "device" if self.device is not None else "host" if device is not None else "vectorised"
@@ -114,7 +120,9 @@ class COCOEval:
         for ann in gt.get("annotations") or []:
             seg = ann.get("segmentation")
             if isinstance(seg, list) and seg:
-                raise ValueError(f"COCOEval: annotation {ann.get('id')} is a polygon; only RLE ground truth is supported")
+                if not self.polygons:
+                    raise ValueError(f"COCOEval: annotation {ann.get('id')} is a polygon; only RLE ground truth is supported")
+                continue
             if iou_type == "segm" and not isinstance(seg, dict):
                 raise ValueError(f"COCOEval: annotation {ann.get('id')} has no RLE segmentation")
         self.records = []
@@ -196,7 +204,15 @@ class COCOEval:
         masks += [(f"annotation {a['id']!r} (image {a['image_id']!r})", self.images[a["image_id"]], a["segmentation"])
                   for a in g["ann"]]
         counts, counts_sizes, counts_at, strings, string_sizes, string_at, labels = [], [], [], [], [], [], []
+        polys, poly_sizes, poly_at = [], [], []
         for m, (label, image, seg) in enumerate(masks):
+            if self.polygons and m >= len(d["rec"]) and isinstance(seg, list) and seg:
+                if "height" not in image or "width" not in image:
+                    raise ValueError(f"COCOEval: {label} is a polygon and its image states no height / width")
+                polys.append(seg)
+                poly_sizes.append((int(image["height"]), int(image["width"])))
+                poly_at.append(m)
+                continue
             if not isinstance(seg, dict):
                 raise ValueError(f"COCOEval: {label} has no RLE segmentation")
             size = self._size_of(seg, image, label)
@@ -217,9 +233,16 @@ class COCOEval:
         if self.device is not None:
             t_counts = t_counts.to(t_strings.rows.device)
         tables = V.concat_tables(t_counts, t_strings)
+        if polys:
+            try:
+                t_polys = polygons_to_runs(polys, poly_sizes, device=self.device)
+            except ValueError as e:
+                raise ValueError(f"COCOEval: malformed polygon ground truth ({masks[poly_at[0]][0]} is object 0): {e}") from None
+            tables = V.concat_tables(tables, t_polys)
         row_of = np.zeros(len(masks), dtype=np.int32)        # one frame per track: track m's mask is row_of[m]
         row_of[counts_at] = np.arange(len(counts), dtype=np.int32)
         row_of[string_at] = len(counts) + np.arange(len(strings), dtype=np.int32)
+        row_of[poly_at] = len(counts) + len(strings) + np.arange(len(polys), dtype=np.int32)
         tracks = np.stack((np.arange(len(masks)), np.ones(len(masks))), 1).astype(np.int32).reshape(-1, 2)
         di, gi = self._pairs(table)
         pairs = np.stack((di, len(d["rec"]) + gi), 1).astype(np.int32).reshape(-1, 2)

@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import _lib
 from ..ops import video_iou as V
+from ..ops.poly_rle import polygons_to_runs
 
 STAT_NAMES = ("AP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
 AREA_LABELS = ("all", "small", "medium", "large")
@@ -43,7 +44,10 @@ class YTVISEval:
     """`YTVISEval(gt).add(records)`, then `.evaluate()` -> the numbers of YTVOSeval.evaluate / accumulate / summarize.
 
     gt: the annotation JSON (a dict or a path): `videos`, `categories`, `annotations` with per-frame `segmentations`
-    (uncompressed RLE, compressed RLE or None), `areas` and `iscrowd`.  Polygon ground truth raises ValueError.
+    (uncompressed RLE, compressed RLE or None), `areas` and `iscrowd`.  polygons: False (the default) = polygon ground
+    truth raises ValueError; True = a frame's list segmentation (polygons or boxes, as frPyObjects takes them) is rasterised
+    at the video's `height` x `width` by `ops.poly_rle.polygons_to_runs`, on the evaluator's device (the kernel) or on the
+    host, and joins the RLE ground truth in one table; `areas` stay what the annotation states.
     device: a CUDA device for the kernels; None = CUDA when this process has one and the library is built, else the
     numpy path; "cpu" = the numpy path.  iou_thrs, rec_thrs, max_dets, area_rng: the reference's Params (defaults: 0.5 :
     0.05 : 0.95, 0 : 0.01 : 1, [1, 10, 100], all / small / medium / large at 128^2 and 256^2).
@@ -52,13 +56,14 @@ class YTVISEval:
     """
 
     def __init__(self, gt, device=None, iou_thrs=None, rec_thrs=None, max_dets=(1, 10, 100), area_rng=None,
-                 device_matching=False):
+                 device_matching=False, polygons=False):
         if isinstance(gt, (str, os.PathLike)):
             with open(gt) as f:
                 gt = json.load(f)
         if not isinstance(gt, dict):
             raise ValueError(f"YTVISEval: annotation format {type(gt)} not supported")
         self.gt = gt
+        self.polygons = bool(polygons)
         self.device = _default_device() if device is None else (None if str(device) == "cpu" else device)
         self.iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True) if iou_thrs is None \
             else np.asarray(iou_thrs, dtype=np.float64)
@@ -75,7 +80,7 @@ class YTVISEval:
         self.cat_ids = [c.item() for c in np.unique(list(self.categories))] if self.categories else []
         for ann in gt.get("annotations") or []:
             for f, seg in enumerate(ann["segmentations"]):
-                if isinstance(seg, list) and seg:
+                if isinstance(seg, list) and seg and not self.polygons:
                     raise ValueError(f"YTVISEval: annotation {ann.get('id')} frame {f} is a polygon; only RLE ground "
                                      "truth is supported")
         self.records = []
@@ -103,17 +108,27 @@ class YTVISEval:
         return size
 
     def _tables(self, tracks):
-        """tracks: [(label, video, segmentations)] -> (tables, frame_mask, track rows); one mask per present frame"""
+        """tracks: [(label, video, segmentations[, is ground truth])] -> (tables, frame_mask, track rows); one mask per
+        present frame"""
+        polys, poly_sizes, poly_slots = [], [], []
         counts, counts_sizes, counts_slots = [], [], []
         strings, string_sizes, string_slots, labels = [], [], [], []
         frame_mask, rows = [], []
-        for label, video, segs in tracks:
+        for label, video, segs, *is_gt in tracks:
             rows.append((len(frame_mask), len(segs)))
             for f, seg in enumerate(segs):
                 if not seg:
                     frame_mask.append(-1)
                     continue
                 where = f"{label} frame {f}"
+                if self.polygons and is_gt and is_gt[0] and isinstance(seg, list):
+                    if "height" not in video or "width" not in video:
+                        raise ValueError(f"YTVISEval: {where} is a polygon and its video states no height / width")
+                    polys.append(seg)
+                    poly_sizes.append((int(video["height"]), int(video["width"])))
+                    poly_slots.append(len(frame_mask))
+                    frame_mask.append(0)
+                    continue
                 size = self._size_of(seg, video, where)
                 c = seg["counts"]
                 if isinstance(c, (str, bytes)):
@@ -137,6 +152,13 @@ class YTVISEval:
         tables = V.concat_tables(t_counts, t_strings)
         frame_mask[counts_slots] = np.arange(len(counts), dtype=np.int32)
         frame_mask[string_slots] = len(counts) + np.arange(len(strings), dtype=np.int32)
+        if polys:
+            try:
+                t_polys = polygons_to_runs(polys, poly_sizes, device=self.device)
+            except ValueError as e:
+                raise ValueError(f"YTVISEval: malformed polygon ground truth: {e}") from None
+            tables = V.concat_tables(tables, t_polys)
+            frame_mask[poly_slots] = len(counts) + len(strings) + np.arange(len(polys), dtype=np.int32)
         return tables, frame_mask, np.array(rows, dtype=np.int32).reshape(-1, 2)
 
     # ---- YTVOSeval.evaluate ---------------------------------------------------------------------------------------
@@ -176,7 +198,7 @@ class YTVISEval:
                 tracks.append((f"record {d['id'] - 1} (video {key[0]!r})", video, d["rec"]["segmentations"]))
             for g in gts.get(key, []):
                 g["track"] = len(tracks)
-                tracks.append((f"annotation {g['id']!r} (video {key[0]!r})", video, g["ann"]["segmentations"]))
+                tracks.append((f"annotation {g['id']!r} (video {key[0]!r})", video, g["ann"]["segmentations"], True))
             pairs += [(d["track"], g["track"]) for d in dts.get(key, []) for g in gts.get(key, [])]
         t0 = time.perf_counter()
         tables, frame_mask, track_rows = self._tables(tracks)

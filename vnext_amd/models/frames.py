@@ -23,7 +23,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import augment, ingest, resize
+from ..ops import augment, ingest, poly_rle, resize
 from ..ops.fused_norm import step_scope
 from ..ops.ingest import sine_position
 
@@ -118,7 +118,14 @@ def host_augmented(batched_inputs):
         sizes = [resize.frame_size(f, layout) for f in clip["image"]]
         instances = []
         for i, fr in enumerate(clip["instances"]):
-            masks, boxes, flags = augment.reference_augment_masks([(i, c) for c in fr["gt_rle"]], sizes, plan)
+            polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
+            # a polygon slot goes in as the empty mask and is replaced by its own host route
+            masks, boxes, flags = augment.reference_augment_masks(
+                [(i, c if q is None else [sizes[i][0] * sizes[i][1]]) for c, q in zip(fr["gt_rle"], polys)], sizes, plan)
+            for s, q in enumerate(polys):
+                if q is not None:
+                    masks[s] = augment.reference_polygon_mask(q, plan[i])
+                    boxes[s], flags[s] = augment.mask_box(masks[s])
             nh, nw = fr["image_size"]
             gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, nh, nw, dtype=torch.bool)
             keep = torch.from_numpy(flags)
@@ -136,23 +143,39 @@ def augment_step(model, batched_inputs):
         (copies) filled with gt_masks, gt_boxes and gt_ids from ONE `augment_masks` call for the whole step -- views of its
         outputs; gt_ids = nonempty ? id : -1 (`filter_empty_instances`: with boxes taken from masks its box test and its
         mask test are the same test).  The clips' "image" entries stay the source frames: nothing reads their pixels again;
-      beyond it (`augment.applies`): `host_augmented` inputs, pre None -- the path without the switch."""
+      beyond it (`augment.applies`): `host_augmented` inputs, pre None -- the path without the switch.
+    Frames staged with `stage_clip(polygons=True)` carry gt_poly: those slots are transformed on the host
+    (`augment.transform_polygons`), rasterised at the target size by ONE `polygons_to_runs` call and read by the same
+    `augment_masks` call through pseudo-frame rows; nothing is read back from the device."""
     if not (getattr(model, "device_augment", False) and model.training
             and all("augment" in clip for clip in batched_inputs)):
         return batched_inputs, None
     layout = batched_inputs[0].get("image_layout", "chw")
     frames = [f for clip in batched_inputs for f in clip["image"]]
     plan = [p for clip in batched_inputs for p in clip["augment"]]
-    if any(clip.get("image_layout", "chw") != layout for clip in batched_inputs) or \
-            not augment.applies(frames, plan, model.device, layout):
-        return host_augmented(batched_inputs), None
-    listed, ids, f = [], [], 0
+    # polygon slots: the coordinates through the frame's plan on the host, ONE rasterisation at the targets on the device
+    listed, ids, objects, sizes, f = [], [], [], [], 0
     for clip in batched_inputs:
         for fr in clip["instances"]:
-            listed += [(f, c) for c in fr["gt_rle"]]
+            polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
+            for c, q in zip(fr["gt_rle"], polys):
+                if q is not None:
+                    c = len(objects)                           # replaced by the object's run slot below
+                    objects.append(augment.transform_polygons(q, plan[f]))
+                    sizes.append((plan[f].nh, plan[f].nw))
+                listed.append((f, c, q is not None))
             ids += fr["gt_ids"].tolist()
             f += 1
-    staged = augment.stage_step(frames, plan, listed, model.device, layout, ids)
+    planned = poly_rle.plan_objects(objects, sizes) if objects else None
+    if any(clip.get("image_layout", "chw") != layout for clip in batched_inputs) or \
+            not augment.applies(frames, plan, model.device, layout, polygons=planned):
+        return host_augmented(batched_inputs), None
+    poly_ends = None
+    if objects:
+        tables = poly_rle.polygons_to_runs(objects, sizes, device=model.device, check=False, planned=planned)
+        poly_ends = tables.ends
+        listed = [(f, augment.PolyRuns(*tables.slot_rows[c]) if is_poly else c, is_poly) for f, c, is_poly in listed]
+    staged = augment.stage_step(frames, plan, [(f, c) for f, c, _ in listed], model.device, layout, ids, poly_ends=poly_ends)
     pre = augment_staged(staged, model._pixel_stats, model.detr.detr.backbone)
     masks, boxes, nonempty = augment.augment_masks(staged)
     gt_ids = torch.where(nonempty, staged.ids, -1).to(torch.int64)

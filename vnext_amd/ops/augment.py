@@ -22,6 +22,12 @@ gives each frame's bool [n_inst, nh, nw] as a view.
 
 The bilinear range is the resize kernel's (ksize <= 17 on both axes, of the WINDOW to the target); `applies` says so and the
 caller takes the host route beyond.  `CALLS` counts the launches made here.
+
+Polygon ground truth: `transform_polygons(segmentation, p)` applies a frame's plan to the coordinates on
+the host (crop, resize, flip, in the reference's order and with its expressions), `ops.poly_rle.polygons_to_runs` rasterises
+them at the TARGET size on the device, and `stage_step` takes such a mask as a `PolyRuns(offset, size)` -- its slot of the
+device-resident run ends -- and gives it a pseudo-frame row (the target as its own source: the full window, no flip, identity
+nearest tables), so ONE `augment_masks` call makes gt_masks, boxes and `nonempty` of RLE and polygon masks alike.
 """
 from __future__ import annotations
 
@@ -33,7 +39,7 @@ import torch
 
 from .. import _lib
 from ..utils.ytvis_json import counts_to_string, rle_decode
-from . import ingest, resize
+from . import ingest, poly_rle, resize
 
 CALLS = {"augment_frames": 0, "augment_masks": 0}      # calls through the C ABI (tests: the ops ran / did not run)
 SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS = 8, 8, 4
@@ -47,6 +53,12 @@ class FramePlan(NamedTuple):
     nh: int
     nw: int
     flip: bool
+
+
+class PolyRuns(NamedTuple):
+    """a mask whose run ends are on the device already (a slot of `polygons_to_runs`' ends, at the frame's TARGET size)"""
+    offset: int
+    size: int
 
 
 def full_plan(h: int, w: int, nh: int, nw: int, flip: bool = False) -> FramePlan:
@@ -95,6 +107,31 @@ def reference_augment_frames(frames, plan, layout: str = "chw"):
     return out
 
 
+def transform_polygons(segmentation, p: FramePlan):
+    """One annotation's polygons (or boxes, as their 4-vertex polygons) through the frame's plan, in float64 and in the
+    reference's order: crop `x -= x0, y -= y0`; resize `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`
+    (ResizeTransform.apply_coords); flip `x = nw - x` (HFlipTransform.apply_coords).  The shifted polygon is NOT clipped to
+    the window (the reference clips with shapely first): the rasteriser drops columns outside the canvas and clamps rows.
+    -> a list of flat float64 polygons for a canvas of nh x nw."""
+    out = []
+    for poly in poly_rle.object_polygons(segmentation):
+        xy = poly.copy()
+        xy[0::2] -= p.x0
+        xy[1::2] -= p.y0
+        xy[0::2] = xy[0::2] * (p.nw * 1.0 / p.cw)
+        xy[1::2] = xy[1::2] * (p.nh * 1.0 / p.ch)
+        if p.flip:
+            xy[0::2] = p.nw - xy[0::2]
+        out.append(xy)
+    return out
+
+
+def reference_polygon_mask(segmentation, p: FramePlan):
+    """the host route of one polygon mask: `transform_polygons`, `object_counts_host` at (nh, nw) -> bool [nh, nw]"""
+    counts = poly_rle.object_counts_host(transform_polygons(segmentation, p), p.nh, p.nw)
+    return np.ascontiguousarray(poly_rle.counts_to_mask(counts, p.nh, p.nw))
+
+
 def mask_box(m):
     """`BitMasks.get_bounding_boxes` of one bool [h, w] array -> ([x0, y0, x1 + 1, y1 + 1] float32, nonempty)"""
     xs, ys = np.flatnonzero(m.any(0)), np.flatnonzero(m.any(1))
@@ -130,12 +167,17 @@ def supported(p: FramePlan) -> bool:
     return resize.supported(p.ch, p.cw, p.nh, p.nw)
 
 
-def applies(frames, plan, device, layout: str = "chw") -> bool:
+def applies(frames, plan, device, layout: str = "chw", polygons=None) -> bool:
     """All frames are uint8 CPU tensors of `layout`, every window lies inside its frame and every (window, target) pair is in
-    the kernel's range"""
+    the kernel's range; polygons: (objects, sizes) of the step's transformed polygon masks, or what
+    `poly_rle.plan_objects` made of them -- every one inside the caps of vnx_poly_rle"""
     ah, aw = resize._hw_axes(layout)
     if not frames or len(frames) != len(plan):
         return False
+    if polygons is not None:
+        fits = polygons[2] if len(polygons) == 3 else poly_rle.plan_objects(*polygons)[2]
+        if not bool(np.all(fits)):
+            return False
     for f, p in zip(frames, plan):
         if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[3 - ah - aw] == 3 and not f.is_cuda):
             return False
@@ -183,6 +225,8 @@ class Staged(NamedTuple):
     layout: str
     mask_bytes: int
     groups: tuple               # per frame (first mask, masks, nh, nw): the masks of a frame are consecutive
+    mask_src: object = None     # with polygon masks: src_table / dst_table of the frames AND the pseudo-frames (the rows
+    mask_dst: object = None     # mask_rows index); src_table and dst_table above are their first n rows
 
     def mask_views(self, masks):
         """the flat output of `augment_masks` -> per frame bool [n_inst, nh, nw] (views)"""
@@ -193,18 +237,29 @@ class Staged(NamedTuple):
         return out
 
 
-def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None) -> Staged:
+def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_ends=None) -> Staged:
     """frames: uint8 CPU tensors of `layout`; plan: a FramePlan per frame; masks: [(frame index, COCO counts)] with the masks
-    of a frame CONSECUTIVE and the frames ascending; ids: the masks' instance ids (default 0).  See the module docstring."""
+    of a frame CONSECUTIVE and the frames ascending; ids: the masks' instance ids (default 0).  A mask may be a
+    `PolyRuns(offset, size)` instead of counts: its run ends are words [offset, offset + size) of `poly_ends` (int32 on
+    `device`, at the frame's target size).  See the module docstring."""
     device = torch.device(device)
     n, m = len(frames), len(masks)
     sizes = [resize.frame_size(f, layout) for f in frames]
-    src, off = np.zeros((n, SRC_WORDS), dtype=np.int32), 0
+    pseudo = {}                              # frame -> the row of its pseudo-frame
+    for f, counts in masks:
+        if isinstance(counts, PolyRuns):
+            pseudo.setdefault(f, n + len(pseudo))
+    assert not pseudo or (poly_ends is not None and poly_ends.is_cuda and device.type == "cuda"), \
+        "stage_step: polygon masks take device-resident run ends"
+    src, off = np.zeros((n + len(pseudo), SRC_WORDS), dtype=np.int32), 0
     for i, ((h, w), p) in enumerate(zip(sizes, plan)):
         src[i] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
         off += ingest._align16(3 * h * w)
-    dst = np.array([(0, p.nh, p.nw) for p in plan], dtype=np.int32).reshape(n, 3)
-    words = _coeff_words(plan)
+    all_plan = list(plan) + [full_plan(plan[f].nh, plan[f].nw, plan[f].nh, plan[f].nw) for f in pseudo]
+    for f, row in pseudo.items():            # the target as its own source; the mask kernel reads no pixels
+        src[row] = (0, plan[f].nh, plan[f].nw, 0, 0, plan[f].nw, plan[f].nh, 0)
+    dst = np.array([(0, p.nh, p.nw) for p in all_plan], dtype=np.int32).reshape(len(all_plan), 3)
+    words = _coeff_words(all_plan)
     rows, ends, e_at, o_at = np.zeros((m, MASK_ROW_WORDS), dtype=np.int32), [], 0, 0
     groups, last = [[0, 0, p.nh, p.nw] for p in plan], -1
     for i, (f, counts) in enumerate(masks):
@@ -213,6 +268,10 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None) -> St
             groups[f][0] = i
         last = f
         groups[f][1] += 1
+        if isinstance(counts, PolyRuns):
+            rows[i] = (counts.offset, counts.size, pseudo[f], o_at)
+            o_at += plan[f].nh * plan[f].nw
+            continue
         e = np.cumsum(np.asarray(counts, dtype=np.int64))
         assert e.size >= 1 and e[-1] <= 0x7fffffff
         rows[i] = (e_at, e.size, f, o_at)
@@ -223,6 +282,8 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None) -> St
         if g[1] == 0:
             g[0] = 0
     ends = np.concatenate(ends) if ends else np.zeros(1, dtype=np.int32)
+    if pseudo:                               # the device-resident ends follow the staged ones
+        rows[[i for i, (_, c) in enumerate(masks) if isinstance(c, PolyRuns)], 0] += ends.size
     idv = np.zeros(m, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(m)
     small = [src.reshape(-1), dst.reshape(-1), words, ends, rows.reshape(-1), idv]
     cuts = np.cumsum([0] + [s.size for s in small])
@@ -235,9 +296,11 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None) -> St
     whole = buf.to(device, non_blocking=True)
     ints = whole[:4 * int(cuts[-1])].view(torch.int32)
     part = [ints[int(a):int(b)] for a, b in zip(cuts[:-1], cuts[1:])]
-    return Staged(whole[head:], part[0].view(n, SRC_WORDS), part[1].view(n, 3), part[2], part[3],
-                  part[4].view(m, MASK_ROW_WORDS), part[5], padded_size(plan), layout, int(o_at),
-                  tuple(tuple(g) for g in groups))
+    src_d, dst_d = part[0].view(-1, SRC_WORDS), part[1].view(-1, 3)
+    ends_d = torch.cat((part[3], poly_ends.to(torch.int32))) if pseudo else part[3]
+    return Staged(whole[head:], src_d[:n], dst_d[:n], part[2], ends_d, part[4].view(m, MASK_ROW_WORDS), part[5],
+                  padded_size(plan), layout, int(o_at), tuple(tuple(g) for g in groups),
+                  src_d if pseudo else None, dst_d if pseudo else None)
 
 
 def _plan_of(staged: Staged):
@@ -286,10 +349,12 @@ def augment_masks(staged: Staged):
         return masks, boxes, nonempty
     lib = _lib.lib()
     work = torch.empty(int(lib.vnx_augment_masks_workspace(m, H, W)), dtype=torch.uint8, device=dev)
+    src = staged.src_table if staged.mask_src is None else staged.mask_src
+    dst = staged.dst_table if staged.mask_dst is None else staged.mask_dst
     with torch.cuda.device(dev):
         _lib.check(lib.vnx_augment_masks(
-            staged.ends.data_ptr(), staged.ends.numel(), staged.mask_rows.data_ptr(), m, staged.src_table.data_ptr(),
-            staged.dst_table.data_ptr(), staged.coeffs.data_ptr(), staged.coeffs.numel(), staged.src_table.shape[0], H, W,
+            staged.ends.data_ptr(), staged.ends.numel(), staged.mask_rows.data_ptr(), m, src.data_ptr(),
+            dst.data_ptr(), staged.coeffs.data_ptr(), staged.coeffs.numel(), src.shape[0], H, W,
             masks.data_ptr(), masks.numel(), boxes.data_ptr(), nonempty.data_ptr(), work.data_ptr(), work.numel(),
             _lib.current_stream(staged.ends)))
     CALLS["augment_masks"] += 1
