@@ -1023,6 +1023,32 @@ int vnx_augment_masks(const void* ends, size_t n_ends, const void* mask_rows, in
                       void* hip_stream);
 
 /*
+ * The first resample of a two-resample augmentation chain (augment.hip; flip -> resize -> crop -> resize, the COCO
+ * pre-training mapper's): a frame resized to (h1, w1) as Pillow's Image.resize(..., BILINEAR) resizes 8-bit images, of which
+ * only a crop window is computed, stored as BYTES into the pixel buffer itself, where vnx_augment_frames reads it as a source
+ * frame.  ADDITIVE: one symbol, no existing signature changed, so VNX_ABI_VERSION stays 17.  The same device code as
+ * vnx_resize_ingest_frames and vnx_augment_frames.
+ *
+ * pixels: uint8 device buffer of pixel_bytes bytes, 4-byte aligned, read AND written.  interleaved: as above, for the source
+ * frames and for the stored windows alike.  win_table: int32 device [batch][16] = {byte offset of the source frame, h, w, h1,
+ * w1, x0, y0, cw, ch, byte offset of the window's slot, then {bounds offset, weights offset, ksize} of (w -> w1) and of
+ * (h -> h1)}: the window of cw x ch pixels at (x0, y0) inside the RESIZED h1 x w1 image; the coefficient tables are those of
+ * vnx_resize_ingest_frames for the whole axes (w1 and h1 rows), offsets in words from the start of coeffs, ksize 0 where
+ * the axis keeps its size.  The slot takes 3 * ch * cw bytes at any byte offset: CHW three planes of ch x cw, HWC ch x cw
+ * pixels of 3 bytes, row pitch cw.  height, width: multiples of 32, at least every ch and cw (they size the launch).
+ *
+ * A row whose window leaves (h1, w1) or height x width, whose source bytes or slot leave pixels, whose slot overlaps its own
+ * source frame, or whose tables are malformed as for vnx_resize_ingest_frames writes NOTHING: its slot keeps its bytes.  No
+ * read leaves pixels or coeffs and no write leaves the row's slot, whatever the table holds; slots of different rows must
+ * not overlap each other or any source frame of the launch (the caller lays them out).  Everything is read from device
+ * memory by the kernel: a captured launch replays on other pixels, sizes and windows of the same batch, height and width.
+ * One launch; 16-byte stores wherever 16 aligned bytes lie inside one tile row of a slot, byte stores at the ends; no
+ * atomics, no workspace, no allocation, no synchronisation: capturable.  batch == 0: VNX_OK, no launch.
+ */
+int vnx_resize_window_bytes(void* pixels, size_t pixel_bytes, const void* win_table, const void* coeffs, size_t coeff_words,
+                            int batch, int height, int width, int interleaved, void* hip_stream);
+
+/*
  * Clipped AdamW step (optim.hip): the full-model gradient norm, clip_grad_norm_'s coefficient and the decoupled AdamW
  * update of EVERY parameter tensor of a model in three launches, whatever the number of tensors.  ADDITIVE: two symbols, no
  * existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.

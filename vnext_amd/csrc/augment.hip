@@ -7,6 +7,13 @@
 // coefficient tables are those of (cw -> nw) and (ch -> nh); the row pitch stays w.  A row with the full window and no flip
 // gives what vnx_resize_ingest_frames gives, bit for bit.
 //
+// vnx_resize_window_bytes is the third instantiation: the first resample of the COCO pre-training
+// chain flip -> resize -> crop -> resize.  It resizes a frame to (h1, w1) but computes only the crop window of the result
+// and stores it as bytes, in the frame's layout, into a slot of the SAME pixel buffer; vnx_augment_frames then reads that
+// slot as a source frame.  A row is {src byte offset, h, w, h1, w1, x0, y0, cw, ch, dst byte offset, bounds / weights /
+// ksize of (w -> w1), of (h -> h1)}.  A malformed row (the window outside (h1, w1) or the padded size, either byte range
+// outside the buffer or the two overlapping, ksize beyond the limit) leaves its slot untouched.
+//
 // vnx_augment_masks.  A ground-truth mask arrives as the END POSITIONS of its COCO runs (the cumulative sums of the counts;
 // column-major, p = x * h + y; runs of zeros and ones alternate, zeros first).  The value of source pixel p is the parity of
 // the number of ends <= p -- an upper bound by binary search; zero-length runs need no special case.  Output pixel (y, x) of
@@ -198,6 +205,46 @@ __global__ __launch_bounds__(kWave) void augment_boxes_kernel(const int32_t* __r
   }
 }
 
+// vnx_resize_window_bytes: what it checks before it launches, and the launch (the kBytes instantiation)
+inline int launch_resize_window_bytes(const char* fn, void* pixels, size_t pixel_bytes, const void* win_table,
+                                      const void* coeffs, size_t coeff_words, int batch, int height, int width,
+                                      int interleaved, void* hip_stream) {
+  if (batch < 0 || height < 32 || width < 32 || height % 32 != 0 || width % 32 != 0) {
+    set_error("%s: bad sizes (batch %d, padded %d x %d: multiples of 32)", fn, batch, height, width);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (batch == 0) return VNX_OK;
+  if (!pixels || !win_table || !coeffs) {
+    set_error("%s: null pointer argument", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (((reinterpret_cast<uintptr_t>(pixels) | reinterpret_cast<uintptr_t>(win_table) | reinterpret_cast<uintptr_t>(coeffs)) & 3) != 0) {
+    set_error("%s: pixels, the table and coeffs must be 4-byte aligned", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  if (pixel_bytes > size_t(0x7fffffff) || coeff_words > size_t(0x7fffffff)) {      // the table's offsets are int32
+    set_error("%s: %zu bytes of pixels, %zu words of coefficients: the table addresses 2^31 - 1 at most", fn, pixel_bytes,
+              coeff_words);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  const long long blocks = (long long)batch * (height / kTile) * (width / kTile);
+  if (blocks > 0x7fffffffll) {
+    set_error("%s: %d frames of %d x %d are more than one launch addresses", fn, batch, height, width);
+    return VNX_ERR_UNSUPPORTED;
+  }
+  ResizeArgs a{};
+  a.pixels = (const unsigned char*)pixels;
+  a.pixel_bytes = (long long)pixel_bytes;
+  a.src_table = (const int32_t*)win_table;
+  a.coeffs = (const int32_t*)coeffs;
+  a.coeff_words = (long long)coeff_words;
+  a.mask = (unsigned char*)pixels;      // the stores go into the pixel buffer
+  a.B = batch; a.H = height; a.W = width; a.interleaved = interleaved != 0;
+  hipLaunchKernelGGL((resize_ingest_kernel<false, true>), dim3(unsigned(blocks)), dim3(kResizeThreads), 0,
+                     (hipStream_t)hip_stream, a);
+  return check_launch(fn);
+}
+
 }  // namespace
 }  // namespace vnx
 
@@ -210,6 +257,13 @@ extern "C" int vnx_augment_frames(const void* pixels, size_t pixel_bytes, const 
   const float mean[3] = {mean0, mean1, mean2}, std[3] = {std0, std1, std2};
   return launch_resize_ingest<true>("vnx_augment_frames", pixels, pixel_bytes, src_table, dst_table, coeffs, coeff_words,
                                     batch, height, width, mean, std, channels_last, interleaved, x, mask, hip_stream);
+}
+
+extern "C" int vnx_resize_window_bytes(void* pixels, size_t pixel_bytes, const void* win_table, const void* coeffs,
+                                       size_t coeff_words, int batch, int height, int width, int interleaved,
+                                       void* hip_stream) {
+  return launch_resize_window_bytes("vnx_resize_window_bytes", pixels, pixel_bytes, win_table, coeffs, coeff_words, batch,
+                                    height, width, interleaved, hip_stream);
 }
 
 extern "C" size_t vnx_augment_masks_workspace(int n_masks, int height, int width) {

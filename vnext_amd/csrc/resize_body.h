@@ -1,13 +1,20 @@
-// resize_body.h -- the one copy of the resize + ingest kernel (DESIGN sections 21 and 24), instantiated twice:
+// resize_body.h -- the one copy of the resize + ingest kernel (DESIGN sections 21, 24 and 30), instantiated three times:
 //   resize.hip   kWindow = false  vnx_resize_ingest_frames: the whole frame, never flipped, a source row of 3 words and a
 //                                 coefficient row of 6.  The window and the flip are compile-time constants there: the
 //                                 instantiation holds none of their arithmetic.
 //   augment.hip  kWindow = true   vnx_augment_frames: a crop window {x0, y0, cw, ch} inside the frame and a horizontal flip
 //                                 flag, a source row of 8 words and a coefficient row of 8.
+//   augment.hip  kBytes = true    vnx_resize_window_bytes: the WHOLE frame resized to (h1, w1), of which only the window
+//                                 {x0, y0, cw, ch} of the RESULT is computed and stored -- as bytes, in the frame's own
+//                                 layout, into the pixel buffer itself.  One row of 16 words per frame holds the geometry
+//                                 and the two coefficient triples.  No normalisation, no padding mask, never flipped.
 // The arithmetic, the tiling and the LDS layout are described at the head of resize.hip.  What the window changes: the
 // coefficient tables are those of (cw -> nw) and (ch -> nh) and count from the window's origin, while the row pitch stays the
 // frame's w and the CHW plane stride h * w.  What the flip changes: output column x takes resized column nw - 1 - x, an index
 // where a tile's 32 horizontal bounds and weight rows are staged; the bytes written to LDS and phase V are the same code.
+// What kBytes changes: the coefficient tables are those of (w -> w1) and (h -> h1) and output pixel (y, x) of the window
+// takes their rows y0 + y and x0 + x -- again an index where the bounds and weights are staged.  Phase V's bytes go to a
+// tile of LDS instead of through the normalisation, and from there to memory in 16-byte pieces (see the stores).
 #pragma once
 
 #include "vnx_common.h"
@@ -23,6 +30,7 @@ constexpr int kMaxKsize = 17;              // VNX_RESIZE_MAX_KSIZE
 constexpr int kMaxRows = 272;              // staged source rows of a tile: (kTile + 1) * 8 + 1 at the limit, rounded up
 constexpr int kAugSrcWords = 8;            // {byte offset, h, w, x0, y0, cw, ch, flip}
 constexpr int kAugCoeffWords = 8;          // the two bilinear triples, then the offsets of the two nearest tables (augment.hip)
+constexpr int kWinWords = 16;              // {src byte offset, h, w, h1, w1, x0, y0, cw, ch, dst byte offset, the two triples}
 
 typedef uint32_t rsz_u4 __attribute__((ext_vector_type(4)));
 
@@ -34,7 +42,7 @@ struct ResizeArgs {
   const int32_t* coeffs;
   long long coeff_words;
   float* x;
-  unsigned char* mask;
+  unsigned char* mask;                     // (kBytes: the pixel buffer again, writable: the windows are stored into it)
   int B, H, W, channels_last, interleaved;
   float mean[3], std[3];
 };
@@ -46,6 +54,10 @@ struct ResizeGeom {
   int x0, y0, cw, ch, flip;   // the window and the flip (kWindow false: 0, 0, w, h, 0)
   AxisTab hor, ver;
 };
+
+// kBytes only (beside ResizeGeom, whose nh x nw is then the window's size): the window's origin inside the resized h1 x w1
+// image, and the byte offset of its slot inside the pixel buffer
+struct WindowOut { int ox, oy, dst; };
 
 // one axis of a frame's coefficient row: inside the buffer for n_out rows of bounds and weights, or a skipped pass
 __device__ __forceinline__ bool axis_ok(const AxisTab t, int n_in, int n_out, long long words) {
@@ -82,6 +94,33 @@ __device__ __forceinline__ ResizeGeom resize_geom(const int32_t* __restrict__ sr
   return g;
 }
 
+// frame `b` of vnx_resize_window_bytes as its row describes it, or the empty frame.  The source window is the whole frame;
+// the "target" nh x nw is the window ch x cw of the resized image, which must lie inside (h1, w1) and inside H x W; its
+// 3 * ch * cw bytes must lie inside the buffer and apart from the frame's own source bytes.
+__device__ __forceinline__ ResizeGeom window_geom(const int32_t* __restrict__ win_table, long long coeff_words,
+                                                  long long pixel_bytes, int H, int W, int b, WindowOut& o) {
+  ResizeGeom g;
+  const int32_t* s = win_table + kWinWords * size_t(b);
+  g.off = s[0]; g.h = s[1]; g.w = s[2];
+  const int h1 = s[3], w1 = s[4];
+  o.ox = s[5]; o.oy = s[6]; g.nw = s[7]; g.nh = s[8]; o.dst = s[9];
+  g.x0 = 0; g.y0 = 0; g.cw = g.w; g.ch = g.h; g.flip = 0;
+  g.hor = AxisTab{s[10], s[11], s[12]};
+  g.ver = AxisTab{s[13], s[14], s[15]};
+  // pixel counts first (a product of two int32 fits 64 bits; three times one that is at most pixel_bytes < 2^31 does too)
+  const long long src_px = (long long)g.h * g.w, dst_px = (long long)g.nh * g.nw;
+  bool ok = g.off >= 0 && g.h >= 1 && g.w >= 1 && src_px <= pixel_bytes && h1 >= 1 && w1 >= 1 && g.nh >= 1 && g.nw >= 1 &&
+            g.nh <= H && g.nw <= W && o.ox >= 0 && o.oy >= 0 && g.nw <= w1 && g.nh <= h1 && o.ox <= w1 - g.nw &&
+            o.oy <= h1 - g.nh && o.dst >= 0 && dst_px <= pixel_bytes && axis_ok(g.hor, g.w, w1, coeff_words) &&
+            axis_ok(g.ver, g.h, h1, coeff_words);
+  if (ok) {
+    const long long src_end = g.off + 3 * src_px, dst_end = o.dst + 3 * dst_px;
+    ok = src_end <= pixel_bytes && dst_end <= pixel_bytes && (dst_end <= g.off || o.dst >= src_end);
+  }
+  if (!ok) g.nh = g.nw = 0;
+  return g;
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // byte `at` (inside the buffer) through the aligned word around it; `cur` / `word` remember the last word fetched
@@ -101,11 +140,18 @@ __device__ __forceinline__ uint32_t source_byte(const unsigned char* __restrict_
   return (word >> (8 * int(at & 3))) & 0xffu;
 }
 
-template <bool kWindow>
+template <bool kWindow, bool kBytes>
+__device__ __forceinline__ ResizeGeom frame_geom(const ResizeArgs& a, int b, WindowOut& wo) {
+  if constexpr (kBytes) return window_geom(a.src_table, a.coeff_words, a.pixel_bytes, a.H, a.W, b, wo);
+  else return resize_geom<kWindow>(a.src_table, a.dst_table, a.coeffs, a.coeff_words, a.pixel_bytes, a.H, a.W, b);
+}
+
+template <bool kWindow, bool kBytes = false>
 __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char rows[3][kMaxRows][kTile];
   __shared__ uint32_t kh[kTile][kMaxKsize], kv[kTile][kMaxKsize];
   __shared__ int bh[kTile][2], bv[kTile][2];      // {first source column, taps}; {first staged row, taps}
+  __shared__ __attribute__((aligned(16))) unsigned char obuf[kBytes ? 3 * kTile * kTile : 16];      // kBytes: the tile's bytes
 
   const int H = a.H, W = a.W, tid = threadIdx.x;
   const int tiles_x = W / kTile, tiles_y = H / kTile;
@@ -113,26 +159,29 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
   const int rest = blockIdx.x / tiles_x;
   const int ty = rest % tiles_y, b = rest / tiles_y;
   const int ox0 = tx * kTile, oy0 = ty * kTile;
-  const ResizeGeom g = resize_geom<kWindow>(a.src_table, a.dst_table, a.coeffs, a.coeff_words, a.pixel_bytes, H, W, b);   // workgroup-uniform
+  WindowOut wo{};
+  const ResizeGeom g = frame_geom<kWindow, kBytes>(a, b, wo);   // workgroup-uniform
   const bool live = oy0 < g.nh && ox0 < g.nw;              // the tile holds pixels of the frame
 
   if (live) {
     const int rows_out = min(kTile, g.nh - oy0), cols_out = min(kTile, g.nw - ox0);
+    // the resized row an output row takes: itself, or (kBytes) the row of the window's origin further down
+    auto resized_row = [&](int y) { return kBytes ? wo.oy + y : y; };
     // the window's rows this tile's output rows reach: [r0, r1)
     int r0, r1;
     if (g.ver.ksize == 0) {
-      r0 = oy0; r1 = oy0 + rows_out;                       // nh == ch
+      r0 = resized_row(oy0); r1 = r0 + rows_out;           // nh == ch
     } else {
       const int32_t* bnd = a.coeffs + g.ver.bounds;
-      const int last = oy0 + rows_out - 1;
-      r0 = clampi(bnd[2 * oy0], 0, g.ch);
+      const int last = resized_row(oy0 + rows_out - 1);
+      r0 = clampi(bnd[2 * resized_row(oy0)], 0, g.ch);
       r1 = clampi(clampi(bnd[2 * last], 0, g.ch) + clampi(bnd[2 * last + 1], 0, g.ver.ksize), r0, g.ch);
       if (r1 - r0 > kMaxRows) r1 = r0 + kMaxRows;
     }
     // ---- stage the tile's bounds and weights ----
     // the resized column an output column takes: itself, or with the flip its mirror (a tile at the frame's right edge then
     // holds the frame's FIRST resized columns)
-    auto resized_col = [&](int x) { return kWindow && g.flip ? g.nw - 1 - x : x; };
+    auto resized_col = [&](int x) { return kBytes ? wo.ox + x : (kWindow && g.flip ? g.nw - 1 - x : x); };
     if (tid < kTile) {
       int first = 0, cnt = 0;
       if (tid < cols_out) {
@@ -151,7 +200,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
       if (r < rows_out) {
         if (g.ver.ksize == 0) { first = r; cnt = 1; }
         else {
-          const int32_t* bnd = a.coeffs + g.ver.bounds + 2 * (oy0 + r);
+          const int32_t* bnd = a.coeffs + g.ver.bounds + 2 * resized_row(oy0 + r);
           const int y = clampi(bnd[0], r0, r1);
           first = y - r0;
           cnt = clampi(bnd[1], 0, min(g.ver.ksize, r1 - y));
@@ -165,7 +214,7 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
       const int r = j / kMaxKsize, t = j - r * kMaxKsize;
       const AxisTab tab = vert ? g.ver : g.hor;
       const bool have = r < (vert ? rows_out : cols_out) && t < tab.ksize;
-      const int idx = vert ? oy0 + r : resized_col(ox0 + r);      // (in range wherever `have` holds)
+      const int idx = vert ? resized_row(oy0 + r) : resized_col(ox0 + r);      // (in range wherever `have` holds)
       const uint32_t k = have ? uint32_t(a.coeffs[tab.kk + (long long)idx * tab.ksize + t]) : 0u;
       (vert ? kv : kh)[r][t] = k;
     }
@@ -230,10 +279,55 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
 #pragma unroll
           for (int j = 0; j < 4; ++j) bytes |= min(acc[j] >> 22, 255u) << (8 * j);
         }
+        if constexpr (kBytes) {      // the tile as it will lie in memory: planes of 32 x 32, or rows of 32 pixels of 3 bytes
+          if (a.interleaved) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) obuf[(ly * kTile + lx + j) * 3 + c] = (unsigned char)(bytes >> (8 * j));
+          } else {
+            *reinterpret_cast<uint32_t*>(&obuf[(c * kTile + ly) * kTile + lx]) = bytes;
+          }
+          continue;
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (x0 + j < g.nw) val[c][j] = (float((bytes >> (8 * j)) & 0xffu) - a.mean[c]) / a.std[c];
       }
+    }
+    if constexpr (kBytes) {
+      // ---- the window's bytes: whole 16-byte pieces of memory where a tile row covers them, bytes at its two ends ----
+      // A tile row is `len` bytes at `base` (any alignment; CHW: 3 * 32 rows of up to 32 bytes, HWC: 32 rows of up to 96).
+      // Piece k of a row is the ALIGNED 16 bytes at (base & ~15) + 16 k: a piece that lies inside the row is one store, a
+      // piece the row only touches is written byte by byte -- its other bytes belong to the neighbouring tile, row or slot.
+      if (!live) return;                                     // (workgroup-uniform)
+      __syncthreads();
+      const int rows_out = min(kTile, g.nh - oy0), cols_out = min(kTile, g.nw - ox0);
+      const int bpp = a.interleaved ? 3 : 1, lines = a.interleaved ? rows_out : 3 * rows_out;
+      const int len = cols_out * bpp, pitch = kTile * bpp, pieces = pitch / 16 + 1;
+      const long long plane = (long long)g.nh * g.nw;
+      for (int item = tid; item < lines * pieces; item += kResizeThreads) {
+        const int line = item / pieces, k = item - line * pieces;
+        const int c = a.interleaved ? 0 : line / rows_out, r = a.interleaved ? line : line - c * rows_out;
+        const long long px = (long long)(oy0 + r) * g.nw + ox0;
+        unsigned char* base = a.mask + wo.dst + (a.interleaved ? px * 3 : c * plane + px);
+        const unsigned char* from = obuf + (a.interleaved ? r : c * kTile + r) * pitch;
+        const int lead = int(reinterpret_cast<uintptr_t>(base) & 15);
+        const int lo = 16 * k - lead;                        // the piece is bytes [lo, lo + 16) of the row
+        if (lo >= len) continue;
+        if (lo >= 0 && lo + 16 <= len) {
+          rsz_u4 v;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            uint32_t word = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) word |= uint32_t(from[lo + 4 * q + j]) << (8 * j);
+            v[q] = word;
+          }
+          *reinterpret_cast<rsz_u4*>(base + lo) = v;
+        } else {
+          for (int j = max(lo, 0); j < min(lo + 16, len); ++j) base[j] = from[j];
+        }
+      }
+      return;
     }
     const size_t row = size_t(b) * H + y;
     if (a.channels_last) {

@@ -28,14 +28,20 @@ takes them) as it is: the frame dict then also holds gt_poly, a list per slot --
 RLE, whose gt_rle entry is None where the slot is a polygon -- and the dummy slot is the reference's polygon [0.0] * 6
 (`_get_dummy_anno`).  The model transforms the coordinates on the host and rasterises them at the target size on the device
 (vnext_amd/ops/poly_rle.py).
+
+COCO pre-training (IDOL's `COCO_CLIP_DatasetMapper`, INPUT.COCO_PRETRAIN): `sample_coco_plan` draws the
+mapper's chain flip -> [resize -> crop] -> resize per frame of the pair as `augment.ChainPlan`s, and `stage_coco_pair` makes
+the pair's entry of `batched_inputs` from ONE source image and its COCO annotations.
 """
 from __future__ import annotations
+
+import sys
 
 import numpy as np
 import torch
 
 from ..ops import resize
-from ..ops.augment import FramePlan
+from ..ops.augment import ChainPlan, FramePlan
 from ..utils.ytvis_json import string_to_counts
 
 
@@ -84,6 +90,88 @@ def sample_plan(cfg, sizes, num_frames, rng):
         nh, nw = resize.shortest_edge_size(ch, cw, size, max_size)
         plan.append(FramePlan(x0, y0, cw, ch, nh, nw, flip))
     return plan
+
+
+COCO_CROP_SHORT_EDGES = (400, 500, 600)      # the mapper's own ResizeShortestEdge in front of the crop; no maximum
+_NO_MAXIMUM = sys.maxsize
+
+
+def sample_coco_plan(cfg, size, rng, frames: int = 2):
+    """-> a ChainPlan per frame of one COCO pre-training pair whose source image has `size` = (h, w): the draws of IDOL's
+    `COCO_CLIP_DatasetMapper`.  Per frame (INPUT.PRETRAIN_SAME_CROP true: ONE draw, shared by all frames):
+      * the mapper's coin: no crop when `rng.random() > 0.5`, and never with INPUT.CROP.ENABLED false;
+      * RandomFlip(): a horizontal flip with p = 0.5;
+      * on the crop side ResizeShortestEdge((400, 500, 600), no maximum, "choice") and RandomCrop("absolute_range",
+        INPUT.CROP.SIZE) on the RESIZED size: `sample_plan`'s four integers, in its order;
+      * ResizeShortestEdge(MIN_SIZE_TRAIN, MAX_SIZE_TRAIN, MIN_SIZE_TRAIN_SAMPLING) on the cropped size.
+    As `sample_plan`, it reproduces the same DISTRIBUTIONS, not the same random stream: the reference draws from numpy's
+    global generator inside detectron2's transform classes, which cannot be replayed (or checked) without detectron2; `rng`
+    is a `numpy.random.Generator`.  What `sample_plan` refuses is refused here: INPUT.AUGMENTATIONS, another crop type, a
+    RANDOM_FLIP it does not know (a vertical flip).  The mapper itself never reads RANDOM_FLIP -- it always builds
+    RandomFlip() -- so every accepted value flips per frame; and its ResizeShortestEdge takes "choice" or "range" only."""
+    inp = cfg.INPUT
+    if _get(inp, "AUGMENTATIONS", None):
+        raise ValueError("sample_coco_plan: INPUT.AUGMENTATIONS %r are not built on the device" % (inp.AUGMENTATIONS,))
+    crop = _get(inp, "CROP", None)
+    crop_on = bool(_get(crop, "ENABLED", False))
+    if crop_on and _get(crop, "TYPE", "relative_range") != "absolute_range":
+        raise ValueError("sample_coco_plan: only RandomCrop('absolute_range') is built on the device")
+    lo, hi = (int(v) for v in _get(crop, "SIZE", (384, 600))) if crop_on else (0, 0)
+    short = _get(inp, "MIN_SIZE_TRAIN", (800,))
+    short = (int(short),) if isinstance(short, int) else tuple(int(s) for s in short)
+    max_size = int(_get(inp, "MAX_SIZE_TRAIN", 1333))
+    style = _get(inp, "MIN_SIZE_TRAIN_SAMPLING", "choice")
+    flip_mode = _get(inp, "RANDOM_FLIP", "horizontal")
+    if style not in ("choice", "range"):
+        raise ValueError("sample_coco_plan: MIN_SIZE_TRAIN_SAMPLING %r" % (style,))
+    if flip_mode not in ("none", "horizontal", "flip_by_clip"):
+        raise ValueError("sample_coco_plan: RANDOM_FLIP %r is not built on the device" % (flip_mode,))
+    if style == "range":
+        assert len(short) == 2, "MIN_SIZE_TRAIN must be two values with a 'range' sampling"
+    h, w = int(size[0]), int(size[1])
+
+    def draw():
+        use_crop = crop_on and not rng.random() > 0.5
+        flip = bool(rng.random() < 0.5)
+        h1, w1, x0, y0, cw, ch = h, w, 0, 0, w, h
+        if use_crop:
+            h1, w1 = resize.shortest_edge_size(h, w, int(rng.choice(COCO_CROP_SHORT_EDGES)), _NO_MAXIMUM)
+            ch = int(rng.integers(min(h1, lo), min(h1, hi) + 1))
+            cw = int(rng.integers(min(w1, lo), min(w1, hi) + 1))
+            y0 = int(rng.integers(h1 - ch + 1))
+            x0 = int(rng.integers(w1 - cw + 1))
+        edge = int(rng.integers(short[0], short[1] + 1)) if style == "range" else int(rng.choice(short))
+        nh, nw = resize.shortest_edge_size(ch, cw, edge, max_size)
+        return ChainPlan(h, w, flip, h1, w1, x0, y0, cw, ch, nh, nw)
+
+    if bool(_get(inp, "PRETRAIN_SAME_CROP", False)):
+        return [draw()] * frames
+    return [draw() for _ in range(frames)]
+
+
+def stage_coco_pair(image, annotations, plans, num_classes, layout: str = "chw"):
+    """image: ONE uint8 source image; annotations: its COCO annotations (dicts with "category_id", "bbox" = [x, y, w, h],
+    "segmentation" and optionally "iscrowd"); plans: a ChainPlan per frame of the pair -> the pair's entry of
+    `batched_inputs`, as `COCO_CLIP_DatasetMapper` arranges it: "image" lists the SAME tensor once per frame (staging uploads
+    it once), "augment" the plans; every frame's instance dict holds the non-crowd annotations in their order -- an
+    `iscrowd` annotation is dropped and gets NO slot -- with gt_ids 1..n (the same in every frame; a model with
+    `device_augment` sets -1 where the transformed box or the mask is empty), gt_classes, gt_poly (the polygon list; None
+    for an RLE slot, whose counts are in gt_rle: such a step takes the host route), gt_bbox (the annotations' boxes as XYXY,
+    float64 [n, 4]) and image_size = (nh, nw).  `num_classes` is unused (no dummy slot exists here); it keeps the signature
+    of `stage_clip`."""
+    assert len(plans) >= 1 and all(isinstance(p, ChainPlan) for p in plans)
+    kept = [a for a in annotations if a.get("iscrowd", 0) == 0]
+    classes = torch.tensor([int(a["category_id"]) for a in kept], dtype=torch.int64)
+    bbox = np.array([[a["bbox"][0], a["bbox"][1], a["bbox"][0] + a["bbox"][2], a["bbox"][1] + a["bbox"][3]] for a in kept],
+                    dtype=np.float64).reshape(len(kept), 4)
+    polys = [a["segmentation"] if _is_polygons(a["segmentation"]) else None for a in kept]
+    rles = [None if q is not None else _counts(a["segmentation"]) for a, q in zip(kept, polys)]
+    instances = [{"gt_classes": classes, "gt_ids": torch.arange(1, len(kept) + 1, dtype=torch.int64), "gt_rle": list(rles),
+                  "gt_poly": list(polys), "gt_bbox": bbox, "image_size": (p.nh, p.nw)} for p in plans]
+    entry = {"image": [image] * len(plans), "augment": list(plans), "instances": instances}
+    if layout != "chw":
+        entry["image_layout"] = layout
+    return entry
 
 
 def _counts(segmentation):

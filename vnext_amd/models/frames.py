@@ -109,10 +109,15 @@ def host_augmented(batched_inputs):
     """The host route of the same plan: every clip's frames and ground truth through `augment.reference_augment_*` on the CPU
     -> `batched_inputs` as a mapper of the reference would have made them (CHW uint8 frames at their targets; gt_masks,
     gt_boxes, the filtered gt_ids).  What a model with `device_augment` takes when `augment.applies` says no, and what the
-    tests compare the device route with."""
+    tests compare the device route with.  A clip of `augment.ChainPlan`s (a COCO pre-training pair) goes
+    through the chain's literal references: `reference_chain_frames`, the polygons through `chain_coords`, gt_boxes from the
+    annotations' boxes (`chain_boxes`), gt_ids = -1 where the box OR the mask is empty."""
     out = []
     for clip in batched_inputs:
         layout, plan = clip.get("image_layout", "chw"), clip["augment"]
+        if plan and augment.is_chain(plan[0]):
+            out.append(_host_chain_pair(clip, layout, plan))
+            continue
         frames = augment.reference_augment_frames(clip["image"], plan, layout)
         frames = [f if layout == "chw" else f.permute(2, 0, 1).contiguous() for f in frames]
         sizes = [resize.frame_size(f, layout) for f in clip["image"]]
@@ -136,6 +141,22 @@ def host_augmented(batched_inputs):
     return out
 
 
+def _host_chain_pair(clip, layout, plan):
+    """`host_augmented` for one clip of ChainPlans"""
+    frames = augment.reference_chain_frames(clip["image"], plan, layout)
+    frames = [f if layout == "chw" else f.permute(2, 0, 1).contiguous() for f in frames]
+    instances = []
+    for fr, p in zip(clip["instances"], plan):
+        masks = [augment.reference_polygon_mask(q, p) if q is not None else augment.reference_chain_rle_mask(c, p)
+                 for c, q in zip(fr["gt_rle"], fr["gt_poly"])]
+        boxes = augment.chain_boxes(fr["gt_bbox"], p)
+        keep = augment.boxes_nonempty(boxes) & np.array([bool(m.any()) for m in masks], dtype=bool)
+        gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, p.nh, p.nw, dtype=torch.bool)
+        instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": gm,
+                          "gt_boxes": torch.from_numpy(boxes), "gt_ids": torch.where(torch.from_numpy(keep), fr["gt_ids"], -1)})
+    return {**{k: v for k, v in clip.items() if k not in ("augment", "image_layout")}, "image": frames, "instances": instances}
+
+
 def augment_step(model, batched_inputs):
     """`device_augment` for one training step.  -> (batched_inputs, pre):
       the switch is off, the model is not training, or a clip carries no "augment": the inputs untouched, pre None;
@@ -146,7 +167,13 @@ def augment_step(model, batched_inputs):
       beyond it (`augment.applies`): `host_augmented` inputs, pre None -- the path without the switch.
     Frames staged with `stage_clip(polygons=True)` carry gt_poly: those slots are transformed on the host
     (`augment.transform_polygons`), rasterised at the target size by ONE `polygons_to_runs` call and read by the same
-    `augment_masks` call through pseudo-frame rows; nothing is read back from the device."""
+    `augment_masks` call through pseudo-frame rows; nothing is read back from the device.
+    A step whose clips ALL carry `augment.ChainPlan`s (COCO pre-training pairs) takes the same route with one launch in front:
+    `resize_window_bytes` for the frames that are resampled twice (none for a step without such a frame), then the same
+    `augment_frames`, `polygons_to_runs` and `augment_masks` calls.  Its gt_boxes are the annotations' boxes through the
+    chain, computed on the host and uploaded with the tables (the masks' own boxes are ignored), and a slot whose box is
+    empty is staged with id -1, so `nonempty ? id : -1` is the mapper's box AND mask test.  A step that mixes the two kinds
+    of plan, or holds an RLE slot under a ChainPlan, takes the host route."""
     if not (getattr(model, "device_augment", False) and model.training
             and all("augment" in clip for clip in batched_inputs)):
         return batched_inputs, None
@@ -154,30 +181,46 @@ def augment_step(model, batched_inputs):
     frames = [f for clip in batched_inputs for f in clip["image"]]
     plan = [p for clip in batched_inputs for p in clip["augment"]]
     # polygon slots: the coordinates through the frame's plan on the host, ONE rasterisation at the targets on the device
-    listed, ids, objects, sizes, f = [], [], [], [], 0
+    kinds = {augment.is_chain(p) for p in plan}
+    if len(kinds) != 1:
+        return host_augmented(batched_inputs), None
+    chain = kinds.pop()
+    listed, ids, objects, sizes, boxes, f = [], [], [], [], [], 0
     for clip in batched_inputs:
         for fr in clip["instances"]:
             polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
+            if chain and any(q is None for q in polys):        # an RLE slot under a ChainPlan: the host route
+                return host_augmented(batched_inputs), None
             for c, q in zip(fr["gt_rle"], polys):
                 if q is not None:
                     c = len(objects)                           # replaced by the object's run slot below
                     objects.append(augment.transform_polygons(q, plan[f]))
                     sizes.append((plan[f].nh, plan[f].nw))
                 listed.append((f, c, q is not None))
-            ids += fr["gt_ids"].tolist()
+            if chain:                                          # the mapper's box test, here; its mask test on the device
+                b = augment.chain_boxes(fr["gt_bbox"], plan[f])
+                boxes.append(b)
+                ids += np.where(augment.boxes_nonempty(b), fr["gt_ids"].numpy(), -1).tolist()
+            else:
+                ids += fr["gt_ids"].tolist()
             f += 1
     planned = poly_rle.plan_objects(objects, sizes) if objects else None
     if any(clip.get("image_layout", "chw") != layout for clip in batched_inputs) or \
-            not augment.applies(frames, plan, model.device, layout, polygons=planned):
+            not augment.applies(frames, plan, model.device, layout, polygons=planned) or \
+            (chain and objects and torch.device(model.device).type != "cuda"):      # (polygons are rasterised on the device)
         return host_augmented(batched_inputs), None
     poly_ends = None
     if objects:
         tables = poly_rle.polygons_to_runs(objects, sizes, device=model.device, check=False, planned=planned)
         poly_ends = tables.ends
         listed = [(f, augment.PolyRuns(*tables.slot_rows[c]) if is_poly else c, is_poly) for f, c, is_poly in listed]
-    staged = augment.stage_step(frames, plan, [(f, c) for f, c, _ in listed], model.device, layout, ids, poly_ends=poly_ends)
+    staged = augment.stage_step(frames, plan, [(f, c) for f, c, _ in listed], model.device, layout, ids, poly_ends=poly_ends,
+                                boxes=np.concatenate(boxes) if boxes else None)
+    augment.resize_window_bytes(staged)                        # (a chain step's first resample; otherwise nothing)
     pre = augment_staged(staged, model._pixel_stats, model.detr.detr.backbone)
     masks, boxes, nonempty = augment.augment_masks(staged)
+    if chain:
+        boxes = staged.boxes
     gt_ids = torch.where(nonempty, staged.ids, -1).to(torch.int64)
     views, out, f = staged.mask_views(masks), [], 0
     for clip in batched_inputs:

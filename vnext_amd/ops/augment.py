@@ -28,6 +28,17 @@ the host (crop, resize, flip, in the reference's order and with its expressions)
 them at the TARGET size on the device, and `stage_step` takes such a mask as a `PolyRuns(offset, size)` -- its slot of the
 device-resident run ends -- and gives it a pseudo-frame row (the target as its own source: the full window, no flip, identity
 nearest tables), so ONE `augment_masks` call makes gt_masks, boxes and `nonempty` of RLE and polygon masks alike.
+
+The COCO pre-training chain: IDOL's `COCO_CLIP_DatasetMapper` applies flip -> resize to (h1, w1) -> crop ->
+resize to (nh, nw), two resamples through a byte-rounded intermediate image.  `ChainPlan` is one frame's draw of it;
+`reference_chain_frames` / `reference_chain_rle_mask` / `chain_boxes` are the literal host route; `transform_polygons` and
+`reference_polygon_mask` take either kind of plan.  `stage_step` takes a step of ChainPlans: a source tensor that is listed
+more than once is uploaded once, every frame that needs the first resample gets a slot behind the source frames in the SAME
+device allocation, and `resize_window_bytes(staged)` -- one launch of `vnx_resize_window_bytes`, none when no frame needs it --
+fills the slots with the (mirrored, where the frame is flipped) crop window of the resized frame; `augment_frames` then reads a
+slot as a source frame.  Pillow's 8-bit bilinear resize commutes with a horizontal flip, so flip-first equals the mirrored
+window with the flip applied last -- which is what the kernels do, and what the tests hold to the literal order.
+`BYTES_CALLS` counts those launches.
 """
 from __future__ import annotations
 
@@ -42,7 +53,8 @@ from ..utils.ytvis_json import counts_to_string, rle_decode
 from . import ingest, poly_rle, resize
 
 CALLS = {"augment_frames": 0, "augment_masks": 0}      # calls through the C ABI (tests: the ops ran / did not run)
-SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS = 8, 8, 4
+BYTES_CALLS = {"resize_window_bytes": 0}               # (a dict of its own: tests compare CALLS as a whole)
+SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS, WIN_WORDS = 8, 8, 4, 16
 
 
 class FramePlan(NamedTuple):
@@ -53,6 +65,42 @@ class FramePlan(NamedTuple):
     nh: int
     nw: int
     flip: bool
+
+
+class ChainPlan(NamedTuple):
+    """One frame's draw of flip -> resize -> crop -> resize: the source size (h, w), the flip, the first resize's target
+    (h1, w1), the crop window {x0, y0, cw, ch} inside the FLIPPED and resized h1 x w1 image, the final target (nh, nw).
+    The side without a crop is the same record with (h1, w1) = (h, w) and the full window (`chain_full`)."""
+    h: int
+    w: int
+    flip: bool
+    h1: int
+    w1: int
+    x0: int
+    y0: int
+    cw: int
+    ch: int
+    nh: int
+    nw: int
+
+    @property
+    def resamples_twice(self) -> bool:
+        """the first resample exists (an identity resize is skipped, not run)"""
+        return (self.h1, self.w1) != (self.h, self.w)
+
+    @property
+    def mirrored_x0(self) -> int:
+        """the window's origin in the UNFLIPPED resized image"""
+        return self.w1 - self.x0 - self.cw if self.flip else self.x0
+
+
+def chain_full(h: int, w: int, nh: int, nw: int, flip: bool = False) -> ChainPlan:
+    """the side of the coin without a crop: flip, one resize"""
+    return ChainPlan(int(h), int(w), bool(flip), int(h), int(w), 0, 0, int(w), int(h), int(nh), int(nw))
+
+
+def is_chain(p) -> bool:
+    return isinstance(p, ChainPlan)
 
 
 class PolyRuns(NamedTuple):
@@ -84,7 +132,10 @@ def nearest_table(n_in: int, n_out: int):
     return _nearest(int(n_in), int(n_out))
 
 
-def _inside(p: FramePlan, h: int, w: int) -> bool:
+def _inside(p, h: int, w: int) -> bool:
+    if is_chain(p):      # the plan is of THIS frame, and its window lies inside the resized image
+        return (p.h, p.w) == (h, w) and min(p.h1, p.w1, p.nh, p.nw) >= 1 and \
+            _inside(FramePlan(p.x0, p.y0, p.cw, p.ch, p.nh, p.nw, p.flip), p.h1, p.w1)
     return p.x0 >= 0 and p.y0 >= 0 and p.cw >= 1 and p.ch >= 1 and p.x0 + p.cw <= w and p.y0 + p.ch <= h
 
 
@@ -107,12 +158,85 @@ def reference_augment_frames(frames, plan, layout: str = "chw"):
     return out
 
 
-def transform_polygons(segmentation, p: FramePlan):
+def chain_coords(xy, p: ChainPlan):
+    """flat float64 [x, y, x, y, ...] (changed in place) through a ChainPlan, in the reference's order and with its
+    expressions: `x = w - x` on a flip (HFlipTransform.apply_coords); `x * (w1 * 1.0 / w), y * (h1 * 1.0 / h)`
+    (ResizeTransform.apply_coords); `x -= x0, y -= y0` (CropTransform); `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`"""
+    if p.flip:
+        xy[0::2] = p.w - xy[0::2]
+    xy[0::2] = xy[0::2] * (p.w1 * 1.0 / p.w)
+    xy[1::2] = xy[1::2] * (p.h1 * 1.0 / p.h)
+    xy[0::2] -= p.x0
+    xy[1::2] -= p.y0
+    xy[0::2] = xy[0::2] * (p.nw * 1.0 / p.cw)
+    xy[1::2] = xy[1::2] * (p.nh * 1.0 / p.ch)
+    return xy
+
+
+def reference_chain_frames(frames, plan, layout: str = "chw"):
+    """uint8 frames (tensors or arrays of `layout`) through their ChainPlans in the LITERAL order: `np.flip`,
+    `resize.reference_resize` to (h1, w1), slicing, `resize.reference_resize` to (nh, nw) -> frames of the same kind and
+    layout.  The CPU route of the chain and the oracle of the GPU tests."""
+    ah, aw = resize._hw_axes(layout)
+    out = []
+    for f, p in zip(frames, plan):
+        is_tensor = torch.is_tensor(f)
+        a = f.detach().cpu().numpy() if is_tensor else np.asarray(f)
+        assert _inside(p, a.shape[ah], a.shape[aw])
+        if p.flip:
+            a = np.ascontiguousarray(np.flip(a, axis=aw))
+        a = resize.reference_resize(a, p.h1, p.w1, layout)
+        sl = [slice(None)] * 3
+        sl[ah], sl[aw] = slice(p.y0, p.y0 + p.ch), slice(p.x0, p.x0 + p.cw)
+        a = np.ascontiguousarray(resize.reference_resize(np.ascontiguousarray(a[tuple(sl)]), p.nh, p.nw, layout))
+        out.append(torch.from_numpy(a) if is_tensor else a)
+    return out
+
+
+def reference_chain_rle_mask(counts, p: ChainPlan):
+    """One RLE mask (COCO counts at the source size) through a ChainPlan as the reference's `apply_segmentation` does it:
+    `np.flip`, Pillow's NEAREST to (h1, w1), slicing, NEAREST to (nh, nw) -> bool [nh, nw].  Host route only."""
+    counts = [int(c) for c in counts]
+    if sum(counts) == p.h * p.w and min(counts) >= 0:
+        m = rle_decode({"size": [p.h, p.w], "counts": counts_to_string(counts)}).astype(bool)
+    else:
+        m = np.zeros((p.h, p.w), dtype=bool)
+    if p.flip:
+        m = np.flip(m, axis=1)
+    m = m[nearest_table(p.h, p.h1)][:, nearest_table(p.w, p.w1)]
+    m = m[p.y0:p.y0 + p.ch, p.x0:p.x0 + p.cw]
+    return np.ascontiguousarray(m[nearest_table(p.ch, p.nh)][:, nearest_table(p.cw, p.nw)])
+
+
+def chain_boxes(bboxes, p: ChainPlan):
+    """The annotations' boxes (XYXY, float64 [n, 4]) through a ChainPlan as `transform_instance_annotations` takes them: the
+    four corners through the coordinates' chain, their min / max, `clip(min=0)`, the minimum with (nw, nh, nw, nh) -- all in
+    float64 -- then float32 [n, 4], as `Boxes` holds them."""
+    b = np.asarray(bboxes, dtype=np.float64).reshape(-1, 4)
+    if b.shape[0] == 0:
+        return np.zeros((0, 4), dtype=np.float32)
+    corners = b[:, [0, 1, 2, 1, 0, 3, 2, 3]].reshape(-1)       # (x0, y0), (x1, y0), (x0, y1), (x1, y1), box by box
+    xy = chain_coords(corners.copy(), p).reshape(-1, 4, 2)
+    lo, hi = xy.min(axis=1), xy.max(axis=1)
+    out = np.concatenate((lo, hi), axis=1).clip(min=0)
+    return np.minimum(out, np.array([p.nw, p.nh, p.nw, p.nh], dtype=np.float64)).astype(np.float32)
+
+
+def boxes_nonempty(boxes, threshold: float = 1e-5):
+    """`Boxes.nonempty(threshold)` of float32 [n, 4]: width and height above the threshold"""
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    return ((boxes[:, 2] - boxes[:, 0]) > threshold) & ((boxes[:, 3] - boxes[:, 1]) > threshold)
+
+
+def transform_polygons(segmentation, p):
     """One annotation's polygons (or boxes, as their 4-vertex polygons) through the frame's plan, in float64 and in the
     reference's order: crop `x -= x0, y -= y0`; resize `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`
-    (ResizeTransform.apply_coords); flip `x = nw - x` (HFlipTransform.apply_coords).  The shifted polygon is NOT clipped to
-    the window (the reference clips with shapely first): the rasteriser drops columns outside the canvas and clamps rows.
+    (ResizeTransform.apply_coords); flip `x = nw - x` (HFlipTransform.apply_coords) -- or, for a ChainPlan, `chain_coords`:
+    flip, resize, crop, resize.  The shifted polygon is NOT clipped to the window (the reference clips with shapely first,
+    which is not installed): the rasteriser drops columns outside the canvas and clamps rows.
     -> a list of flat float64 polygons for a canvas of nh x nw."""
+    if is_chain(p):
+        return [chain_coords(poly.copy(), p) for poly in poly_rle.object_polygons(segmentation)]
     out = []
     for poly in poly_rle.object_polygons(segmentation):
         xy = poly.copy()
@@ -126,7 +250,7 @@ def transform_polygons(segmentation, p: FramePlan):
     return out
 
 
-def reference_polygon_mask(segmentation, p: FramePlan):
+def reference_polygon_mask(segmentation, p):
     """the host route of one polygon mask: `transform_polygons`, `object_counts_host` at (nh, nw) -> bool [nh, nw]"""
     counts = poly_rle.object_counts_host(transform_polygons(segmentation, p), p.nh, p.nw)
     return np.ascontiguousarray(poly_rle.counts_to_mask(counts, p.nh, p.nw))
@@ -163,7 +287,10 @@ def reference_augment_masks(masks, sizes, plan):
 
 
 # ---- staging ----------------------------------------------------------------------------------------------------------------
-def supported(p: FramePlan) -> bool:
+def supported(p) -> bool:
+    """both resamples of a ChainPlan, the one of a FramePlan, are in the kernel's range"""
+    if is_chain(p) and p.resamples_twice and not resize.supported(p.h, p.w, p.h1, p.w1):
+        return False
     return resize.supported(p.ch, p.cw, p.nh, p.nw)
 
 
@@ -172,7 +299,7 @@ def applies(frames, plan, device, layout: str = "chw", polygons=None) -> bool:
     the kernel's range; polygons: (objects, sizes) of the step's transformed polygon masks, or what
     `poly_rle.plan_objects` made of them -- every one inside the caps of vnx_poly_rle"""
     ah, aw = resize._hw_axes(layout)
-    if not frames or len(frames) != len(plan):
+    if not frames or len(frames) != len(plan) or len({is_chain(p) for p in plan}) > 1:
         return False
     if polygons is not None:
         fits = polygons[2] if len(polygons) == 3 else poly_rle.plan_objects(*polygons)[2]
@@ -213,6 +340,24 @@ def _coeff_words(plan):
     return np.concatenate([head.reshape(-1)] + parts)
 
 
+def _window_words(words, win):
+    """`resize_window_bytes`' rows (lists of 16, the triples still zero) and a step's `coeffs` words -> (the words with each
+    distinct table of (w -> w1) and (h -> h1) appended once, int32 [k, 16] rows that name them)"""
+    win = np.asarray(win, dtype=np.int32).reshape(-1, WIN_WORDS)
+    parts, at, placed = [words], int(words.size), {}
+    for row in win:
+        for j, pair in enumerate(((int(row[2]), int(row[4])), (int(row[1]), int(row[3])))):
+            if pair[0] == pair[1]:
+                continue                     # ksize 0: the pass is skipped
+            if pair not in placed:
+                bounds, kk = resize.pillow_coeffs(*pair)
+                placed[pair] = (at, at + bounds.size, kk.shape[1])
+                parts += [bounds.reshape(-1), kk.reshape(-1)]
+                at += bounds.size + kk.size
+            row[10 + 3 * j:13 + 3 * j] = placed[pair]
+    return np.concatenate(parts), win
+
+
 class Staged(NamedTuple):
     pixels: torch.Tensor        # uint8 [bytes]
     src_table: torch.Tensor     # int32 [n, 8] = {byte offset, h, w, x0, y0, cw, ch, flip}
@@ -227,6 +372,9 @@ class Staged(NamedTuple):
     groups: tuple               # per frame (first mask, masks, nh, nw): the masks of a frame are consecutive
     mask_src: object = None     # with polygon masks: src_table / dst_table of the frames AND the pseudo-frames (the rows
     mask_dst: object = None     # mask_rows index); src_table and dst_table above are their first n rows
+    win_table: object = None    # a step of ChainPlans: int32 [k, 16], the rows of `resize_window_bytes` (k may be 0)
+    win_size: tuple = None      # (H1, W1) that launch is padded to
+    boxes: object = None        # fp32 [m, 4]: the masks' boxes where the caller computed them (`chain_boxes`)
 
     def mask_views(self, masks):
         """the flat output of `augment_masks` -> per frame bool [n_inst, nh, nw] (views)"""
@@ -237,11 +385,12 @@ class Staged(NamedTuple):
         return out
 
 
-def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_ends=None) -> Staged:
+def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_ends=None, boxes=None) -> Staged:
     """frames: uint8 CPU tensors of `layout`; plan: a FramePlan per frame; masks: [(frame index, COCO counts)] with the masks
     of a frame CONSECUTIVE and the frames ascending; ids: the masks' instance ids (default 0).  A mask may be a
     `PolyRuns(offset, size)` instead of counts: its run ends are words [offset, offset + size) of `poly_ends` (int32 on
-    `device`, at the frame's target size).  See the module docstring."""
+    `device`, at the frame's target size).  plan may be a ChainPlan per frame instead (its masks are PolyRuns; boxes: the
+    masks' boxes, fp32 [m, 4], packed into the same upload).  See the module docstring."""
     device = torch.device(device)
     n, m = len(frames), len(masks)
     sizes = [resize.frame_size(f, layout) for f in frames]
@@ -252,9 +401,29 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_
     assert not pseudo or (poly_ends is not None and poly_ends.is_cuda and device.type == "cuda"), \
         "stage_step: polygon masks take device-resident run ends"
     src, off = np.zeros((n + len(pseudo), SRC_WORDS), dtype=np.int32), 0
-    for i, ((h, w), p) in enumerate(zip(sizes, plan)):
-        src[i] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
-        off += ingest._align16(3 * h * w)
+    chain = bool(plan) and is_chain(plan[0])
+    assert all(is_chain(p) == chain for p in plan), "stage_step: ChainPlans or FramePlans, not both"
+    win, uploads = [], list(zip(frames, [0] * n))      # uploads: (frame, byte offset), each distinct tensor once
+    if not chain:
+        for i, ((h, w), p) in enumerate(zip(sizes, plan)):
+            src[i] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
+            uploads[i] = (frames[i], off)
+            off += ingest._align16(3 * h * w)
+    else:
+        placed = {}                              # a source listed twice (the pair of one image) is uploaded once
+        for f, (h, w) in zip(frames, sizes):
+            if id(f) not in placed:
+                placed[id(f)] = off
+                off += ingest._align16(3 * h * w)
+        uploads, slot = [(f, placed[id(f)]) for f in {id(f): f for f in frames}.values()], off
+        for i, ((h, w), p) in enumerate(zip(sizes, plan)):
+            assert _inside(p, h, w), "stage_step: a ChainPlan of another frame, or a window outside (h1, w1)"
+            if p.resamples_twice:                # the window of the unflipped resized frame -> its slot; the flip comes last
+                win.append([placed[id(frames[i])], h, w, p.h1, p.w1, p.mirrored_x0, p.y0, p.cw, p.ch, slot] + [0] * 6)
+                src[i] = (slot, p.ch, p.cw, 0, 0, p.cw, p.ch, int(p.flip))
+                slot += ingest._align16(3 * p.ch * p.cw)
+            else:                                # one resample: the (mirrored) window of the source itself
+                src[i] = (placed[id(frames[i])], h, w, p.mirrored_x0, p.y0, p.cw, p.ch, int(p.flip))
     all_plan = list(plan) + [full_plan(plan[f].nh, plan[f].nw, plan[f].nh, plan[f].nw) for f in pseudo]
     for f, row in pseudo.items():            # the target as its own source; the mask kernel reads no pixels
         src[row] = (0, plan[f].nh, plan[f].nw, 0, 0, plan[f].nw, plan[f].nh, 0)
@@ -286,21 +455,33 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_
         rows[[i for i, (_, c) in enumerate(masks) if isinstance(c, PolyRuns)], 0] += ends.size
     idv = np.zeros(m, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(m)
     small = [src.reshape(-1), dst.reshape(-1), words, ends, rows.reshape(-1), idv]
+    if chain:                                    # the first resample's tables ride behind the others, each distinct one once
+        words, win = _window_words(words, win)
+        box_bits = np.zeros((m, 4), dtype=np.float32) if boxes is None else np.asarray(boxes, dtype=np.float32).reshape(m, 4)
+        small[2:3] = [words]
+        small += [win.reshape(-1), box_bits.reshape(-1).view(np.int32)]
     cuts = np.cumsum([0] + [s.size for s in small])
     head = ingest._align16(4 * int(cuts[-1]))
     buf = torch.empty(head + off, dtype=torch.uint8, pin_memory=device.type == "cuda")
     buf[:4 * int(cuts[-1])].view(torch.int32).copy_(torch.from_numpy(np.concatenate(small)))
-    for f, row in zip(frames, src.tolist()):
-        o, h, w = row[:3]
-        buf[head + o:head + o + 3 * h * w].view(f.shape).copy_(f)
-    whole = buf.to(device, non_blocking=True)
+    for f, o in uploads:
+        buf[head + o:head + o + f.numel()].view(f.shape).copy_(f)
+    if chain:                                    # the slots follow the source frames in the SAME allocation; nothing of them is uploaded
+        whole = torch.empty(head + slot, dtype=torch.uint8, device=device)
+        whole[:head + off].copy_(buf, non_blocking=True)
+    else:
+        whole = buf.to(device, non_blocking=True)
     ints = whole[:4 * int(cuts[-1])].view(torch.int32)
     part = [ints[int(a):int(b)] for a, b in zip(cuts[:-1], cuts[1:])]
     src_d, dst_d = part[0].view(-1, SRC_WORDS), part[1].view(-1, 3)
     ends_d = torch.cat((part[3], poly_ends.to(torch.int32))) if pseudo else part[3]
+    extra = ()
+    if chain:
+        extra = (part[6].view(len(win), WIN_WORDS), resize.padded_size([(r[8], r[7]) for r in win.tolist()] or [(1, 1)]),
+                 part[7].view(torch.float32).view(m, 4))
     return Staged(whole[head:], src_d[:n], dst_d[:n], part[2], ends_d, part[4].view(m, MASK_ROW_WORDS), part[5],
                   padded_size(plan), layout, int(o_at), tuple(tuple(g) for g in groups),
-                  src_d if pseudo else None, dst_d if pseudo else None)
+                  src_d if pseudo else None, dst_d if pseudo else None, *extra)
 
 
 def _plan_of(staged: Staged):
@@ -309,6 +490,29 @@ def _plan_of(staged: Staged):
 
 
 # ---- the ops ----------------------------------------------------------------------------------------------------------------
+def resize_window_bytes(staged: Staged) -> None:
+    """The first resample of a step of ChainPlans: every row of `staged.win_table` -> the bytes of its slot inside
+    `staged.pixels` (in place).  One launch on the current stream, before `augment_frames`; none when the step has no such
+    frame (or is not a chain step)."""
+    win, pixels, layout = staged.win_table, staged.pixels, staged.layout
+    if win is None or win.shape[0] == 0:
+        return
+    if not pixels.is_cuda:
+        ah, aw = resize._hw_axes(layout)
+        for o, h, w, h1, w1, x0, y0, cw, ch, d in (r[:10] for r in win.tolist()):
+            f = pixels[o:o + 3 * h * w].view((3, h, w) if layout == "chw" else (h, w, 3))
+            sl = [slice(None)] * 3
+            sl[ah], sl[aw] = slice(y0, y0 + ch), slice(x0, x0 + cw)
+            pixels[d:d + 3 * ch * cw].copy_(resize.reference_resize(f, h1, w1, layout)[tuple(sl)].reshape(-1))
+        return
+    H1, W1 = staged.win_size
+    with torch.cuda.device(pixels.device):
+        _lib.check(_lib.lib().vnx_resize_window_bytes(
+            pixels.data_ptr(), pixels.numel(), win.data_ptr(), staged.coeffs.data_ptr(), staged.coeffs.numel(),
+            win.shape[0], H1, W1, int(layout == "hwc"), _lib.current_stream(pixels)))
+    BYTES_CALLS["resize_window_bytes"] += 1
+
+
 def augment_frames(staged: Staged, mean, std, channels_last: bool = False):
     """-> (x fp32 [B, 3, H, W], mask bool [B, H, W]) of the augmented frames; one launch"""
     pixels, layout, (H, W) = staged.pixels, staged.layout, staged.size
