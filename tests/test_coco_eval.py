@@ -259,7 +259,7 @@ def test_ytvis_eval_with_device_matching_reproduces_its_fixture():
     fx = ytvis_golden()
     ev = YTVISEval(gt, device="cuda", area_rng=fx["area_rng"].tolist(), device_matching=True).add(recs)
     res = ev.evaluate()
-    assert ev.timings["device_matching"] is True
+    assert ev.matching == "device" and ev.timings["matching"] == "device" and not ev.timings["host_fallback"]
     assert_ytvis(res, fx)
     plain = YTVISEval(gt, device="cuda", area_rng=fx["area_rng"].tolist()).add(recs).evaluate()
     for a, b in zip(res["eval_vids"], plain["eval_vids"]):

@@ -329,3 +329,19 @@ def test_evaluator_on_the_device_reproduces_the_reference():
         segs = [dict(s) for s in recs[0]["segmentations"]]
         segs[1]["counts"] = segs[1]["counts"][:-1] + "o"
         YTVISEval(gt, device="cuda").add([dict(recs[0], segmentations=segs)]).evaluate()
+
+
+def test_the_three_matching_routes_agree_on_the_device_and_the_kernel_route_repeats():
+    from test_ytvis_eval import assert_same_eval_vids
+    gt, recs = golden_documents()
+    res = {}
+    for name, matching in (("device", "device"), ("vectorised", "vectorised"), ("host", "host"), ("again", "device")):
+        ev = YTVISEval(gt, device="cuda", area_rng=golden()["area_rng"].tolist(), matching=matching).add(recs)
+        res[name] = ev.evaluate()
+        assert ev.timings["matching"] == matching and not ev.timings["host_fallback"]
+    for name in ("vectorised", "host", "again"):
+        for k in ("precision", "recall", "scores", "stats"):
+            assert res[name][k].tobytes() == res["device"][k].tobytes(), (name, k)
+        assert_same_eval_vids(res[name], res["device"])
+    for key in res["device"]["ious"]:
+        assert np.asarray(res["again"]["ious"][key]).tobytes() == np.asarray(res["device"]["ious"][key]).tobytes()

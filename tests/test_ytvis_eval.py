@@ -124,6 +124,64 @@ def test_per_category_ap_and_untouched_entries():
     assert (none["precision"][:, :, :, 1:, :] == -1).all()
 
 
+# ---- the matching routes, and the arithmetic shared with COCOEval ----------------------------------------------------
+def assert_same_eval_vids(a, b):
+    """two results' `eval_vids`: the same ids and scores, the four match arrays byte for byte with equal dtypes"""
+    assert len(a["eval_vids"]) == len(b["eval_vids"]) > 0
+    for x, y in zip(a["eval_vids"], b["eval_vids"]):
+        assert (x is None) == (y is None)
+        if x is not None:
+            assert x["dtIds"] == y["dtIds"] and x["gtIds"] == y["gtIds"] and x["dtScores"] == y["dtScores"]
+            for k in ("dtMatches", "gtMatches", "dtIgnore", "gtIgnore"):
+                assert x[k].tobytes() == y[k].tobytes() and x[k].dtype == y[k].dtype, k
+
+
+def test_vectorised_host_route_equals_match_host():
+    gt, recs = golden_documents()
+    res = {}
+    for matching in ("host", "vectorised"):
+        ev = YTVISEval(gt, device="cpu", area_rng=golden()["area_rng"].tolist(), matching=matching).add(recs)
+        res[matching] = ev.evaluate()
+        assert ev.matching == ev.timings["matching"] == matching
+        assert_equals_golden(res[matching], golden())
+    assert_same_eval_vids(res["vectorised"], res["host"])
+
+
+def test_matching_defaults_and_the_device_route_without_a_device():
+    gt, _ = golden_documents()
+    assert YTVISEval(gt, device="cpu").matching == "host"
+    assert YTVISEval(gt, device="cpu", device_matching=True).matching == "host"       # silently off without a device
+    with pytest.raises(ValueError, match="matching 'device'"):
+        YTVISEval(gt, device="cpu", matching="device")
+
+
+def test_coco_eval_and_ytvis_eval_share_their_arithmetic():
+    """COCO's segm documents restated as one-frame videos score the same under both classes once the crowds are gone:
+    the crowd's union (the detection's area alone) is COCOEval's, and with the crowds in, the two differ."""
+    from vnext_amd.evaluation import COCOEval
+    fx = dict(np.load(os.path.join(GOLDEN_DIR, "coco_eval.npz")))
+    gt, recs = json.loads(str(fx["gt_json"])), json.loads(str(fx["dt_json"]))
+    area_rng = fx["area_rng"].tolist()
+    assert len(gt["annotations"]) == 18 and sum(bool(a["iscrowd"]) for a in gt["annotations"]) == 2
+
+    def both(anns):
+        coco = dict(gt, annotations=anns)
+        videos = {"videos": [dict(v, length=1) for v in gt["images"]], "categories": gt["categories"],
+                  "annotations": [{"id": a["id"], "video_id": a["image_id"], "category_id": a["category_id"],
+                                   "iscrowd": a["iscrowd"], "segmentations": [a["segmentation"]], "areas": [a["area"]]}
+                                  for a in anns]}
+        tracks = [{"video_id": r["image_id"], "category_id": r["category_id"], "score": r["score"],
+                   "segmentations": [r["segmentation"]]} for r in recs]
+        return (COCOEval(coco, "segm", device="cpu", area_rng=area_rng).add(recs).evaluate(),
+                YTVISEval(videos, device="cpu", area_rng=area_rng).add(tracks).evaluate())
+    a, b = both([a for a in gt["annotations"] if not a["iscrowd"]])
+    assert a["AP"] > 0.5
+    for key in ("precision", "recall", "scores", "stats"):
+        assert a[key].dtype == b[key].dtype and a[key].tobytes() == b[key].tobytes(), key
+    a, b = both(gt["annotations"])
+    assert a["precision"].tobytes() != b["precision"].tobytes()
+
+
 # ---- run tables ------------------------------------------------------------------------------------------------------
 def alternating(h, w):
     """the checkerboard of the column-major order: every pixel differs from the one before it, h * w runs"""

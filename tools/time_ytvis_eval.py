@@ -7,8 +7,8 @@ one category each, masks of a few ellipses (a few hundred runs), drawn and RLE-e
   decode_ms    the two launches of the run-table decode (vnx_rle_runs_measure / _write) and the scan between them, over
                every string of the set, arenas preallocated; median of device-event times
   sums_ms      vnx_video_iou_sums over every (detection, ground truth) pair of the set; device events
-  evaluate     YTVISEval(device="cuda").evaluate() by stage on the host clock (tables = upload + decode, sums =
-               upload + kernel + copy back, matching, accumulation)
+  evaluate     YTVISEval(device="cuda").evaluate() by stage on the host clock (tables = flat state + upload + decode,
+               sums = upload + kernel + copy back, matching, accumulation)
   numpy_path   the same evaluate() on THIS PACKAGE'S OWN numpy path (device="cpu": string decode and pair sums in
                numpy / Python) -- not the reference's evaluator, which needs pycocotools and cannot run here; both paths
                must return identical arrays
