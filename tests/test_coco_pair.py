@@ -302,7 +302,7 @@ def packed(golden, layout):
             buf[slot:slot + 3 * p.ch * p.cw] = 0xCD
             want = in_layout(np.flip(mid, axis=1) if flip else mid, layout).reshape(-1)
             expect[slot:slot + want.numel()] = want
-    words, win = augment._window_words(np.zeros(0, dtype=np.int32), rows)
+    words, win = augment.window_words(np.zeros(0, dtype=np.int32), rows)
     return buf, torch.from_numpy(win), torch.from_numpy(words), listed, where, expect
 
 
@@ -340,7 +340,7 @@ def test_window_bytes_equal_the_fixture_and_nothing_else_is_written(golden, layo
     plans = [p for _, _, _, p, _, _ in listed]
     dst = torch.tensor([(0, p.nh, p.nw) for p in plans], dtype=torch.int32)
     H2, W2 = augment.padded_size(plans)
-    x, mask = c_frames(got, src, dst, torch.from_numpy(augment._coeff_words(plans)), len(plans), H2, W2, False, layout)
+    x, mask = c_frames(got, src, dst, torch.from_numpy(augment.coeff_words(plans)), len(plans), H2, W2, False, layout)
     for k, (i, flip, _, p, _, want) in enumerate(listed):
         assert torch.equal(x[k, :, :p.nh, :p.nw].cpu(), torch.from_numpy(want.transpose(2, 0, 1).astype(np.float32))), (i, flip)
         assert not mask[k, :p.nh, :p.nw].any() and mask[k, p.nh:].all() and mask[k, :, p.nw:].all()

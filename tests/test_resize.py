@@ -290,7 +290,7 @@ def tables(frames, targets, layout, offs):
     sizes = [resize.frame_size(f, layout) for f in frames]
     src = torch.tensor([(o, h, w) for o, (h, w) in zip(offs, sizes)], dtype=torch.int32)
     dst = torch.tensor([(0, nh, nw) for nh, nw in targets], dtype=torch.int32)
-    return src, dst, torch.from_numpy(resize._coeff_words(sizes, targets))
+    return src, dst, torch.from_numpy(resize.coeff_words(sizes, targets))
 
 
 def c_resize(buf, src, dst, coeffs, B, H, W, mean, std, channels_last, layout):

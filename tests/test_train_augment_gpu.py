@@ -78,7 +78,7 @@ def tables(frames, plan, layout, offs):
     src = torch.tensor([(o, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip)) for o, (h, w), p in zip(offs, sizes, plan)],
                        dtype=torch.int32)
     dst = torch.tensor([(0, p.nh, p.nw) for p in plan], dtype=torch.int32)
-    return src, dst, torch.from_numpy(augment._coeff_words(plan))
+    return src, dst, torch.from_numpy(augment.coeff_words(plan))
 
 
 def c_frames(buf, src, dst, coeffs, B, H, W, channels_last, layout, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0),
@@ -170,7 +170,7 @@ def test_a_full_window_without_flip_equals_resize_ingest_frames_bit_for_bit():
         buf, offs = pack(frames)
         plan = [augment.full_plan(h, w, nh, nw) for (h, w), (nh, nw) in zip(sizes, targets)]
         src, dst, coeffs = tables(frames, plan, layout, offs)
-        old_coeffs = torch.from_numpy(resize._coeff_words(sizes, targets))
+        old_coeffs = torch.from_numpy(resize.coeff_words(sizes, targets))
         for channels_last in (False, True):
             x, mask = c_frames(buf, src, dst, coeffs, 4, H, W, channels_last, layout, mean, std)
             want, want_mask = c_frames(buf, src[:, :3].contiguous(), dst, old_coeffs, 4, H, W, channels_last, layout, mean, std,
@@ -245,7 +245,7 @@ def mask_tables(sizes, plan, masks):
         e_at += e.size
         o_at += plan[f].nh * plan[f].nw
     return (torch.from_numpy(np.concatenate(ends)), torch.tensor(rows, dtype=torch.int32), src, dst,
-            torch.from_numpy(augment._coeff_words(plan)), o_at)
+            torch.from_numpy(augment.coeff_words(plan)), o_at)
 
 
 @pytest.mark.gpu

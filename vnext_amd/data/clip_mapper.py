@@ -51,28 +51,36 @@ def _get(node, key, default):
     return node.get(key, default) if isinstance(node, dict) else getattr(node, key, default)
 
 
-def sample_plan(cfg, sizes, num_frames, rng):
-    """-> a FramePlan per frame of one clip; see the module docstring"""
+def _read_input(cfg, who: str, styles):
+    """What both samplers read of `cfg.INPUT`, and their refusals (`who`: the sampler's name in the messages; `styles`: the
+    MIN_SIZE_TRAIN_SAMPLING values it takes) -> (crop on, crop lo, crop hi, short edges, max size, sampling, flip mode)"""
     inp = cfg.INPUT
-    assert len(sizes) == num_frames
     if _get(inp, "AUGMENTATIONS", None):
-        raise ValueError("sample_plan: INPUT.AUGMENTATIONS %r are not built on the device" % (inp.AUGMENTATIONS,))
+        raise ValueError("%s: INPUT.AUGMENTATIONS %r are not built on the device" % (who, inp.AUGMENTATIONS))
     crop = _get(inp, "CROP", None)
     crop_on = bool(_get(crop, "ENABLED", False))
     if crop_on and _get(crop, "TYPE", "relative_range") != "absolute_range":
-        raise ValueError("sample_plan: only RandomCrop('absolute_range') is built on the device")
+        raise ValueError("%s: only RandomCrop('absolute_range') is built on the device" % who)
     lo, hi = (int(v) for v in _get(crop, "SIZE", (384, 600))) if crop_on else (0, 0)
     short = _get(inp, "MIN_SIZE_TRAIN", (800,))
     short = (int(short),) if isinstance(short, int) else tuple(int(s) for s in short)
     max_size = int(_get(inp, "MAX_SIZE_TRAIN", 1333))
     style = _get(inp, "MIN_SIZE_TRAIN_SAMPLING", "choice")
     flip_mode = _get(inp, "RANDOM_FLIP", "horizontal")
-    if style not in ("choice", "range", "choice_by_clip", "range_by_clip"):
-        raise ValueError("sample_plan: MIN_SIZE_TRAIN_SAMPLING %r" % (style,))
+    if style not in styles:
+        raise ValueError("%s: MIN_SIZE_TRAIN_SAMPLING %r" % (who, style))
     if flip_mode not in ("none", "horizontal", "flip_by_clip"):
-        raise ValueError("sample_plan: RANDOM_FLIP %r is not built on the device" % (flip_mode,))
+        raise ValueError("%s: RANDOM_FLIP %r is not built on the device" % (who, flip_mode))
     if "range" in style:
         assert len(short) == 2, "MIN_SIZE_TRAIN must be two values with a 'range' sampling"
+    return crop_on, lo, hi, short, max_size, style, flip_mode
+
+
+def sample_plan(cfg, sizes, num_frames, rng):
+    """-> a FramePlan per frame of one clip; see the module docstring"""
+    assert len(sizes) == num_frames
+    crop_on, lo, hi, short, max_size, style, flip_mode = _read_input(
+        cfg, "sample_plan", ("choice", "range", "choice_by_clip", "range_by_clip"))
 
     use_crop = crop_on and not rng.random() > 0.5      # the coin per clip
     plan, size, flip = [], None, False
@@ -109,25 +117,7 @@ def sample_coco_plan(cfg, size, rng, frames: int = 2):
     is a `numpy.random.Generator`.  What `sample_plan` refuses is refused here: INPUT.AUGMENTATIONS, another crop type, a
     RANDOM_FLIP it does not know (a vertical flip).  The mapper itself never reads RANDOM_FLIP -- it always builds
     RandomFlip() -- so every accepted value flips per frame; and its ResizeShortestEdge takes "choice" or "range" only."""
-    inp = cfg.INPUT
-    if _get(inp, "AUGMENTATIONS", None):
-        raise ValueError("sample_coco_plan: INPUT.AUGMENTATIONS %r are not built on the device" % (inp.AUGMENTATIONS,))
-    crop = _get(inp, "CROP", None)
-    crop_on = bool(_get(crop, "ENABLED", False))
-    if crop_on and _get(crop, "TYPE", "relative_range") != "absolute_range":
-        raise ValueError("sample_coco_plan: only RandomCrop('absolute_range') is built on the device")
-    lo, hi = (int(v) for v in _get(crop, "SIZE", (384, 600))) if crop_on else (0, 0)
-    short = _get(inp, "MIN_SIZE_TRAIN", (800,))
-    short = (int(short),) if isinstance(short, int) else tuple(int(s) for s in short)
-    max_size = int(_get(inp, "MAX_SIZE_TRAIN", 1333))
-    style = _get(inp, "MIN_SIZE_TRAIN_SAMPLING", "choice")
-    flip_mode = _get(inp, "RANDOM_FLIP", "horizontal")
-    if style not in ("choice", "range"):
-        raise ValueError("sample_coco_plan: MIN_SIZE_TRAIN_SAMPLING %r" % (style,))
-    if flip_mode not in ("none", "horizontal", "flip_by_clip"):
-        raise ValueError("sample_coco_plan: RANDOM_FLIP %r is not built on the device" % (flip_mode,))
-    if style == "range":
-        assert len(short) == 2, "MIN_SIZE_TRAIN must be two values with a 'range' sampling"
+    crop_on, lo, hi, short, max_size, style, _ = _read_input(cfg, "sample_coco_plan", ("choice", "range"))
     h, w = int(size[0]), int(size[1])
 
     def draw():
@@ -144,7 +134,7 @@ def sample_coco_plan(cfg, size, rng, frames: int = 2):
         nh, nw = resize.shortest_edge_size(ch, cw, edge, max_size)
         return ChainPlan(h, w, flip, h1, w1, x0, y0, cw, ch, nh, nw)
 
-    if bool(_get(inp, "PRETRAIN_SAME_CROP", False)):
+    if bool(_get(cfg.INPUT, "PRETRAIN_SAME_CROP", False)):
         return [draw()] * frames
     return [draw() for _ in range(frames)]
 

@@ -106,55 +106,54 @@ def augment_staged(staged, stats, backbone):
 
 
 def host_augmented(batched_inputs):
-    """The host route of the same plan: every clip's frames and ground truth through `augment.reference_augment_*` on the CPU
+    """The host route of the same plan: every clip's frames and ground truth through `augment.reference_*` on the CPU
     -> `batched_inputs` as a mapper of the reference would have made them (CHW uint8 frames at their targets; gt_masks,
     gt_boxes, the filtered gt_ids).  What a model with `device_augment` takes when `augment.applies` says no, and what the
-    tests compare the device route with.  A clip of `augment.ChainPlan`s (a COCO pre-training pair) goes
-    through the chain's literal references: `reference_chain_frames`, the polygons through `chain_coords`, gt_boxes from the
-    annotations' boxes (`chain_boxes`), gt_ids = -1 where the box OR the mask is empty."""
+    tests compare the device route with.  Frames, RLE masks and polygons go through their own plan's `frame`, `mask` and
+    `coords`; only the boxes and the keep flags differ by kind (`truth`): a FramePlan takes them from the masks, a ChainPlan
+    (a COCO pre-training pair) from the annotations' boxes (`chain_boxes`), gt_ids = -1 where the box OR
+    the mask is empty."""
     out = []
     for clip in batched_inputs:
         layout, plan = clip.get("image_layout", "chw"), clip["augment"]
-        if plan and augment.is_chain(plan[0]):
-            out.append(_host_chain_pair(clip, layout, plan))
-            continue
         frames = augment.reference_augment_frames(clip["image"], plan, layout)
         frames = [f if layout == "chw" else f.permute(2, 0, 1).contiguous() for f in frames]
-        sizes = [resize.frame_size(f, layout) for f in clip["image"]]
         instances = []
-        for i, fr in enumerate(clip["instances"]):
+        for fr, p, src in zip(clip["instances"], plan, clip["image"]):
             polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
-            # a polygon slot goes in as the empty mask and is replaced by its own host route
-            masks, boxes, flags = augment.reference_augment_masks(
-                [(i, c if q is None else [sizes[i][0] * sizes[i][1]]) for c, q in zip(fr["gt_rle"], polys)], sizes, plan)
-            for s, q in enumerate(polys):
-                if q is not None:
-                    masks[s] = augment.reference_polygon_mask(q, plan[i])
-                    boxes[s], flags[s] = augment.mask_box(masks[s])
-            nh, nw = fr["image_size"]
-            gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, nh, nw, dtype=torch.bool)
-            keep = torch.from_numpy(flags)
+            masks = [augment.reference_polygon_mask(q, p) if q is not None else
+                     augment.reference_rle_mask(c, resize.frame_size(src, layout), p) for c, q in zip(fr["gt_rle"], polys)]
+            boxes, keep = p.truth(masks, fr.get("gt_bbox"))
+            gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, p.nh, p.nw, dtype=torch.bool)
             instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": gm,
-                              "gt_boxes": torch.from_numpy(boxes), "gt_ids": torch.where(keep, fr["gt_ids"], -1)})
+                              "gt_boxes": torch.from_numpy(boxes), "gt_ids": torch.where(torch.from_numpy(keep), fr["gt_ids"], -1)})
         out.append({**{k: v for k, v in clip.items() if k not in ("augment", "image_layout")}, "image": frames,
                     "instances": instances})
     return out
 
 
-def _host_chain_pair(clip, layout, plan):
-    """`host_augmented` for one clip of ChainPlans"""
-    frames = augment.reference_chain_frames(clip["image"], plan, layout)
-    frames = [f if layout == "chw" else f.permute(2, 0, 1).contiguous() for f in frames]
-    instances = []
-    for fr, p in zip(clip["instances"], plan):
-        masks = [augment.reference_polygon_mask(q, p) if q is not None else augment.reference_chain_rle_mask(c, p)
-                 for c, q in zip(fr["gt_rle"], fr["gt_poly"])]
-        boxes = augment.chain_boxes(fr["gt_bbox"], p)
-        keep = augment.boxes_nonempty(boxes) & np.array([bool(m.any()) for m in masks], dtype=bool)
-        gm = torch.from_numpy(np.stack(masks)) if masks else torch.zeros(0, p.nh, p.nw, dtype=torch.bool)
-        instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": gm,
-                          "gt_boxes": torch.from_numpy(boxes), "gt_ids": torch.where(torch.from_numpy(keep), fr["gt_ids"], -1)})
-    return {**{k: v for k, v in clip.items() if k not in ("augment", "image_layout")}, "image": frames, "instances": instances}
+def _step_masks(truths, plan, chain):
+    """A step's frame dicts and plans -> (masks [(frame, counts or polygon object index, is a polygon)], ids, the polygon
+    slots' transformed objects and target sizes, boxes or None); None where a ChainPlan meets an RLE slot: the host route.
+    Under ChainPlans the boxes are the annotations' through the chain and a slot whose box is empty gets id -1 (the
+    mapper's box test, here; its mask test on the device)."""
+    listed, ids, objects, sizes, boxes = [], [], [], [], []
+    for f, (fr, p) in enumerate(zip(truths, plan)):
+        polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
+        if chain and any(q is None for q in polys):
+            return None
+        for c, q in zip(fr["gt_rle"], polys):
+            if q is not None:
+                c = len(objects)                               # replaced by the object's run slot after the rasterisation
+                objects.append(augment.transform_polygons(q, p))
+                sizes.append((p.nh, p.nw))
+            listed.append((f, c, q is not None))
+        if chain:
+            boxes.append(augment.chain_boxes(fr["gt_bbox"], p))
+            ids += np.where(augment.boxes_nonempty(boxes[-1]), fr["gt_ids"].numpy(), -1).tolist()
+        else:
+            ids += fr["gt_ids"].tolist()
+    return listed, ids, objects, sizes, np.concatenate(boxes) if boxes else None
 
 
 def augment_step(model, batched_inputs):
@@ -180,30 +179,14 @@ def augment_step(model, batched_inputs):
     layout = batched_inputs[0].get("image_layout", "chw")
     frames = [f for clip in batched_inputs for f in clip["image"]]
     plan = [p for clip in batched_inputs for p in clip["augment"]]
-    # polygon slots: the coordinates through the frame's plan on the host, ONE rasterisation at the targets on the device
-    kinds = {augment.is_chain(p) for p in plan}
-    if len(kinds) != 1:
+    truths = [fr for clip in batched_inputs for fr in clip["instances"]]
+    kinds = {isinstance(p, augment.ChainPlan) for p in plan}
+    chain = kinds == {True}
+    listed = _step_masks(truths, plan, chain) if len(kinds) == 1 else None      # (a step that mixes the kinds: the host route)
+    if listed is None:
         return host_augmented(batched_inputs), None
-    chain = kinds.pop()
-    listed, ids, objects, sizes, boxes, f = [], [], [], [], [], 0
-    for clip in batched_inputs:
-        for fr in clip["instances"]:
-            polys = fr.get("gt_poly") or [None] * len(fr["gt_rle"])
-            if chain and any(q is None for q in polys):        # an RLE slot under a ChainPlan: the host route
-                return host_augmented(batched_inputs), None
-            for c, q in zip(fr["gt_rle"], polys):
-                if q is not None:
-                    c = len(objects)                           # replaced by the object's run slot below
-                    objects.append(augment.transform_polygons(q, plan[f]))
-                    sizes.append((plan[f].nh, plan[f].nw))
-                listed.append((f, c, q is not None))
-            if chain:                                          # the mapper's box test, here; its mask test on the device
-                b = augment.chain_boxes(fr["gt_bbox"], plan[f])
-                boxes.append(b)
-                ids += np.where(augment.boxes_nonempty(b), fr["gt_ids"].numpy(), -1).tolist()
-            else:
-                ids += fr["gt_ids"].tolist()
-            f += 1
+    listed, ids, objects, sizes, boxes = listed
+    # polygon slots: the coordinates through the frame's plan on the host, ONE rasterisation at the targets on the device
     planned = poly_rle.plan_objects(objects, sizes) if objects else None
     if any(clip.get("image_layout", "chw") != layout for clip in batched_inputs) or \
             not augment.applies(frames, plan, model.device, layout, polygons=planned) or \
@@ -215,23 +198,18 @@ def augment_step(model, batched_inputs):
         poly_ends = tables.ends
         listed = [(f, augment.PolyRuns(*tables.slot_rows[c]) if is_poly else c, is_poly) for f, c, is_poly in listed]
     staged = augment.stage_step(frames, plan, [(f, c) for f, c, _ in listed], model.device, layout, ids, poly_ends=poly_ends,
-                                boxes=np.concatenate(boxes) if boxes else None)
+                                boxes=boxes)
     augment.resize_window_bytes(staged)                        # (a chain step's first resample; otherwise nothing)
     pre = augment_staged(staged, model._pixel_stats, model.detr.detr.backbone)
-    masks, boxes, nonempty = augment.augment_masks(staged)
-    if chain:
-        boxes = staged.boxes
+    masks, mask_boxes, nonempty = augment.augment_masks(staged)
+    boxes = staged.boxes if chain else mask_boxes
     gt_ids = torch.where(nonempty, staged.ids, -1).to(torch.int64)
-    views, out, f = staged.mask_views(masks), [], 0
-    for clip in batched_inputs:
-        instances = []
-        for fr in clip["instances"]:
-            first, k = staged.groups[f][:2]
-            instances.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": views[f],
-                              "gt_boxes": boxes[first:first + k], "gt_ids": gt_ids[first:first + k]})
-            f += 1
-        out.append({**clip, "instances": instances})
-    return out, pre
+    views, filled = staged.mask_views(masks), []
+    for fr, gm, (first, k, _, _) in zip(truths, views, staged.groups):
+        filled.append({"gt_classes": fr["gt_classes"], "image_size": fr["image_size"], "gt_masks": gm,
+                       "gt_boxes": boxes[first:first + k], "gt_ids": gt_ids[first:first + k]})
+    filled = iter(filled)
+    return [{**clip, "instances": [next(filled) for _ in clip["instances"]]} for clip in batched_inputs], pre
 
 
 def takes_bytes(frames, device_ingest, device) -> bool:

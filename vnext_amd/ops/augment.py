@@ -7,15 +7,22 @@ draws the random numbers (`vnext_amd/data/clip_mapper.py`); frames cross the bus
 lengths, and a few launches produce (x, mask) and every mask, box and `nonempty` flag.
 
 `FramePlan(x0, y0, cw, ch, nh, nw, flip)`: one frame's draw: the crop window inside the source, the target size, the flip.
-`nearest_table(n_in, n_out) -> int32 [n_out]`: Pillow's `resize(..., NEAREST)` source indices.  Pillow takes its affine path
-for NEAREST and ACCUMULATES in double -- xo = 0.5 * a, then tab[i] = int(xo); xo += a with a = n_in / n_out -- which is not
-`floor((i + 0.5) * n_in / n_out)` (they differ on about a fifth of the size pairs).  Python floats, cached per pair.
+A plan answers for itself: `inside(h, w)`, `resamples()` (the (n_in, n_out) pairs `supported` checks), `coords(xy)` (polygon
+and box coordinates, in float64), `frame(...)` and `mask(dense)` (the host route of one frame and one mask), `truth(masks,
+bboxes)` (a frame's boxes and keep flags); `ChainPlan` below has the same methods, so nothing outside the two asks which
+kind a plan is.
+`nearest_table(n_in, n_out) -> int32 [n_out]` (`resize.nearest_table`): Pillow's `resize(..., NEAREST)` source indices.  Pillow
+takes its affine path for NEAREST and ACCUMULATES in double -- xo = 0.5 * a, then tab[i] = int(xo); xo += a with
+a = n_in / n_out -- which is not `floor((i + 0.5) * n_in / n_out)` (they differ on about a fifth of the size pairs).  Python
+floats, cached per pair.
 `reference_augment_frames(frames, plan, layout)`: numpy slicing, `resize.reference_resize`, `np.flip` -> uint8 frames.
-`reference_augment_masks(masks, sizes, plan)`: `rle_decode`, slicing, the index tables, `np.flip`, then the box as
-`BitMasks.get_bounding_boxes` computes it.  Both are the CPU route of the ops and the oracle of the GPU tests.
-`stage_step(frames, plan, masks, device, layout) -> Staged`: the tables, the coefficients (each distinct bilinear and nearest
-table once), the masks' run END positions (one cumsum each), their rows and ids, and the frame bytes in ONE pinned buffer and
-one `non_blocking` copy.
+`reference_augment_masks(masks, sizes, plan)`: `rle_decode`, slicing, the index tables, `np.flip` (`reference_rle_mask`), then
+the box as `BitMasks.get_bounding_boxes` computes it.  Both are the CPU route of the ops and the oracle of the GPU tests.
+`coeff_words(plan)`, `window_words(words, rows)`: the `coeffs` buffer of a step and the first resamples' tables behind it;
+each distinct bilinear and nearest table once (`resize.CoeffTables`).
+`stage_step(frames, plan, masks, device, layout) -> Staged`: the tables, the coefficients, the masks' run END positions (one
+cumsum each), their rows and ids, and the frame bytes in ONE pinned buffer and one `non_blocking` copy
+(`ingest.pack_upload`): the sources' layout of its kind of plan, the mask rows, the upload.
 `augment_frames(staged, mean, std, channels_last) -> (x, mask)`: one launch; the outputs of `resize.resize_ingest_frames`.
 `augment_masks(staged) -> (masks uint8 [bytes], boxes fp32 [m, 4], nonempty bool [m])`: two launches; `staged.mask_views(masks)`
 gives each frame's bool [n_inst, nh, nw] as a view.
@@ -31,8 +38,9 @@ nearest tables), so ONE `augment_masks` call makes gt_masks, boxes and `nonempty
 
 The COCO pre-training chain: IDOL's `COCO_CLIP_DatasetMapper` applies flip -> resize to (h1, w1) -> crop ->
 resize to (nh, nw), two resamples through a byte-rounded intermediate image.  `ChainPlan` is one frame's draw of it;
-`reference_chain_frames` / `reference_chain_rle_mask` / `chain_boxes` are the literal host route; `transform_polygons` and
-`reference_polygon_mask` take either kind of plan.  `stage_step` takes a step of ChainPlans: a source tensor that is listed
+`ChainPlan.frame` / `mask` / `coords` and `chain_boxes` are the literal host route; `reference_augment_frames` (also under
+the name `reference_chain_frames`), `reference_rle_mask`, `transform_polygons` and `reference_polygon_mask` take either kind
+of plan.  `stage_step` takes a step of ChainPlans: a source tensor that is listed
 more than once is uploaded once, every frame that needs the first resample gets a slot behind the source frames in the SAME
 device allocation, and `resize_window_bytes(staged)` -- one launch of `vnx_resize_window_bytes`, none when no frame needs it --
 fills the slots with the (mirrored, where the frame is flipped) crop window of the resized frame; `augment_frames` then reads a
@@ -42,7 +50,6 @@ window with the flip applied last -- which is what the kernels do, and what the 
 """
 from __future__ import annotations
 
-import functools
 from typing import NamedTuple
 
 import numpy as np
@@ -57,7 +64,22 @@ BYTES_CALLS = {"resize_window_bytes": 0}               # (a dict of its own: tes
 SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS, WIN_WORDS = 8, 8, 4, 16
 
 
+nearest_table = resize.nearest_table
+
+
+def _window(a, p, ah: int, aw: int):
+    """the plan's crop window {x0, y0, cw, ch} of an array whose rows and columns are axes (ah, aw)"""
+    sl = [slice(None)] * a.ndim
+    sl[ah], sl[aw] = slice(p.y0, p.y0 + p.ch), slice(p.x0, p.x0 + p.cw)
+    return np.ascontiguousarray(a[tuple(sl)])
+
+
+def _window_inside(p, h: int, w: int) -> bool:
+    return p.x0 >= 0 and p.y0 >= 0 and p.cw >= 1 and p.ch >= 1 and p.x0 + p.cw <= w and p.y0 + p.ch <= h
+
+
 class FramePlan(NamedTuple):
+    """One frame's draw of crop -> resize -> flip: the window {x0, y0, cw, ch} inside the source, the target, the flip"""
     x0: int
     y0: int
     cw: int
@@ -65,6 +87,41 @@ class FramePlan(NamedTuple):
     nh: int
     nw: int
     flip: bool
+
+    def inside(self, h: int, w: int) -> bool:
+        """the window lies inside a source of h x w"""
+        return _window_inside(self, h, w)
+
+    def resamples(self):
+        """the (n_in, n_out) pairs the kernels resample, horizontal first"""
+        return [(self.cw, self.nw), (self.ch, self.nh)]
+
+    def coords(self, xy):
+        """flat float64 [x, y, x, y, ...] (changed in place) in the reference's order and with its expressions: crop
+        `x -= x0, y -= y0`; resize `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)` (ResizeTransform.apply_coords); flip
+        `x = nw - x` (HFlipTransform.apply_coords)"""
+        xy[0::2] -= self.x0
+        xy[1::2] -= self.y0
+        xy[0::2] = xy[0::2] * (self.nw * 1.0 / self.cw)
+        xy[1::2] = xy[1::2] * (self.nh * 1.0 / self.ch)
+        if self.flip:
+            xy[0::2] = self.nw - xy[0::2]
+        return xy
+
+    def frame(self, a, ah: int, aw: int, layout: str):
+        """a uint8 source array -> the augmented one: slicing, `resize.reference_resize`, `np.flip`"""
+        a = resize.reference_resize(_window(a, self, ah, aw), self.nh, self.nw, layout)
+        return np.flip(a, axis=aw) if self.flip else a
+
+    def mask(self, dense):
+        """a bool [h, w] mask at the source size -> bool [nh, nw]: slicing, the index tables, `np.flip`"""
+        m = _window(dense, self, 0, 1)[nearest_table(self.ch, self.nh)][:, nearest_table(self.cw, self.nw)]
+        return np.flip(m, axis=1) if self.flip else m
+
+    def truth(self, masks, bboxes=None):
+        """a frame's augmented masks -> (their boxes float32 [n, 4] as `BitMasks.get_bounding_boxes` computes them, the
+        instances `filter_empty_instances` keeps bool [n]); the annotations' boxes are not read"""
+        return mask_boxes(masks)
 
 
 class ChainPlan(NamedTuple):
@@ -93,14 +150,55 @@ class ChainPlan(NamedTuple):
         """the window's origin in the UNFLIPPED resized image"""
         return self.w1 - self.x0 - self.cw if self.flip else self.x0
 
+    def inside(self, h: int, w: int) -> bool:
+        """the plan is of THIS frame (h x w), and its window lies inside the resized image"""
+        return (self.h, self.w) == (h, w) and min(self.h1, self.w1, self.nh, self.nw) >= 1 and \
+            _window_inside(self, self.h1, self.w1)
+
+    def resamples(self):
+        """the (n_in, n_out) pairs the kernels resample: the first resize (where it exists), then the second"""
+        first = [(self.w, self.w1), (self.h, self.h1)] if self.resamples_twice else []
+        return first + [(self.cw, self.nw), (self.ch, self.nh)]
+
+    def coords(self, xy):
+        """flat float64 [x, y, x, y, ...] (changed in place) in the reference's order and with its expressions:
+        `x = w - x` on a flip (HFlipTransform.apply_coords); `x * (w1 * 1.0 / w), y * (h1 * 1.0 / h)`
+        (ResizeTransform.apply_coords); `x -= x0, y -= y0` (CropTransform); `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`"""
+        if self.flip:
+            xy[0::2] = self.w - xy[0::2]
+        xy[0::2] = xy[0::2] * (self.w1 * 1.0 / self.w)
+        xy[1::2] = xy[1::2] * (self.h1 * 1.0 / self.h)
+        xy[0::2] -= self.x0
+        xy[1::2] -= self.y0
+        xy[0::2] = xy[0::2] * (self.nw * 1.0 / self.cw)
+        xy[1::2] = xy[1::2] * (self.nh * 1.0 / self.ch)
+        return xy
+
+    def frame(self, a, ah: int, aw: int, layout: str):
+        """a uint8 source array through the chain in the LITERAL order: `np.flip`, `resize.reference_resize` to (h1, w1),
+        slicing, `resize.reference_resize` to (nh, nw)"""
+        if self.flip:
+            a = np.ascontiguousarray(np.flip(a, axis=aw))
+        a = resize.reference_resize(a, self.h1, self.w1, layout)
+        return resize.reference_resize(_window(a, self, ah, aw), self.nh, self.nw, layout)
+
+    def mask(self, dense):
+        """a bool [h, w] mask at the source size as the reference's `apply_segmentation` does it: `np.flip`, Pillow's
+        NEAREST to (h1, w1), slicing, NEAREST to (nh, nw) -> bool [nh, nw]"""
+        m = np.flip(dense, axis=1) if self.flip else dense
+        m = _window(m[nearest_table(self.h, self.h1)][:, nearest_table(self.w, self.w1)], self, 0, 1)
+        return m[nearest_table(self.ch, self.nh)][:, nearest_table(self.cw, self.nw)]
+
+    def truth(self, masks, bboxes):
+        """a frame's augmented masks and its annotations' boxes (XYXY) -> (`chain_boxes`, the instances the mapper keeps:
+        the box AND the mask are not empty)"""
+        boxes = chain_boxes(bboxes, self)
+        return boxes, boxes_nonempty(boxes) & np.array([bool(m.any()) for m in masks], dtype=bool)
+
 
 def chain_full(h: int, w: int, nh: int, nw: int, flip: bool = False) -> ChainPlan:
     """the side of the coin without a crop: flip, one resize"""
     return ChainPlan(int(h), int(w), bool(flip), int(h), int(w), 0, 0, int(w), int(h), int(nh), int(nw))
-
-
-def is_chain(p) -> bool:
-    return isinstance(p, ChainPlan)
 
 
 class PolyRuns(NamedTuple):
@@ -114,98 +212,36 @@ def full_plan(h: int, w: int, nh: int, nw: int, flip: bool = False) -> FramePlan
     return FramePlan(0, 0, int(w), int(h), int(nh), int(nw), bool(flip))
 
 
-@functools.lru_cache(maxsize=256)
-def _nearest(n_in: int, n_out: int):
-    a = n_in / n_out
-    xo = a * 0.5
-    tab = np.empty(n_out, dtype=np.int32)
-    for i in range(n_out):
-        tab[i] = int(xo)
-        xo += a
-    np.minimum(tab, n_in - 1, out=tab)      # (Pillow skips a sample outside the image; none is on these tables)
-    tab.setflags(write=False)
-    return tab
-
-
-def nearest_table(n_in: int, n_out: int):
-    """-> int32 [n_out], read-only, cached per (n_in, n_out); see the module docstring"""
-    return _nearest(int(n_in), int(n_out))
-
-
-def _inside(p, h: int, w: int) -> bool:
-    if is_chain(p):      # the plan is of THIS frame, and its window lies inside the resized image
-        return (p.h, p.w) == (h, w) and min(p.h1, p.w1, p.nh, p.nw) >= 1 and \
-            _inside(FramePlan(p.x0, p.y0, p.cw, p.ch, p.nh, p.nw, p.flip), p.h1, p.w1)
-    return p.x0 >= 0 and p.y0 >= 0 and p.cw >= 1 and p.ch >= 1 and p.x0 + p.cw <= w and p.y0 + p.ch <= h
-
-
 # ---- the CPU route and oracle -----------------------------------------------------------------------------------------------
 def reference_augment_frames(frames, plan, layout: str = "chw"):
-    """uint8 frames (tensors or arrays of `layout`) -> the cropped, resized and flipped frames, same kind and layout"""
+    """uint8 frames (tensors or arrays of `layout`) -> each through its plan's `frame` (a FramePlan: cropped, resized and
+    flipped; a ChainPlan: the chain in its literal order), same kind and layout.  The CPU route of the ops and the oracle of
+    the GPU tests."""
     ah, aw = resize._hw_axes(layout)
     out = []
     for f, p in zip(frames, plan):
         is_tensor = torch.is_tensor(f)
         a = f.detach().cpu().numpy() if is_tensor else np.asarray(f)
-        assert _inside(p, a.shape[ah], a.shape[aw])
-        sl = [slice(None)] * 3
-        sl[ah], sl[aw] = slice(p.y0, p.y0 + p.ch), slice(p.x0, p.x0 + p.cw)
-        a = resize.reference_resize(np.ascontiguousarray(a[tuple(sl)]), p.nh, p.nw, layout)
-        if p.flip:
-            a = np.flip(a, axis=aw)
-        a = np.ascontiguousarray(a)
+        assert p.inside(a.shape[ah], a.shape[aw])
+        a = np.ascontiguousarray(p.frame(a, ah, aw, layout))
         out.append(torch.from_numpy(a) if is_tensor else a)
     return out
 
 
-def chain_coords(xy, p: ChainPlan):
-    """flat float64 [x, y, x, y, ...] (changed in place) through a ChainPlan, in the reference's order and with its
-    expressions: `x = w - x` on a flip (HFlipTransform.apply_coords); `x * (w1 * 1.0 / w), y * (h1 * 1.0 / h)`
-    (ResizeTransform.apply_coords); `x -= x0, y -= y0` (CropTransform); `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`"""
-    if p.flip:
-        xy[0::2] = p.w - xy[0::2]
-    xy[0::2] = xy[0::2] * (p.w1 * 1.0 / p.w)
-    xy[1::2] = xy[1::2] * (p.h1 * 1.0 / p.h)
-    xy[0::2] -= p.x0
-    xy[1::2] -= p.y0
-    xy[0::2] = xy[0::2] * (p.nw * 1.0 / p.cw)
-    xy[1::2] = xy[1::2] * (p.nh * 1.0 / p.ch)
-    return xy
+reference_chain_frames = reference_augment_frames      # (the name the chain's tests and callers use)
 
 
-def reference_chain_frames(frames, plan, layout: str = "chw"):
-    """uint8 frames (tensors or arrays of `layout`) through their ChainPlans in the LITERAL order: `np.flip`,
-    `resize.reference_resize` to (h1, w1), slicing, `resize.reference_resize` to (nh, nw) -> frames of the same kind and
-    layout.  The CPU route of the chain and the oracle of the GPU tests."""
-    ah, aw = resize._hw_axes(layout)
-    out = []
-    for f, p in zip(frames, plan):
-        is_tensor = torch.is_tensor(f)
-        a = f.detach().cpu().numpy() if is_tensor else np.asarray(f)
-        assert _inside(p, a.shape[ah], a.shape[aw])
-        if p.flip:
-            a = np.ascontiguousarray(np.flip(a, axis=aw))
-        a = resize.reference_resize(a, p.h1, p.w1, layout)
-        sl = [slice(None)] * 3
-        sl[ah], sl[aw] = slice(p.y0, p.y0 + p.ch), slice(p.x0, p.x0 + p.cw)
-        a = np.ascontiguousarray(resize.reference_resize(np.ascontiguousarray(a[tuple(sl)]), p.nh, p.nw, layout))
-        out.append(torch.from_numpy(a) if is_tensor else a)
-    return out
-
-
-def reference_chain_rle_mask(counts, p: ChainPlan):
-    """One RLE mask (COCO counts at the source size) through a ChainPlan as the reference's `apply_segmentation` does it:
-    `np.flip`, Pillow's NEAREST to (h1, w1), slicing, NEAREST to (nh, nw) -> bool [nh, nw].  Host route only."""
+def _dense(counts, h: int, w: int):
+    """COCO counts -> bool [h, w]; counts that do not sum to h * w, or a negative one, are the empty mask"""
     counts = [int(c) for c in counts]
-    if sum(counts) == p.h * p.w and min(counts) >= 0:
-        m = rle_decode({"size": [p.h, p.w], "counts": counts_to_string(counts)}).astype(bool)
-    else:
-        m = np.zeros((p.h, p.w), dtype=bool)
-    if p.flip:
-        m = np.flip(m, axis=1)
-    m = m[nearest_table(p.h, p.h1)][:, nearest_table(p.w, p.w1)]
-    m = m[p.y0:p.y0 + p.ch, p.x0:p.x0 + p.cw]
-    return np.ascontiguousarray(m[nearest_table(p.ch, p.nh)][:, nearest_table(p.cw, p.nw)])
+    if sum(counts) == h * w and min(counts) >= 0:
+        return rle_decode({"size": [h, w], "counts": counts_to_string(counts)}).astype(bool)
+    return np.zeros((h, w), dtype=bool)
+
+
+def reference_rle_mask(counts, size, p):
+    """One RLE mask (COCO counts at the source `size` = (h, w)) through a plan of either kind (`p.mask`) -> bool [nh, nw]"""
+    return np.ascontiguousarray(p.mask(_dense(counts, *size)))
 
 
 def chain_boxes(bboxes, p: ChainPlan):
@@ -216,7 +252,7 @@ def chain_boxes(bboxes, p: ChainPlan):
     if b.shape[0] == 0:
         return np.zeros((0, 4), dtype=np.float32)
     corners = b[:, [0, 1, 2, 1, 0, 3, 2, 3]].reshape(-1)       # (x0, y0), (x1, y0), (x0, y1), (x1, y1), box by box
-    xy = chain_coords(corners.copy(), p).reshape(-1, 4, 2)
+    xy = p.coords(corners.copy()).reshape(-1, 4, 2)
     lo, hi = xy.min(axis=1), xy.max(axis=1)
     out = np.concatenate((lo, hi), axis=1).clip(min=0)
     return np.minimum(out, np.array([p.nw, p.nh, p.nw, p.nh], dtype=np.float64)).astype(np.float32)
@@ -230,24 +266,11 @@ def boxes_nonempty(boxes, threshold: float = 1e-5):
 
 def transform_polygons(segmentation, p):
     """One annotation's polygons (or boxes, as their 4-vertex polygons) through the frame's plan, in float64 and in the
-    reference's order: crop `x -= x0, y -= y0`; resize `x * (nw * 1.0 / cw), y * (nh * 1.0 / ch)`
-    (ResizeTransform.apply_coords); flip `x = nw - x` (HFlipTransform.apply_coords) -- or, for a ChainPlan, `chain_coords`:
-    flip, resize, crop, resize.  The shifted polygon is NOT clipped to the window (the reference clips with shapely first,
-    which is not installed): the rasteriser drops columns outside the canvas and clamps rows.
+    reference's order (`FramePlan.coords`: crop, resize, flip; `ChainPlan.coords`: flip, resize, crop, resize).  The shifted
+    polygon is NOT clipped to the window (the reference clips with shapely first, which is not installed): the rasteriser
+    drops columns outside the canvas and clamps rows.
     -> a list of flat float64 polygons for a canvas of nh x nw."""
-    if is_chain(p):
-        return [chain_coords(poly.copy(), p) for poly in poly_rle.object_polygons(segmentation)]
-    out = []
-    for poly in poly_rle.object_polygons(segmentation):
-        xy = poly.copy()
-        xy[0::2] -= p.x0
-        xy[1::2] -= p.y0
-        xy[0::2] = xy[0::2] * (p.nw * 1.0 / p.cw)
-        xy[1::2] = xy[1::2] * (p.nh * 1.0 / p.ch)
-        if p.flip:
-            xy[0::2] = p.nw - xy[0::2]
-        out.append(xy)
-    return out
+    return [p.coords(poly.copy()) for poly in poly_rle.object_polygons(segmentation)]
 
 
 def reference_polygon_mask(segmentation, p):
@@ -264,42 +287,33 @@ def mask_box(m):
     return np.array([xs[0], ys[0], xs[-1] + 1, ys[-1] + 1], dtype=np.float32), True
 
 
+def mask_boxes(masks):
+    """`mask_box` of each -> (boxes float32 [m, 4], nonempty bool [m])"""
+    found = [mask_box(m) for m in masks]
+    return (np.array([b for b, _ in found], dtype=np.float32).reshape(len(masks), 4),
+            np.array([k for _, k in found], dtype=bool))
+
+
 def reference_augment_masks(masks, sizes, plan):
     """masks: [(frame index, COCO counts)]; sizes: the frames' source (h, w); plan: the frames' FramePlan
     -> ([bool array [nh, nw] per mask], boxes float32 [m, 4], nonempty bool [m]).  Counts that do not sum to h * w are the
     empty mask."""
-    outs, boxes, flags = [], np.zeros((len(masks), 4), dtype=np.float32), np.zeros(len(masks), dtype=bool)
-    for i, (f, counts) in enumerate(masks):
-        (h, w), p = sizes[f], plan[f]
-        counts = [int(c) for c in counts]
-        if sum(counts) == h * w and min(counts) >= 0:
-            dense = rle_decode({"size": [h, w], "counts": counts_to_string(counts)}).astype(bool)
-        else:
-            dense = np.zeros((h, w), dtype=bool)
-        crop = dense[p.y0:p.y0 + p.ch, p.x0:p.x0 + p.cw]
-        m = crop[nearest_table(p.ch, p.nh)][:, nearest_table(p.cw, p.nw)]
-        if p.flip:
-            m = np.flip(m, axis=1)
-        m = np.ascontiguousarray(m)
-        outs.append(m)
-        boxes[i], flags[i] = mask_box(m)
-    return outs, boxes, flags
+    outs = [reference_rle_mask(counts, sizes[f], plan[f]) for f, counts in masks]
+    return (outs, *mask_boxes(outs))
 
 
 # ---- staging ----------------------------------------------------------------------------------------------------------------
 def supported(p) -> bool:
-    """both resamples of a ChainPlan, the one of a FramePlan, are in the kernel's range"""
-    if is_chain(p) and p.resamples_twice and not resize.supported(p.h, p.w, p.h1, p.w1):
-        return False
-    return resize.supported(p.ch, p.cw, p.nh, p.nw)
+    """every resample of the plan (both of a ChainPlan, the one of a FramePlan) is in the kernel's range"""
+    return all(resize.axis_supported(n_in, n_out) for n_in, n_out in p.resamples())
 
 
 def applies(frames, plan, device, layout: str = "chw", polygons=None) -> bool:
-    """All frames are uint8 CPU tensors of `layout`, every window lies inside its frame and every (window, target) pair is in
-    the kernel's range; polygons: (objects, sizes) of the step's transformed polygon masks, or what
-    `poly_rle.plan_objects` made of them -- every one inside the caps of vnx_poly_rle"""
+    """All frames are uint8 CPU tensors of `layout`, the plans are of one kind, every window lies inside its frame and every
+    (window, target) pair is in the kernel's range; polygons: (objects, sizes) of the step's transformed polygon masks, or
+    what `poly_rle.plan_objects` made of them -- every one inside the caps of vnx_poly_rle"""
     ah, aw = resize._hw_axes(layout)
-    if not frames or len(frames) != len(plan) or len({is_chain(p) for p in plan}) > 1:
+    if not frames or len(frames) != len(plan) or len({type(p) for p in plan}) > 1:
         return False
     if polygons is not None:
         fits = polygons[2] if len(polygons) == 3 else poly_rle.plan_objects(*polygons)[2]
@@ -308,54 +322,39 @@ def applies(frames, plan, device, layout: str = "chw", polygons=None) -> bool:
     for f, p in zip(frames, plan):
         if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[3 - ah - aw] == 3 and not f.is_cuda):
             return False
-        if not (_inside(p, f.shape[ah], f.shape[aw]) and supported(p)):
+        if not (p.inside(f.shape[ah], f.shape[aw]) and supported(p)):
             return False
     return True
 
 
 def padded_size(plan):
-    return resize.padded_size([(p.nh, p.nw) for p in plan])
+    return ingest.padded_hw([(p.nh, p.nw) for p in plan])
 
 
-def _coeff_words(plan):
-    """the `coeffs` buffer of a step as one int32 array: a row of 8 per frame, then each distinct bilinear table and each
-    distinct nearest table once"""
-    n = len(plan)
-    head = np.zeros((n, COEFF_WORDS), dtype=np.int32)
-    parts, at, bil, near = [], COEFF_WORDS * n, {}, {}
-    for i, p in enumerate(plan):
+def coeff_words(plan):
+    """the `coeffs` buffer of a step as one int32 array: a row of 8 per frame ({bounds offset, weights offset, ksize} x
+    {horizontal, vertical}, then the two nearest tables' offsets), then each distinct bilinear and nearest table once"""
+    tables = resize.CoeffTables(COEFF_WORDS * len(plan))
+    rows = np.zeros((len(plan), COEFF_WORDS), dtype=np.int32)
+    for row, p in zip(rows, plan):
         for j, pair in enumerate(((p.cw, p.nw), (p.ch, p.nh))):
-            if pair[0] != pair[1]:           # else ksize 0: the pass is skipped
-                if pair not in bil:
-                    bounds, kk = resize.pillow_coeffs(*pair)
-                    bil[pair] = (at, at + bounds.size, kk.shape[1])
-                    parts += [bounds.reshape(-1), kk.reshape(-1)]
-                    at += bounds.size + kk.size
-                head[i, 3 * j:3 * j + 3] = bil[pair]
-            if pair not in near:
-                near[pair] = at
-                parts.append(nearest_table(*pair))
-                at += pair[1]
-            head[i, 6 + j] = near[pair]
-    return np.concatenate([head.reshape(-1)] + parts)
+            row[3 * j:3 * j + 3] = tables.bilinear(*pair)
+            row[6 + j] = tables.nearest(*pair)
+    return tables.words(rows)
 
 
-def _window_words(words, win):
+def window_words(words, win):
     """`resize_window_bytes`' rows (lists of 16, the triples still zero) and a step's `coeffs` words -> (the words with each
     distinct table of (w -> w1) and (h -> h1) appended once, int32 [k, 16] rows that name them)"""
     win = np.asarray(win, dtype=np.int32).reshape(-1, WIN_WORDS)
-    parts, at, placed = [words], int(words.size), {}
+    tables = resize.CoeffTables(words.size)
     for row in win:
-        for j, pair in enumerate(((int(row[2]), int(row[4])), (int(row[1]), int(row[3])))):
-            if pair[0] == pair[1]:
-                continue                     # ksize 0: the pass is skipped
-            if pair not in placed:
-                bounds, kk = resize.pillow_coeffs(*pair)
-                placed[pair] = (at, at + bounds.size, kk.shape[1])
-                parts += [bounds.reshape(-1), kk.reshape(-1)]
-                at += bounds.size + kk.size
-            row[10 + 3 * j:13 + 3 * j] = placed[pair]
-    return np.concatenate(parts), win
+        row[10:13] = tables.bilinear(int(row[2]), int(row[4]))
+        row[13:16] = tables.bilinear(int(row[1]), int(row[3]))
+    return tables.words(words), win
+
+
+_coeff_words, _window_words = coeff_words, window_words      # (their names while private: callers written against them keep working)
 
 
 class Staged(NamedTuple):
@@ -370,11 +369,11 @@ class Staged(NamedTuple):
     layout: str
     mask_bytes: int
     groups: tuple               # per frame (first mask, masks, nh, nw): the masks of a frame are consecutive
-    mask_src: object = None     # with polygon masks: src_table / dst_table of the frames AND the pseudo-frames (the rows
-    mask_dst: object = None     # mask_rows index); src_table and dst_table above are their first n rows
-    win_table: object = None    # a step of ChainPlans: int32 [k, 16], the rows of `resize_window_bytes` (k may be 0)
-    win_size: tuple = None      # (H1, W1) that launch is padded to
-    boxes: object = None        # fp32 [m, 4]: the masks' boxes where the caller computed them (`chain_boxes`)
+    mask_src: torch.Tensor      # src_table / dst_table of the frames AND the pseudo-frames of polygon masks (the rows
+    mask_dst: torch.Tensor      # mask_rows index); src_table and dst_table above are their first n rows
+    win_table: torch.Tensor     # int32 [k, 16], the rows of `resize_window_bytes`: k = 0 unless a step of ChainPlans needs it
+    win_size: tuple             # (H1, W1) that launch is padded to
+    boxes: object = None        # a step of ChainPlans: fp32 [m, 4], the masks' boxes the caller computed (`chain_boxes`)
 
     def mask_views(self, masks):
         """the flat output of `augment_masks` -> per frame bool [n_inst, nh, nw] (views)"""
@@ -385,6 +384,66 @@ class Staged(NamedTuple):
         return out
 
 
+def _frame_sources(frames, sizes, plan):
+    """a step of FramePlans -> (src rows, [(tensor, byte offset)], source bytes, window rows, slot bytes): every frame at
+    the next 16-byte offset, its window in its row"""
+    src, off = np.zeros((len(plan), SRC_WORDS), dtype=np.int32), 0
+    for row, (h, w), p in zip(src, sizes, plan):
+        row[:] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
+        off += ingest._align16(3 * h * w)
+    return src, list(zip(frames, src[:, 0].tolist())), off, [], 0
+
+
+def _chain_sources(frames, sizes, plan):
+    """a step of ChainPlans -> the same: a source listed twice (the pair of one image) is placed once; a frame that is
+    resampled twice gets a window row and a slot behind the sources, which its src row then names as its source"""
+    placed, off = {}, 0
+    for f, (h, w) in zip(frames, sizes):
+        if id(f) not in placed:
+            placed[id(f)] = (f, off)
+            off += ingest._align16(3 * h * w)
+    src, win, slot = np.zeros((len(plan), SRC_WORDS), dtype=np.int32), [], off
+    for row, f, (h, w), p in zip(src, frames, sizes, plan):
+        assert p.inside(h, w), "stage_step: a ChainPlan of another frame, or a window outside (h1, w1)"
+        at = placed[id(f)][1]
+        if p.resamples_twice:                # the window of the unflipped resized frame -> its slot; the flip comes last
+            win.append([at, h, w, p.h1, p.w1, p.mirrored_x0, p.y0, p.cw, p.ch, slot] + [0] * 6)
+            row[:] = (slot, p.ch, p.cw, 0, 0, p.cw, p.ch, int(p.flip))
+            slot += ingest._align16(3 * p.ch * p.cw)
+        else:                                # one resample: the (mirrored) window of the source itself
+            row[:] = (at, h, w, p.mirrored_x0, p.y0, p.cw, p.ch, int(p.flip))
+    return src, list(placed.values()), off, win, slot - off
+
+
+def _mask_rows(masks, plan):
+    """-> (mask rows int32 [m, 4], the staged run ends, groups, {frame: row of its pseudo-frame}, the output's bytes); a
+    PolyRuns mask names its pseudo-frame, and its ends offset counts from the END of the staged ones"""
+    n = len(plan)
+    rows, ends, e_at, o_at = np.zeros((len(masks), MASK_ROW_WORDS), dtype=np.int32), [], 0, 0
+    groups, pseudo, last = [[0, 0, p.nh, p.nw] for p in plan], {}, -1
+    for i, (f, counts) in enumerate(masks):
+        assert f >= last, "stage_step: the masks of a frame are consecutive, the frames ascending"
+        if f != last:
+            groups[f][0] = i
+        last = f
+        groups[f][1] += 1
+        if isinstance(counts, PolyRuns):
+            rows[i] = (counts.offset, counts.size, pseudo.setdefault(f, n + len(pseudo)), o_at)
+        else:
+            e = np.cumsum(np.asarray(counts, dtype=np.int64))
+            assert e.size >= 1 and e[-1] <= 0x7fffffff
+            rows[i] = (e_at, e.size, f, o_at)
+            ends.append(e.astype(np.int32))
+            e_at += e.size
+        o_at += plan[f].nh * plan[f].nw
+    ends = np.concatenate(ends) if ends else np.zeros(1, dtype=np.int32)
+    rows[rows[:, 2] >= n, 0] += ends.size    # the device-resident ends follow the staged ones
+    return rows, ends, tuple(tuple(g) for g in groups), pseudo, int(o_at)
+
+
+_SOURCES = {FramePlan: (_frame_sources, False), ChainPlan: (_chain_sources, True)}      # (layout, the boxes ride along)
+
+
 def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_ends=None, boxes=None) -> Staged:
     """frames: uint8 CPU tensors of `layout`; plan: a FramePlan per frame; masks: [(frame index, COCO counts)] with the masks
     of a frame CONSECUTIVE and the frames ascending; ids: the masks' instance ids (default 0).  A mask may be a
@@ -393,95 +452,30 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_
     masks' boxes, fp32 [m, 4], packed into the same upload).  See the module docstring."""
     device = torch.device(device)
     n, m = len(frames), len(masks)
-    sizes = [resize.frame_size(f, layout) for f in frames]
-    pseudo = {}                              # frame -> the row of its pseudo-frame
-    for f, counts in masks:
-        if isinstance(counts, PolyRuns):
-            pseudo.setdefault(f, n + len(pseudo))
+    kinds = {type(p) for p in plan} or {FramePlan}
+    assert len(kinds) == 1, "stage_step: ChainPlans or FramePlans, not both"
+    sources, with_boxes = _SOURCES[kinds.pop()]
+    src, uploads, nbytes, win, slots = sources(frames, [resize.frame_size(f, layout) for f in frames], plan)
+    rows, ends, groups, pseudo, mask_bytes = _mask_rows(masks, plan)
     assert not pseudo or (poly_ends is not None and poly_ends.is_cuda and device.type == "cuda"), \
         "stage_step: polygon masks take device-resident run ends"
-    src, off = np.zeros((n + len(pseudo), SRC_WORDS), dtype=np.int32), 0
-    chain = bool(plan) and is_chain(plan[0])
-    assert all(is_chain(p) == chain for p in plan), "stage_step: ChainPlans or FramePlans, not both"
-    win, uploads = [], list(zip(frames, [0] * n))      # uploads: (frame, byte offset), each distinct tensor once
-    if not chain:
-        for i, ((h, w), p) in enumerate(zip(sizes, plan)):
-            src[i] = (off, h, w, p.x0, p.y0, p.cw, p.ch, int(p.flip))
-            uploads[i] = (frames[i], off)
-            off += ingest._align16(3 * h * w)
-    else:
-        placed = {}                              # a source listed twice (the pair of one image) is uploaded once
-        for f, (h, w) in zip(frames, sizes):
-            if id(f) not in placed:
-                placed[id(f)] = off
-                off += ingest._align16(3 * h * w)
-        uploads, slot = [(f, placed[id(f)]) for f in {id(f): f for f in frames}.values()], off
-        for i, ((h, w), p) in enumerate(zip(sizes, plan)):
-            assert _inside(p, h, w), "stage_step: a ChainPlan of another frame, or a window outside (h1, w1)"
-            if p.resamples_twice:                # the window of the unflipped resized frame -> its slot; the flip comes last
-                win.append([placed[id(frames[i])], h, w, p.h1, p.w1, p.mirrored_x0, p.y0, p.cw, p.ch, slot] + [0] * 6)
-                src[i] = (slot, p.ch, p.cw, 0, 0, p.cw, p.ch, int(p.flip))
-                slot += ingest._align16(3 * p.ch * p.cw)
-            else:                                # one resample: the (mirrored) window of the source itself
-                src[i] = (placed[id(frames[i])], h, w, p.mirrored_x0, p.y0, p.cw, p.ch, int(p.flip))
-    all_plan = list(plan) + [full_plan(plan[f].nh, plan[f].nw, plan[f].nh, plan[f].nw) for f in pseudo]
-    for f, row in pseudo.items():            # the target as its own source; the mask kernel reads no pixels
-        src[row] = (0, plan[f].nh, plan[f].nw, 0, 0, plan[f].nw, plan[f].nh, 0)
-    dst = np.array([(0, p.nh, p.nw) for p in all_plan], dtype=np.int32).reshape(len(all_plan), 3)
-    words = _coeff_words(all_plan)
-    rows, ends, e_at, o_at = np.zeros((m, MASK_ROW_WORDS), dtype=np.int32), [], 0, 0
-    groups, last = [[0, 0, p.nh, p.nw] for p in plan], -1
-    for i, (f, counts) in enumerate(masks):
-        assert f >= last, "stage_step: the masks of a frame are consecutive, the frames ascending"
-        if f != last:
-            groups[f][0] = i
-        last = f
-        groups[f][1] += 1
-        if isinstance(counts, PolyRuns):
-            rows[i] = (counts.offset, counts.size, pseudo[f], o_at)
-            o_at += plan[f].nh * plan[f].nw
-            continue
-        e = np.cumsum(np.asarray(counts, dtype=np.int64))
-        assert e.size >= 1 and e[-1] <= 0x7fffffff
-        rows[i] = (e_at, e.size, f, o_at)
-        ends.append(e.astype(np.int32))
-        e_at += e.size
-        o_at += plan[f].nh * plan[f].nw
-    for g in groups:                         # a frame without masks: its (empty) group starts where the next one does
-        if g[1] == 0:
-            g[0] = 0
-    ends = np.concatenate(ends) if ends else np.zeros(1, dtype=np.int32)
-    if pseudo:                               # the device-resident ends follow the staged ones
-        rows[[i for i, (_, c) in enumerate(masks) if isinstance(c, PolyRuns)], 0] += ends.size
+    # a pseudo-frame: the target as its own source (the full window, no flip); the mask kernel reads no pixels
+    full = [full_plan(plan[f].nh, plan[f].nw, plan[f].nh, plan[f].nw) for f in pseudo]
+    src = np.concatenate([src] + [np.array([(0, p.ch, p.cw, 0, 0, p.cw, p.ch, 0)], dtype=np.int32) for p in full])
+    dst = np.array([(0, p.nh, p.nw) for p in list(plan) + full], dtype=np.int32).reshape(n + len(full), 3)
+    words, win = window_words(coeff_words(list(plan) + full), win)      # the first resample's tables ride behind the others
     idv = np.zeros(m, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(m)
-    small = [src.reshape(-1), dst.reshape(-1), words, ends, rows.reshape(-1), idv]
-    if chain:                                    # the first resample's tables ride behind the others, each distinct one once
-        words, win = _window_words(words, win)
+    ints = [src, dst, words, ends, rows, idv, win]
+    if with_boxes:
         box_bits = np.zeros((m, 4), dtype=np.float32) if boxes is None else np.asarray(boxes, dtype=np.float32).reshape(m, 4)
-        small[2:3] = [words]
-        small += [win.reshape(-1), box_bits.reshape(-1).view(np.int32)]
-    cuts = np.cumsum([0] + [s.size for s in small])
-    head = ingest._align16(4 * int(cuts[-1]))
-    buf = torch.empty(head + off, dtype=torch.uint8, pin_memory=device.type == "cuda")
-    buf[:4 * int(cuts[-1])].view(torch.int32).copy_(torch.from_numpy(np.concatenate(small)))
-    for f, o in uploads:
-        buf[head + o:head + o + f.numel()].view(f.shape).copy_(f)
-    if chain:                                    # the slots follow the source frames in the SAME allocation; nothing of them is uploaded
-        whole = torch.empty(head + slot, dtype=torch.uint8, device=device)
-        whole[:head + off].copy_(buf, non_blocking=True)
-    else:
-        whole = buf.to(device, non_blocking=True)
-    ints = whole[:4 * int(cuts[-1])].view(torch.int32)
-    part = [ints[int(a):int(b)] for a, b in zip(cuts[:-1], cuts[1:])]
-    src_d, dst_d = part[0].view(-1, SRC_WORDS), part[1].view(-1, 3)
-    ends_d = torch.cat((part[3], poly_ends.to(torch.int32))) if pseudo else part[3]
-    extra = ()
-    if chain:
-        extra = (part[6].view(len(win), WIN_WORDS), resize.padded_size([(r[8], r[7]) for r in win.tolist()] or [(1, 1)]),
-                 part[7].view(torch.float32).view(m, 4))
-    return Staged(whole[head:], src_d[:n], dst_d[:n], part[2], ends_d, part[4].view(m, MASK_ROW_WORDS), part[5],
-                  padded_size(plan), layout, int(o_at), tuple(tuple(g) for g in groups),
-                  src_d if pseudo else None, dst_d if pseudo else None, *extra)
+        ints.append(box_bits.view(np.int32))
+    (src_d, dst_d, words_d, ends_d, rows_d, ids_d, win_d, *box_d), pixels = ingest.pack_upload(
+        ints, uploads, nbytes, device, extra=slots)
+    if pseudo:
+        ends_d = torch.cat((ends_d, poly_ends.to(torch.int32)))
+    win_size = ingest.padded_hw([(r[8], r[7]) for r in win.tolist()] or [(1, 1)])
+    return Staged(pixels, src_d[:n], dst_d[:n], words_d, ends_d, rows_d, ids_d, padded_size(plan), layout, mask_bytes, groups,
+                  src_d, dst_d, win_d, win_size, *(b.view(torch.float32) for b in box_d))
 
 
 def _plan_of(staged: Staged):
@@ -495,7 +489,7 @@ def resize_window_bytes(staged: Staged) -> None:
     `staged.pixels` (in place).  One launch on the current stream, before `augment_frames`; none when the step has no such
     frame (or is not a chain step)."""
     win, pixels, layout = staged.win_table, staged.pixels, staged.layout
-    if win is None or win.shape[0] == 0:
+    if win.shape[0] == 0:
         return
     if not pixels.is_cuda:
         ah, aw = resize._hw_axes(layout)
@@ -553,8 +547,7 @@ def augment_masks(staged: Staged):
         return masks, boxes, nonempty
     lib = _lib.lib()
     work = torch.empty(int(lib.vnx_augment_masks_workspace(m, H, W)), dtype=torch.uint8, device=dev)
-    src = staged.src_table if staged.mask_src is None else staged.mask_src
-    dst = staged.dst_table if staged.mask_dst is None else staged.mask_dst
+    src, dst = staged.mask_src, staged.mask_dst
     with torch.cuda.device(dev):
         _lib.check(lib.vnx_augment_masks(
             staged.ends.data_ptr(), staged.ends.numel(), staged.mask_rows.data_ptr(), m, src.data_ptr(),

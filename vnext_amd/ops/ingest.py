@@ -8,6 +8,9 @@ four times the bytes and a chain of small launches per frame and per pyramid lev
 frame's planes 16-byte aligned behind it) and cross the bus in one `non_blocking` copy; the buffer comes from torch's pinned
 allocator, which holds the block back until the copy that reads it has finished.  uint8 frames already on the device: one
 `cat` of their flattened planes and a small table upload.
+`pack_upload(ints, uploads, nbytes, device, extra) -> (int32 views, pixels)`: that one buffer and one copy, for any list of
+int32 tables in front of the frames; `resize.stage_sources` and `augment.stage_step` stage through it as well.
+`padded_hw(sizes) -> (H, W)`: the largest (h, w), rounded up to multiples of 32 -- what `padded_size` of all three ops is.
 `ingest_frames(pixels, table, B, H, W, mean, std, channels_last) -> (x, mask)`: x fp32 [B, 3, H, W] (contiguous or
 channels-last) = (u - mean) / std inside each frame and 0 outside, mask bool [B, H, W] = True outside: one launch, no memset.
 `level_constants(table, B, H, W, level_sizes, num_pos_feats, temperature) -> (masks, poss)`: per level the nearest-resized
@@ -24,6 +27,7 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -40,41 +44,56 @@ def applies(frames, device) -> bool:
                                 and f.numel() > 0 and (not f.is_cuda or f.device == torch.device(device)) for f in frames)
 
 
+def padded_hw(sizes):
+    """(H, W): the largest of the (h, w) `sizes`, rounded up to multiples of 32"""
+    H = max(int(s[0]) for s in sizes)
+    W = max(int(s[1]) for s in sizes)
+    return (H + 31) // 32 * 32, (W + 31) // 32 * 32
+
+
 def padded_size(frames):
     """(H, W): the largest frame, rounded up to multiples of 32"""
-    H = max(f.shape[-2] for f in frames)
-    W = max(f.shape[-1] for f in frames)
-    return (H + 31) // 32 * 32, (W + 31) // 32 * 32
+    return padded_hw([f.shape[-2:] for f in frames])
 
 
 def _align16(n: int) -> int:
     return (n + 15) // 16 * 16
 
 
+def pack_upload(ints, uploads, nbytes: int, device, extra: int = 0):
+    """int32 arrays, [(uint8 tensor, byte offset)] and the byte count of the pixel area -> (the arrays as int32 views on
+    `device`, pixels uint8 [nbytes + extra]).  ONE host buffer -- the arrays back to back, padded to 16 bytes, then every
+    tensor at its offset (the caller keeps them 16-byte aligned) -- pinned for a CUDA device, and ONE `non_blocking` copy.
+    `extra` bytes behind the pixels are allocated on the device in the same block and not uploaded."""
+    device = torch.device(device)
+    cuts = np.cumsum([0] + [a.size for a in ints]).tolist()
+    head = _align16(4 * cuts[-1])
+    buf = torch.empty(head + nbytes, dtype=torch.uint8, pin_memory=device.type == "cuda")
+    buf[:4 * cuts[-1]].view(torch.int32).copy_(torch.from_numpy(np.concatenate([a.reshape(-1) for a in ints])))
+    for f, o in uploads:
+        buf[head + o:head + o + f.numel()].view(f.shape).copy_(f)
+    if extra:
+        whole = torch.empty(head + nbytes + extra, dtype=torch.uint8, device=device)
+        whole[:head + nbytes].copy_(buf, non_blocking=True)
+    else:
+        whole = buf.to(device, non_blocking=True)
+    words = whole[:4 * cuts[-1]].view(torch.int32)
+    return [words[a:b].view(arr.shape) for arr, a, b in zip(ints, cuts[:-1], cuts[1:])], whole[head:]
+
+
 def stage_frames(frames, device):
     """uint8 [3, h, w] frames -> (pixels uint8 [bytes], table int32 [n, 3]) on `device`; see the module docstring."""
-    device = torch.device(device)
-    n = len(frames)
-    if frames[0].is_cuda:
-        sizes = [3 * f.shape[-2] * f.shape[-1] for f in frames]
-        rows, off = [], 0
-        for f, s in zip(frames, sizes):
-            rows.append((off, f.shape[-2], f.shape[-1]))
-            off += s
-        pixels = torch.cat([f.reshape(-1) for f in frames])
-        host = torch.tensor(rows, dtype=torch.int32).pin_memory()
-        return pixels, host.to(device, non_blocking=True)
-    head = _align16(12 * n)
+    on_device = frames[0].is_cuda
     rows, off = [], 0
     for f in frames:
         rows.append((off, f.shape[-2], f.shape[-1]))
-        off += _align16(3 * f.shape[-2] * f.shape[-1])
-    buf = torch.empty(head + off, dtype=torch.uint8, pin_memory=device.type == "cuda")
-    buf[:12 * n].view(torch.int32).view(n, 3).copy_(torch.tensor(rows, dtype=torch.int32))
-    for f, (o, h, w) in zip(frames, rows):
-        buf[head + o:head + o + 3 * h * w].view(3, h, w).copy_(f)
-    dev = buf.to(device, non_blocking=True)
-    return dev[head:], dev[:12 * n].view(torch.int32).view(n, 3)
+        off += f.numel() if on_device else _align16(f.numel())
+    table = np.array(rows, dtype=np.int32)
+    if on_device:
+        pixels = torch.cat([f.reshape(-1) for f in frames])
+        return pixels, torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+    (table,), pixels = pack_upload([table], [(f, o) for f, (o, _, _) in zip(frames, rows)], off, device)
+    return pixels, table
 
 
 def closed_form_embeds(h: int, w: int, vh: int, vw: int):

@@ -7,6 +7,11 @@ coefficient tables, restated here:
 `shortest_edge_size(h, w, short, max_size) -> (nh, nw)`: the target size, in Python floats as the reference computes it.
 `pillow_coeffs(n_in, n_out) -> (bounds int32 [n_out, 2], kk int32 [n_out, ksize])`: per output index the first source index and
 the tap count, and the taps' weights in 22-bit fixed point -- out of IEEE double arithmetic, cached per (n_in, n_out).
+`nearest_table(n_in, n_out) -> int32 [n_out]`: Pillow's NEAREST source indices, what `ops.augment` resamples masks with.
+`CoeffTables(first)`: the builder of every `coeffs` buffer -- `bilinear(n_in, n_out) -> (bounds offset, weights offset, ksize)`
+((0, 0, 0) where the axis keeps its size), `nearest(n_in, n_out) -> offset`, each distinct table placed once, `words(front)`
+the finished buffer; `coeff_words(sizes, targets)` writes this op's 6-word rows with it, `augment.coeff_words` and
+`augment.window_words` theirs.
 `reference_resize(frame_u8, nh, nw, layout)`: the two passes by numpy on the CPU (horizontal first, rounded to uint8, then
 vertical; a pass whose axis keeps its size is skipped).  It is the CPU route of the op and the oracle of the GPU tests; Pillow
 is not imported.
@@ -94,6 +99,56 @@ def pillow_coeffs(n_in: int, n_out: int):
     return _coeffs(int(n_in), int(n_out))
 
 
+@functools.lru_cache(maxsize=256)
+def _nearest(n_in: int, n_out: int):
+    a = n_in / n_out
+    xo = a * 0.5
+    tab = np.empty(n_out, dtype=np.int32)
+    for i in range(n_out):
+        tab[i] = int(xo)
+        xo += a
+    np.minimum(tab, n_in - 1, out=tab)      # (Pillow skips a sample outside the image; none is on these tables)
+    tab.setflags(write=False)
+    return tab
+
+
+def nearest_table(n_in: int, n_out: int):
+    """-> int32 [n_out], read-only, cached per (n_in, n_out): Pillow's `resize(..., NEAREST)` source indices (what the masks
+    of `ops.augment` are resampled with; see its module docstring)"""
+    return _nearest(int(n_in), int(n_out))
+
+
+class CoeffTables:
+    """The tables behind the rows of a `coeffs` buffer: the next free word, the parts so far, what is already placed.
+    `first`: the words in front of the first table (the rows, or a buffer that is being extended)."""
+
+    def __init__(self, first: int):
+        self.at, self.parts, self.placed = int(first), [], {}
+
+    def _place(self, key, tables, value):
+        if key not in self.placed:
+            self.placed[key] = value
+            self.parts += [t.reshape(-1) for t in tables]
+            self.at += sum(t.size for t in tables)
+        return self.placed[key]
+
+    def bilinear(self, n_in: int, n_out: int):
+        """-> (bounds offset, weights offset, ksize) of `pillow_coeffs(n_in, n_out)`, placed once; (0, 0, 0) for
+        n_in == n_out: the pass is skipped"""
+        if n_in == n_out:
+            return 0, 0, 0
+        bounds, kk = pillow_coeffs(n_in, n_out)
+        return self._place(("bilinear", n_in, n_out), (bounds, kk), (self.at, self.at + bounds.size, kk.shape[1]))
+
+    def nearest(self, n_in: int, n_out: int) -> int:
+        """-> the offset of `nearest_table(n_in, n_out)`, placed once"""
+        return self._place(("nearest", n_in, n_out), (nearest_table(n_in, n_out),), self.at)
+
+    def words(self, front):
+        """`front` (the `first` words) and every placed table behind it, as one int32 array"""
+        return np.concatenate([np.asarray(front, dtype=np.int32).reshape(-1)] + self.parts)
+
+
 def _pass(src, bounds, kk):
     """one resample pass along axis 1 of uint8 [rows, n_in, ...] -> uint8 [rows, n_out, ...]"""
     out = np.empty((src.shape[0], bounds.shape[0]) + src.shape[2:], dtype=np.uint8)
@@ -132,10 +187,14 @@ def reference_resize(frame_u8, nh: int, nw: int, layout: str = "chw"):
     return torch.from_numpy(a.copy() if not a.flags.writeable else a) if is_tensor else a
 
 
+def axis_supported(n_in: int, n_out: int) -> bool:
+    """the kernel's range on one axis: at most VNX_RESIZE_MAX_KSIZE taps"""
+    return min(n_in, n_out) >= 1 and kernel_size(n_in, n_out) <= _lib.RESIZE_MAX_KSIZE
+
+
 def supported(h: int, w: int, nh: int, nw: int) -> bool:
     """the kernel's range: at most VNX_RESIZE_MAX_KSIZE taps on both axes"""
-    return (min(h, w, nh, nw) >= 1 and kernel_size(h, nh) <= _lib.RESIZE_MAX_KSIZE
-            and kernel_size(w, nw) <= _lib.RESIZE_MAX_KSIZE)
+    return min(h, w, nh, nw) >= 1 and axis_supported(h, nh) and axis_supported(w, nw)
 
 
 def applies(frames, targets, device, layout: str = "chw") -> bool:
@@ -178,58 +237,37 @@ def plan_video(frames, layout: str, short: int, max_size: int, device):
     return out, None, sizes[0]
 
 
-def padded_size(targets):
-    """(H, W): the largest target, rounded up to multiples of 32"""
-    H = max(t[0] for t in targets)
-    W = max(t[1] for t in targets)
-    return (H + 31) // 32 * 32, (W + 31) // 32 * 32
+padded_size = ingest.padded_hw           # (H, W): the largest target (nh, nw), rounded up to multiples of 32
 
 
-def _coeff_words(sizes, targets):
+def coeff_words(sizes, targets):
     """the `coeffs` buffer of a batch as one int32 array: the per-frame rows, then each distinct axis table once"""
-    n = len(sizes)
-    head = np.zeros((n, 6), dtype=np.int32)
-    parts, at, placed = [], 6 * n, {}
-    for i, ((h, w), (nh, nw)) in enumerate(zip(sizes, targets)):
-        for j, (n_in, n_out) in enumerate(((w, nw), (h, nh))):
-            if n_in == n_out:
-                continue                 # ksize 0: the pass is skipped
-            if (n_in, n_out) not in placed:
-                bounds, kk = pillow_coeffs(n_in, n_out)
-                placed[(n_in, n_out)] = (at, at + bounds.size, kk.shape[1])
-                parts += [bounds.reshape(-1), kk.reshape(-1)]
-                at += bounds.size + kk.size
-            head[i, 3 * j:3 * j + 3] = placed[(n_in, n_out)]
-    return np.concatenate([head.reshape(-1)] + parts)
+    tables = CoeffTables(6 * len(sizes))
+    rows = [tables.bilinear(w, nw) + tables.bilinear(h, nh) for (h, w), (nh, nw) in zip(sizes, targets)]
+    return tables.words(np.array(rows, dtype=np.int32).reshape(len(sizes), 6))
+
+
+_coeff_words = coeff_words               # (the name it had while it was private: callers written against it keep working)
 
 
 def stage_sources(frames, targets, device, layout: str = "chw"):
     """uint8 frames of `layout` and their target sizes [(nh, nw)] -> (pixels uint8 [bytes], src_table int32 [n, 3],
     dst_table int32 [n, 3], coeffs int32 [words]) on `device`; see the module docstring."""
-    device = torch.device(device)
     n = len(frames)
     sizes = [frame_size(f, layout) for f in frames]
-    words = torch.from_numpy(_coeff_words(sizes, targets))
-    dst = torch.tensor([(0, int(nh), int(nw)) for nh, nw in targets], dtype=torch.int32)
     on_device = frames[0].is_cuda
     rows, off = [], 0
     for h, w in sizes:
         rows.append((off, h, w))
         off += 3 * h * w if on_device else ingest._align16(3 * h * w)
-    src = torch.tensor(rows, dtype=torch.int32)
-    small = torch.cat([src.reshape(-1), dst.reshape(-1), words])
-    head = ingest._align16(4 * small.numel())
+    ints = [np.array(rows, dtype=np.int32), np.array([(0, int(nh), int(nw)) for nh, nw in targets], dtype=np.int32),
+            coeff_words(sizes, targets)]
     if on_device:
         pixels = torch.cat([f.reshape(-1) for f in frames])
-        dev = small.pin_memory().to(device, non_blocking=True)
-    else:
-        buf = torch.empty(head + off, dtype=torch.uint8, pin_memory=device.type == "cuda")
-        buf[:4 * small.numel()].view(torch.int32).copy_(small)
-        for f, (o, h, w) in zip(frames, rows):
-            buf[head + o:head + o + 3 * h * w].view(f.shape).copy_(f)
-        whole = buf.to(device, non_blocking=True)
-        pixels, dev = whole[head:], whole[:4 * small.numel()].view(torch.int32)
-    return pixels, dev[:3 * n].view(n, 3), dev[3 * n:6 * n].view(n, 3), dev[6 * n:]
+        dev = torch.from_numpy(np.concatenate([a.reshape(-1) for a in ints])).pin_memory().to(device, non_blocking=True)
+        return pixels, dev[:3 * n].view(n, 3), dev[3 * n:6 * n].view(n, 3), dev[6 * n:]
+    (src, dst, words), pixels = ingest.pack_upload(ints, [(f, o) for f, (o, _, _) in zip(frames, rows)], off, device)
+    return pixels, src, dst, words
 
 
 def reference_resize_ingest(pixels, src_table, dst_table, coeffs, B, H, W, mean, std, channels_last=False, layout="chw"):
