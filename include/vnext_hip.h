@@ -1049,6 +1049,37 @@ int vnx_resize_window_bytes(void* pixels, size_t pixel_bytes, const void* win_ta
                             int batch, int height, int width, int interleaved, void* hip_stream);
 
 /*
+ * Colour augmentation inside the frame launch (augment.hip): vnx_augment_frames with detectron2's RandomBrightness,
+ * RandomContrast and RandomSaturation applied, in that order and per frame, to the resized and flipped BYTES before they are
+ * normalised.  ADDITIVE: two symbols, no existing signature changed, so VNX_ABI_VERSION stays 17.
+ *
+ * Every argument of vnx_augment_frames keeps its meaning.  color_table: int32 device [batch][8] = {flags, the brightness
+ * weight's float bit pattern, the contrast weight as a double (low word, high word), the saturation weight likewise, 0, 0};
+ * flags: 1 brightness, 2 contrast, 4 saturation; a row with flags 0 gives what vnx_augment_frames gives, bit for bit.  Each
+ * step returns bytes through clip(x, 0, 255) and truncation, so the next one sees bytes:
+ *   brightness  x = float(w) * float(u): one rounding, in float;
+ *   contrast    x = (1 - w) * m + w * double(u), m = the integer sum of the frame's own nh * nw * 3 bytes AFTER brightness
+ *               divided once, in double; the padding and the other frames do not count;
+ *   saturation  g = u0 * 0.299 + u1 * 0.587 + u2 * 0.114 (three rounded products, summed left to right, on the channels in
+ *               stored order), x = (1 - w) * g + w * double(u_c) per channel.
+ * Every product and every sum is rounded on its own (no fused multiply-add): the results are numpy's, byte for byte.
+ *
+ * contrast == 0: ONE launch; a row that asks for contrast is then malformed.  contrast != 0: TWO launches -- the first stores
+ * the post-brightness bytes and a sum per 32 x 32 tile into the workspace, the second folds a frame's sums and finishes.  The
+ * workspace is vnx_augment_color_workspace(batch, height, width) bytes INSIDE pixels at byte workspace_offset (a multiple of
+ * 16), behind every source frame; pixels is written there and nowhere else.  Every slot of it that is read was written by
+ * the first launch: no memset, no atomics, bit-identical run to run.
+ * A malformed row -- those of vnx_augment_frames, a flag beyond the three, a weight in use that is not finite, source bytes
+ * that reach into the workspace -- makes an empty frame.  No read leaves a buffer whatever the tables hold.  The weights live
+ * in device memory: a captured launch replays on other pixels, geometry and weights.  batch == 0: VNX_OK, no launch.
+ */
+size_t vnx_augment_color_workspace(int batch, int height, int width);
+int vnx_augment_frames_color(void* pixels, size_t pixel_bytes, const void* src_table, const void* dst_table,
+                             const void* coeffs, size_t coeff_words, const void* color_table, int batch, int height, int width,
+                             float mean0, float mean1, float mean2, float std0, float std1, float std2, int channels_last,
+                             int interleaved, int contrast, size_t workspace_offset, void* x, void* mask, void* hip_stream);
+
+/*
  * Clipped AdamW step (optim.hip): the full-model gradient norm, clip_grad_norm_'s coefficient and the decoupled AdamW
  * update of EVERY parameter tensor of a model in three launches, whatever the number of tensors.  ADDITIVE: two symbols, no
  * existing signature changed, so VNX_ABI_VERSION stays 17; a binding that needs them looks the symbols up.

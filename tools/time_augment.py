@@ -18,6 +18,12 @@ a plan, and per (instance, frame) the mask's COCO counts.
     time: it includes the launch gaps).
 
     python tools/time_augment.py [--out FILE.json] [--rounds N] [--warmup N]
+
+`--color` (profiles/augment_color.json): the same two workloads with a brightness, a contrast and a
+saturation weight per frame.  Three routes alternate per round, every round kept: the host route with colour (the three
+numpy steps of `augment.color_frame` on every resized frame), the device route with colour (two frame launches) and the
+device route without (the plan as it was: the figure to hold against profiles/augment.json).  The bar is the same, between
+the two routes WITH colour; the colour's cost on the device route is reported next to the bytes its extra pass moves.
 """
 from __future__ import annotations
 
@@ -97,6 +103,8 @@ def host_route(frames, plan, masks, ids, stats_):
             a = resize.reference_resize(np.ascontiguousarray(a), p.nh, p.nw, "hwc")
         if p.flip:
             a = np.flip(a, axis=1)
+        if p.color != augment.NO_COLOR:
+            a = augment.color_frame(a, 2, *p.color)
         out_frames.append(torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))))
     gt, boxes, keep = [], [], []
     for f, c in masks:
@@ -168,9 +176,60 @@ def ops_alone(frames, plan, masks, ids, stats_, reps=50):
     return out
 
 
+def with_color(plan, seed):
+    """the plan with a weight per frame and step, as `sample_plan` draws them"""
+    rng = np.random.default_rng(seed)
+    return [p._replace(**{name: float(rng.uniform(0.9, 1.1)) for name in ("brightness", "contrast", "saturation")}) for p in plan]
+
+
+def color_main(a, stats_):
+    res = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "warmup": a.warmup, "host_resize": HOST_RESIZE,
+           "host_threads": torch.get_num_threads(), "cases": {}}
+    for i, name in enumerate(("seqformer_2x5x720p_short480_4inst", "idol_2_pairs_720p_crop384-600_short480_4inst")):
+        frames, plan, masks, ids = workload(name, seed=90 + i)
+        plans = {"host_color": with_color(plan, 190 + i), "device_color": with_color(plan, 190 + i), "device_plain": plan}
+        routes = {"host_color": host_route, "device_color": device_route, "device_plain": device_route}
+        times = {key: [] for key in routes}
+        for r in range(a.rounds + a.warmup):
+            for key, fn in routes.items():
+                t = timed(lambda: fn(frames, plans[key], masks, ids, stats_))
+                if r >= a.warmup:
+                    times[key].append(t)
+        n, (H, W) = len(frames), augment.padded_size(plan)
+        case = {"frames": n, "masks": len(masks), "targets": sorted({(p.nh, p.nw) for p in plan}),
+                "outputs_equal": same(host_route(frames, plans["host_color"], masks, ids, stats_),
+                                      device_route(frames, plans["device_color"], masks, ids, stats_))}
+        for key, v in times.items():
+            case[key + "_route"] = {"host_wall_clock": stats([t[0] for t in v]), "event_region": stats([t[1] for t in v])}
+        hw, dw, pw = (case[k + "_route"]["host_wall_clock"] for k in routes)
+        spread = max(hw["max_ms"] - hw["min_ms"], dw["max_ms"] - dw["min_ms"])
+        case["spread_of_rounds_ms"] = spread
+        case["device_route_meets_the_bar"] = bool(dw["median_ms"] <= hw["median_ms"] + spread)
+        inside = sum(3 * p.nh * p.nw for p in plan)
+        case["color_on_cost"] = {
+            "host_wall_clock_median_ms": dw["median_ms"] - pw["median_ms"],
+            "event_region_median_ms": case["device_color_route"]["event_region"]["median_ms"]
+            - case["device_plain_route"]["event_region"]["median_ms"],
+            "extra_pass_bytes": {"written_by_the_first_launch": inside + 4 * n * (H // 32) * (W // 32),
+                                 "read_by_the_second_launch": inside + 4 * n * (H // 32) * (W // 32) * (H // 32) * (W // 32),
+                                 "note": "the post-brightness bytes inside the frames, once each way, and a uint32 per tile; "
+                                         "every workgroup of the second launch reads its frame's tile sums (from cache)"}}
+        try:
+            case["launches_and_copies"] = {k: counts(lambda: fn(frames, plans[k], masks, ids, stats_)) for k, fn in routes.items()}
+        except Exception as e:      # no device tracer in this torch build: the counts are not measured
+            case["launches_and_copies"] = {"not_measured": repr(e)}
+        res["cases"][name] = case
+    res["timing"] = ("as profiles/augment.json, three routes alternating per round: the host route with the three colour steps in "
+                     "numpy, the device route with them (vnx_augment_frames_color, two launches) and the device route without; "
+                     "the bar: the device route's median with colour is not above the host route's with colour by more than "
+                     "the spread of the rounds; device_plain is the figure to compare with profiles/augment.json")
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "augment.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--color", action="store_true", help="time the colour steps (profiles/augment_color.json)")
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     a = ap.parse_args()
@@ -179,6 +238,9 @@ def main():
     from vnext_amd.registry import get_seqformer_cfg
     cfg = get_seqformer_cfg()
     stats_ = ([float(v) for v in cfg.MODEL.PIXEL_MEAN], [float(v) for v in cfg.MODEL.PIXEL_STD])
+    a.out = a.out or os.path.join(ROOT, "profiles", "augment_color.json" if a.color else "augment.json")
+    if a.color:
+        return write(color_main(a, stats_), a.out)
     res = {"device": torch.cuda.get_device_name(0), "rounds": a.rounds, "warmup": a.warmup, "host_resize": HOST_RESIZE,
            "host_threads": torch.get_num_threads(), "cases": {}}
     for i, name in enumerate(("seqformer_2x5x720p_short480_4inst", "idol_2_pairs_720p_crop384-600_short480_4inst")):
@@ -208,10 +270,14 @@ def main():
                      "ids on the device; host wall clock from the call to a device synchronise and the HIP-event region of the "
                      "same stretch, host / device route alternating per round; launch counts in a pass of their own; the bar: "
                      "the device route's median is not above the host route's by more than the spread of the rounds")
+    write(res, a.out)
+
+
+def write(res, out):
     text = json.dumps(res, indent=1)
     print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         f.write(text)
 
 

@@ -118,6 +118,9 @@ SIGNATURES = {
     "vnx_augment_masks_workspace": (_sz, [_i, _i, _i]),
     "vnx_augment_masks": (_i, [_vp, _sz, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "vnx_resize_window_bytes": (_i, [_vp, _sz, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
+    "vnx_augment_color_workspace": (_sz, [_i, _i, _i]),
+    "vnx_augment_frames_color": (_i, [_vp, _sz, _vp, _vp, _vp, _sz, _vp, _i, _i, _i] + [ctypes.c_float] * 6 +
+                                 [_i, _i, _i, _sz, _vp, _vp, _vp]),
     "vnx_adamw_grad_norm":(_i, [_vp, _i, _vp, _ll, ctypes.c_double, _vp, _vp, _vp]),
     "vnx_adamw_clipped_step": (_i, [_vp, _i, _vp, _i, _vp, _ll, _vp, _vp]),
     "vnx_rle_runs_measure": (_i, [_vp, _ll, _vp, _vp, _i, _vp, _vp]),

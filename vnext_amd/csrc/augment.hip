@@ -14,6 +14,15 @@
 // ksize of (w -> w1), of (h -> h1)}.  A malformed row (the window outside (h1, w1) or the padded size, either byte range
 // outside the buffer or the two overlapping, ksize beyond the limit) leaves its slot untouched.
 //
+// vnx_augment_frames_color is vnx_augment_frames with detectron2's RandomBrightness, RandomContrast and
+// RandomSaturation on the resampled bytes, per frame, the weights read from a colour table in device memory.  Brightness and
+// saturation are pointwise: the kColor = 1 instantiation applies them between phase V and the normalisation, in the one
+// launch.  Contrast blends with the mean of the whole frame after brightness: the kColor = 2 instantiation stores the
+// post-brightness bytes and every tile's integer sum behind the frames in the pixel buffer, and color_finish_kernel (below)
+// folds a frame's sums, divides once in double and finishes: two launches, no atomics, no memset, bit-identical run to run.
+// The float64 expressions are numpy's, rounding for rounding: resize_body.h switches contraction OFF for the whole file
+// (`#pragma clang fp contract(off)`), this one included.
+//
 // vnx_augment_masks.  A ground-truth mask arrives as the END POSITIONS of its COCO runs (the cumulative sums of the counts;
 // column-major, p = x * h + y; runs of zeros and ones alternate, zeros first).  The value of source pixel p is the parity of
 // the number of ends <= p -- an upper bound by binary search; zero-length runs need no special case.  Output pixel (y, x) of
@@ -245,6 +254,68 @@ inline int launch_resize_window_bytes(const char* fn, void* pixels, size_t pixel
   return check_launch(fn);
 }
 
+// ---- colour ----
+// The second of two launches when contrast is on: the grid and the tiles of the frame kernel.  A workgroup folds ITS frame's
+// tile sums (integers: any order gives the same total; the order here is fixed all the same) into the mean of the frame's
+// own nh * nw * 3 bytes -- one division, in double -- then takes its tile's post-brightness bytes through contrast and
+// saturation and on through the frame kernel's normalisation, padding and mask.
+__global__ __launch_bounds__(kResizeThreads) void color_finish_kernel(ResizeArgs a) {
+  __shared__ unsigned long long part[kResizeThreads / kWave];
+  const int H = a.H, W = a.W, tid = threadIdx.x;
+  const int tiles_x = W / kTile, tiles_y = H / kTile;
+  const int tx = blockIdx.x % tiles_x;
+  const int rest = blockIdx.x / tiles_x;
+  const int ty = rest % tiles_y, b = rest / tiles_y;
+  const int ox0 = tx * kTile, oy0 = ty * kTile;
+  ColorRow cr{};
+  const ResizeGeom g = color_geom<2>(a, b, cr);              // workgroup-uniform: what the first launch saw
+  const bool live = oy0 < g.nh && ox0 < g.nw;
+
+  double mean = 0.0;
+  if (live && (cr.flags & kContrast)) {
+    const int tiles = tiles_x * tiles_y;
+    const uint32_t* sums = a.sums + size_t(b) * tiles;
+    unsigned long long s = 0;
+    for (int t = tid; t < tiles; t += kResizeThreads) s += sums[t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t lo = uint32_t(__shfl_xor(int(uint32_t(s)), off, 64)), hi = uint32_t(__shfl_xor(int(uint32_t(s >> 32)), off, 64));
+      s += (unsigned long long)hi << 32 | lo;
+    }
+    if ((tid & (kWave - 1)) == 0) part[tid / kWave] = s;
+    __syncthreads();
+    s = part[0];
+    for (int w = 1; w < kResizeThreads / kWave; ++w) s += part[w];
+    mean = double(s) / double(3ll * g.nh * g.nw);            // (exact integers below 2^53; u.mean() divides once)
+  }
+
+  const int ly = tid >> 3, lx = (tid & 7) << 2;
+  const int y = oy0 + ly, x0 = ox0 + lx;
+  float val[3][4];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) val[c][j] = 0.f;
+  }
+  if (live && y < g.nh && x0 < g.nw) {
+    uint32_t px[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = *reinterpret_cast<const uint32_t*>(a.stage + ((size_t(b) * 3 + c) * H + y) * W + x0);
+    if (cr.flags & kContrast) contrast_words(px, cr.wc, mean);
+    if (cr.flags & kSaturation) saturate_words(px, cr.ws);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x0 + j < g.nw) val[c][j] = (float((px[c] >> (8 * j)) & 0xffu) - a.mean[c]) / a.std[c];
+    }
+  }
+  store_x(a, b, y, x0, val);
+  store_mask(a, b, oy0, ox0, tid, g.nh, g.nw);
+}
+
+inline size_t color_stage_bytes(int batch, int height, int width) { return size_t(batch) * 3 * size_t(height) * size_t(width); }
+
 }  // namespace
 }  // namespace vnx
 
@@ -257,6 +328,48 @@ extern "C" int vnx_augment_frames(const void* pixels, size_t pixel_bytes, const 
   const float mean[3] = {mean0, mean1, mean2}, std[3] = {std0, std1, std2};
   return launch_resize_ingest<true>("vnx_augment_frames", pixels, pixel_bytes, src_table, dst_table, coeffs, coeff_words,
                                     batch, height, width, mean, std, channels_last, interleaved, x, mask, hip_stream);
+}
+
+extern "C" size_t vnx_augment_color_workspace(int batch, int height, int width) {
+  if (batch <= 0 || height < 32 || width < 32) return 0;
+  return color_stage_bytes(batch, height, width) + size_t(batch) * size_t(height / kTile) * size_t(width / kTile) * sizeof(uint32_t);
+}
+
+extern "C" int vnx_augment_frames_color(void* pixels, size_t pixel_bytes, const void* src_table, const void* dst_table,
+                                        const void* coeffs, size_t coeff_words, const void* color_table, int batch, int height,
+                                        int width, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                                        int channels_last, int interleaved, int contrast, size_t workspace_offset, void* x,
+                                        void* mask, void* hip_stream) {
+  const char* fn = "vnx_augment_frames_color";
+  const float mean[3] = {mean0, mean1, mean2}, std[3] = {std0, std1, std2};
+  ResizeArgs a;
+  unsigned grid;
+  const int rc = resize_ingest_args<true>(fn, pixels, pixel_bytes, src_table, dst_table, coeffs, coeff_words, batch, height,
+                                          width, mean, std, channels_last, interleaved, x, mask, a, grid);
+  if (rc != VNX_OK || grid == 0) return rc;
+  if (!color_table || (reinterpret_cast<uintptr_t>(color_table) & 3) != 0) {
+    set_error("%s: the colour table is null or not 4-byte aligned", fn);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  a.color = (const int32_t*)color_table;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (!contrast) {      // pointwise steps only: inside the one frame launch
+    hipLaunchKernelGGL((resize_ingest_kernel<true, false, 1>), dim3(grid), dim3(kResizeThreads), 0, stream, a);
+    return check_launch(fn);
+  }
+  const size_t need = vnx_augment_color_workspace(batch, height, width);
+  if ((workspace_offset & 15) != 0 || workspace_offset > pixel_bytes || need > pixel_bytes - workspace_offset) {
+    set_error("%s: the workspace (%zu bytes at byte %zu, 16-byte aligned) does not lie inside the %zu bytes of pixels", fn, need,
+              workspace_offset, pixel_bytes);
+    return VNX_ERR_INVALID_ARGUMENT;
+  }
+  a.stage = (unsigned char*)pixels + workspace_offset;
+  a.sums = reinterpret_cast<uint32_t*>(a.stage + color_stage_bytes(batch, height, width));      // (a multiple of 16 behind it)
+  hipLaunchKernelGGL((resize_ingest_kernel<true, false, 2>), dim3(grid), dim3(kResizeThreads), 0, stream, a);
+  const int rc1 = check_launch(fn);
+  if (rc1 != VNX_OK) return rc1;
+  hipLaunchKernelGGL(color_finish_kernel, dim3(grid), dim3(kResizeThreads), 0, stream, a);
+  return check_launch(fn);
 }
 
 extern "C" int vnx_resize_window_bytes(void* pixels, size_t pixel_bytes, const void* win_table, const void* coeffs,

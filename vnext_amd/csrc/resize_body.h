@@ -15,6 +15,18 @@
 // What kBytes changes: the coefficient tables are those of (w -> w1) and (h -> h1) and output pixel (y, x) of the window
 // takes their rows y0 + y and x0 + x -- again an index where the bounds and weights are staged.  Phase V's bytes go to a
 // tile of LDS instead of through the normalisation, and from there to memory in 16-byte pieces (see the stores).
+//
+// kColor (augment.hip): detectron2's RandomBrightness / RandomContrast / RandomSaturation on the bytes
+// phase V made, before the normalisation.  A colour row of 8 words per frame holds {flags, the brightness weight's fp32 bits,
+// the contrast weight (a double: low word, high word), the saturation weight (likewise), 0, 0}.
+//   kColor = 1  vnx_augment_frames_color without contrast: brightness and saturation are pointwise, so they sit between
+//               phase V and the normalisation of the SAME launch.
+//   kColor = 2  the first of two launches when contrast is on: contrast blends with the mean of the whole frame AFTER
+//               brightness, so this pass stores the post-brightness bytes ([B][3][H][W], a word of 4 pixels per thread) and
+//               each tile's integer sum (one uint32 per workgroup, every slot written) behind the frames in the pixel buffer;
+//               augment.hip's second kernel folds the sums and finishes.
+// The double expressions are the reference's numpy expressions, rounding for rounding: contraction is OFF for this whole
+// file (the pragma below), so a product and the sum that takes it stay two roundings.
 #pragma once
 
 #include "vnx_common.h"
@@ -32,6 +44,9 @@ constexpr int kAugSrcWords = 8;            // {byte offset, h, w, x0, y0, cw, ch
 constexpr int kAugCoeffWords = 8;          // the two bilinear triples, then the offsets of the two nearest tables (augment.hip)
 constexpr int kWinWords = 16;              // {src byte offset, h, w, h1, w1, x0, y0, cw, ch, dst byte offset, the two triples}
 
+constexpr int kColorWords = 8;             // {flags, brightness fp32 bits, contrast lo, hi, saturation lo, hi, 0, 0}
+constexpr int kBrightness = 1, kContrast = 2, kSaturation = 4;      // the flags
+
 typedef uint32_t rsz_u4 __attribute__((ext_vector_type(4)));
 
 struct ResizeArgs {
@@ -45,6 +60,9 @@ struct ResizeArgs {
   unsigned char* mask;                     // (kBytes: the pixel buffer again, writable: the windows are stored into it)
   int B, H, W, channels_last, interleaved;
   float mean[3], std[3];
+  const int32_t* color;                    // kColor: [B][8]
+  unsigned char* stage;                    // kColor = 2 and the second kernel: [B][3][H][W] post-brightness bytes
+  uint32_t* sums;                          //   and [B][tiles] sums of them
 };
 
 struct AxisTab { int bounds, kk, ksize; };      // ksize 0: the pass is skipped
@@ -140,18 +158,127 @@ __device__ __forceinline__ uint32_t source_byte(const unsigned char* __restrict_
   return (word >> (8 * int(at & 3))) & 0xffu;
 }
 
+// ---- colour (kColor) ----
+struct ColorRow { int flags; float wb; double wc, ws; };
+
+// frame `b`'s colour row; `allowed`: the flags this launch can honour.  A flag outside them, or a weight in use that is
+// not finite, is a malformed row: -> false, and the frame is the empty frame
+__device__ __forceinline__ bool color_row(const int32_t* __restrict__ color, int b, int allowed, ColorRow& r) {
+  const int32_t* s = color + kColorWords * size_t(b);
+  r.flags = s[0];
+  r.wb = __int_as_float(s[1]);
+  r.wc = __hiloint2double(s[3], s[2]);
+  r.ws = __hiloint2double(s[5], s[4]);
+  return (r.flags & ~allowed) == 0 && (!(r.flags & kBrightness) || __builtin_isfinite(r.wb)) &&
+         (!(r.flags & kContrast) || __builtin_isfinite(r.wc)) && (!(r.flags & kSaturation) || __builtin_isfinite(r.ws));
+}
+
+// np.clip(x, 0, 255).astype(np.uint8): the conversion truncates
+__device__ __forceinline__ uint32_t clip_byte(float x) { return uint32_t(x < 0.f ? 0.f : (x > 255.f ? 255.f : x)); }
+__device__ __forceinline__ uint32_t clip_byte(double x) { return uint32_t(x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x)); }
+
+// BlendTransform in float64: src + w * float64(u), where src = (1 - w) * {mean, gray} is rounded already; the product is
+// rounded, then the sum (no contraction in this file)
+__device__ __forceinline__ uint32_t blend_byte(double src, double w, uint32_t u) { return clip_byte(src + w * double(u)); }
+
+// px[c]: 4 pixels of channel c, a byte each.  Brightness: float32(w) * float32(u), one rounding
+__device__ __forceinline__ void brighten_words(uint32_t (&px)[3], float w) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    uint32_t out = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out |= clip_byte(w * float((px[c] >> (8 * j)) & 0xffu)) << (8 * j);
+    px[c] = out;
+  }
+}
+
+// Contrast: (1 - w) * mean + w * float64(u)
+__device__ __forceinline__ void contrast_words(uint32_t (&px)[3], double w, double mean) {
+  const double src = (1.0 - w) * mean;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    uint32_t out = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) out |= blend_byte(src, w, (px[c] >> (8 * j)) & 0xffu) << (8 * j);
+    px[c] = out;
+  }
+}
+
+// Saturation: gray = c0 * 0.299 + c1 * 0.587 + c2 * 0.114, three rounded products summed left to right, then
+// (1 - w) * gray + w * float64(u_c) per channel
+__device__ __forceinline__ void saturate_words(uint32_t (&px)[3], double w) {
+  uint32_t out[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t u0 = (px[0] >> (8 * j)) & 0xffu, u1 = (px[1] >> (8 * j)) & 0xffu, u2 = (px[2] >> (8 * j)) & 0xffu;
+    const double gray = double(u0) * 0.299 + double(u1) * 0.587 + double(u2) * 0.114;
+    const double src = (1.0 - w) * gray;
+    out[0] |= blend_byte(src, w, u0) << (8 * j);
+    out[1] |= blend_byte(src, w, u1) << (8 * j);
+    out[2] |= blend_byte(src, w, u2) << (8 * j);
+  }
+  px[0] = out[0]; px[1] = out[1]; px[2] = out[2];
+}
+
 template <bool kWindow, bool kBytes>
 __device__ __forceinline__ ResizeGeom frame_geom(const ResizeArgs& a, int b, WindowOut& wo) {
   if constexpr (kBytes) return window_geom(a.src_table, a.coeff_words, a.pixel_bytes, a.H, a.W, b, wo);
   else return resize_geom<kWindow>(a.src_table, a.dst_table, a.coeffs, a.coeff_words, a.pixel_bytes, a.H, a.W, b);
 }
 
-template <bool kWindow, bool kBytes = false>
+// frame `b` of a colour launch: the geometry of vnx_augment_frames, emptied where the colour row is malformed or, with two
+// launches (kColor = 2, and the second kernel alike), where the frame's source bytes reach into the staging area
+template <int kColor>
+__device__ __forceinline__ ResizeGeom color_geom(const ResizeArgs& a, int b, ColorRow& cr) {
+  ResizeGeom g = resize_geom<true>(a.src_table, a.dst_table, a.coeffs, a.coeff_words, a.pixel_bytes, a.H, a.W, b);
+  bool ok = color_row(a.color, b, kColor == 2 ? (kBrightness | kContrast | kSaturation) : (kBrightness | kSaturation), cr);
+  if constexpr (kColor == 2)      // (a live g: off + 3 h w <= pixel_bytes < 2^31)
+    ok = ok && g.nh > 0 && (long long)g.off + 3ll * g.h * g.w <= (long long)(a.stage - a.pixels);
+  if (!ok) g.nh = g.nw = 0;
+  return g;
+}
+
+// x of 4 pixels of one output row, contiguous or channels-last
+__device__ __forceinline__ void store_x(const ResizeArgs& a, int b, int y, int x0, const float (&val)[3][4]) {
+  const int H = a.H, W = a.W;
+  const size_t row = size_t(b) * H + y;
+  if (a.channels_last) {
+    float* out = a.x + (row * W + x0) * 3;
+    *reinterpret_cast<vnx_f4*>(out) = vnx_f4{val[0][0], val[1][0], val[2][0], val[0][1]};
+    *reinterpret_cast<vnx_f4*>(out + 4) = vnx_f4{val[1][1], val[2][1], val[0][2], val[1][2]};
+    *reinterpret_cast<vnx_f4*>(out + 8) = vnx_f4{val[2][2], val[0][3], val[1][3], val[2][3]};
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      *reinterpret_cast<vnx_f4*>(a.x + ((size_t(b) * 3 + c) * H + y) * W + x0) =
+          vnx_f4{val[c][0], val[c][1], val[c][2], val[c][3]};
+  }
+}
+
+// the padding mask of a tile: 16 pixels per thread, 64 threads
+__device__ __forceinline__ void store_mask(const ResizeArgs& a, int b, int oy0, int ox0, int tid, int nh, int nw) {
+  if (tid < 2 * kTile) {
+    const int y = oy0 + (tid >> 1), x0 = ox0 + ((tid & 1) << 4);
+    rsz_u4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) word |= uint32_t(y >= nh || x0 + 4 * k + j >= nw) << (8 * j);
+      v[k] = word;
+    }
+    *reinterpret_cast<rsz_u4*>(a.mask + ((size_t(b) * a.H + y) * a.W + x0)) = v;
+  }
+}
+
+template <bool kWindow, bool kBytes = false, int kColor = 0>
 __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArgs a) {
+  static_assert(kColor == 0 || (kWindow && !kBytes), "colour rides on the augment instantiation");
   __shared__ __attribute__((aligned(16))) unsigned char rows[3][kMaxRows][kTile];
   __shared__ uint32_t kh[kTile][kMaxKsize], kv[kTile][kMaxKsize];
   __shared__ int bh[kTile][2], bv[kTile][2];      // {first source column, taps}; {first staged row, taps}
   __shared__ __attribute__((aligned(16))) unsigned char obuf[kBytes ? 3 * kTile * kTile : 16];      // kBytes: the tile's bytes
+  __shared__ uint32_t wave_sum[kResizeThreads / 64];      // kColor = 2: the waves' sums of the tile's bytes
 
   const int H = a.H, W = a.W, tid = threadIdx.x;
   const int tiles_x = W / kTile, tiles_y = H / kTile;
@@ -160,7 +287,11 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
   const int ty = rest % tiles_y, b = rest / tiles_y;
   const int ox0 = tx * kTile, oy0 = ty * kTile;
   WindowOut wo{};
-  const ResizeGeom g = frame_geom<kWindow, kBytes>(a, b, wo);   // workgroup-uniform
+  ColorRow cr{};
+  const ResizeGeom g = [&] {                                    // workgroup-uniform
+    if constexpr (kColor != 0) return color_geom<kColor>(a, b, cr);
+    else return frame_geom<kWindow, kBytes>(a, b, wo);
+  }();
   const bool live = oy0 < g.nh && ox0 < g.nw;              // the tile holds pixels of the frame
 
   if (live) {
@@ -260,7 +391,9 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
 #pragma unroll
       for (int j = 0; j < 4; ++j) val[c][j] = 0.f;
     }
-    if (live && y < g.nh && x0 < g.nw) {
+    uint32_t px[3] = {0u, 0u, 0u};                           // the thread's 4 pixels, a word of bytes per channel
+    const bool inside = live && y < g.nh && x0 < g.nw;
+    if (inside) {
       const int first = bv[ly][0], cnt = bv[ly][1];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
@@ -288,10 +421,43 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
           }
           continue;
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (x0 + j < g.nw) val[c][j] = (float((bytes >> (8 * j)) & 0xffu) - a.mean[c]) / a.std[c];
+        px[c] = bytes;
       }
+      if constexpr (kColor != 0) {                           // (the flags are workgroup-uniform)
+        if (cr.flags & kBrightness) brighten_words(px, cr.wb);
+        if constexpr (kColor == 1)
+          if (cr.flags & kSaturation) saturate_words(px, cr.ws);
+      }
+      if constexpr (!kBytes && kColor != 2) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (x0 + j < g.nw) val[c][j] = (float((px[c] >> (8 * j)) & 0xffu) - a.mean[c]) / a.std[c];
+        }
+      }
+    }
+    if constexpr (kColor == 2) {
+      // ---- the first of two launches: the post-brightness bytes and the tile's sum of them (pixels inside the frame only) ----
+      uint32_t s = 0;
+      if (inside) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          *reinterpret_cast<uint32_t*>(a.stage + ((size_t(b) * 3 + c) * H + y) * W + x0) = px[c];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (x0 + j < g.nw) s += (px[c] >> (8 * j)) & 0xffu;
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += uint32_t(__shfl_xor(int(s), off, 64));
+      if ((tid & 63) == 0) wave_sum[tid >> 6] = s;
+      __syncthreads();
+      if (tid == 0) {                                        // every slot is written, a dead tile's with 0: no memset
+        for (int w = 1; w < kResizeThreads / 64; ++w) s += wave_sum[w];
+        a.sums[blockIdx.x] = s;                              // (at most 32 * 32 * 3 * 255)
+      }
+      return;
     }
     if constexpr (kBytes) {
       // ---- the window's bytes: whole 16-byte pieces of memory where a tile row covers them, bytes at its two ends ----
@@ -329,41 +495,19 @@ __global__ __launch_bounds__(kResizeThreads) void resize_ingest_kernel(ResizeArg
       }
       return;
     }
-    const size_t row = size_t(b) * H + y;
-    if (a.channels_last) {
-      float* out = a.x + (row * W + x0) * 3;
-      *reinterpret_cast<vnx_f4*>(out) = vnx_f4{val[0][0], val[1][0], val[2][0], val[0][1]};
-      *reinterpret_cast<vnx_f4*>(out + 4) = vnx_f4{val[1][1], val[2][1], val[0][2], val[1][2]};
-      *reinterpret_cast<vnx_f4*>(out + 8) = vnx_f4{val[2][2], val[0][3], val[1][3], val[2][3]};
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        *reinterpret_cast<vnx_f4*>(a.x + ((size_t(b) * 3 + c) * H + y) * W + x0) =
-            vnx_f4{val[c][0], val[c][1], val[c][2], val[c][3]};
-    }
+    store_x(a, b, y, x0, val);
   }
-  // ---- the mask: 16 pixels per thread, 64 threads ----
-  if (tid < 2 * kTile) {
-    const int y = oy0 + (tid >> 1), x0 = ox0 + ((tid & 1) << 4);
-    rsz_u4 v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) word |= uint32_t(y >= g.nh || x0 + 4 * k + j >= g.nw) << (8 * j);
-      v[k] = word;
-    }
-    *reinterpret_cast<rsz_u4*>(a.mask + ((size_t(b) * H + y) * W + x0)) = v;
-  }
+  store_mask(a, b, oy0, ox0, tid, g.nh, g.nw);
 }
 
-// what both entry points check before they launch, and the launch
+// what the entry points check before they launch -> the kernel's arguments and its grid (blocks 0: nothing to launch)
 template <bool kWindow>
-inline int launch_resize_ingest(const char* fn, const void* pixels, size_t pixel_bytes, const void* src_table,
-                                const void* dst_table, const void* coeffs, size_t coeff_words, int batch, int height, int width,
-                                const float* mean, const float* std, int channels_last, int interleaved, void* x, void* mask,
-                                void* hip_stream) {
+inline int resize_ingest_args(const char* fn, const void* pixels, size_t pixel_bytes, const void* src_table,
+                              const void* dst_table, const void* coeffs, size_t coeff_words, int batch, int height, int width,
+                              const float* mean, const float* std, int channels_last, int interleaved, void* x, void* mask,
+                              ResizeArgs& a, unsigned& grid) {
   constexpr int kRow = kWindow ? kAugCoeffWords : 6;
+  grid = 0;
   if (batch < 0 || height < 32 || width < 32 || height % 32 != 0 || width % 32 != 0) {
     set_error("%s: bad sizes (batch %d, padded %d x %d: multiples of 32)", fn, batch, height, width);
     return VNX_ERR_INVALID_ARGUMENT;
@@ -393,7 +537,7 @@ inline int launch_resize_ingest(const char* fn, const void* pixels, size_t pixel
     set_error("%s: %d frames of %d x %d are more than one launch addresses", fn, batch, height, width);
     return VNX_ERR_UNSUPPORTED;
   }
-  ResizeArgs a;
+  a = ResizeArgs{};
   a.pixels = (const unsigned char*)pixels;
   a.pixel_bytes = (long long)pixel_bytes;
   a.src_table = (const int32_t*)src_table;
@@ -404,7 +548,22 @@ inline int launch_resize_ingest(const char* fn, const void* pixels, size_t pixel
   a.mask = (unsigned char*)mask;
   a.B = batch; a.H = height; a.W = width; a.channels_last = channels_last != 0; a.interleaved = interleaved != 0;
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std[c]; }
-  hipLaunchKernelGGL(resize_ingest_kernel<kWindow>, dim3(unsigned(blocks)), dim3(kResizeThreads), 0, (hipStream_t)hip_stream, a);
+  grid = unsigned(blocks);
+  return VNX_OK;
+}
+
+// both plain entry points: the checks, and the launch
+template <bool kWindow>
+inline int launch_resize_ingest(const char* fn, const void* pixels, size_t pixel_bytes, const void* src_table,
+                                const void* dst_table, const void* coeffs, size_t coeff_words, int batch, int height, int width,
+                                const float* mean, const float* std, int channels_last, int interleaved, void* x, void* mask,
+                                void* hip_stream) {
+  ResizeArgs a;
+  unsigned grid;
+  const int rc = resize_ingest_args<kWindow>(fn, pixels, pixel_bytes, src_table, dst_table, coeffs, coeff_words, batch, height,
+                                             width, mean, std, channels_last, interleaved, x, mask, a, grid);
+  if (rc != VNX_OK || grid == 0) return rc;
+  hipLaunchKernelGGL(resize_ingest_kernel<kWindow>, dim3(grid), dim3(kResizeThreads), 0, (hipStream_t)hip_stream, a);
   return check_launch(fn);
 }
 

@@ -6,14 +6,19 @@ clip whose source frames have `sizes` [(h, w)]:
   * INPUT.CROP.ENABLED: ONE coin per clip picks the list with the crop or the list without it (the mapper's
     `np.random.rand() > 0.5` -> no crop);
   * detectron2's RandomCrop("absolute_range", (lo, hi)), PER FRAME: ch in [min(h, lo), min(h, hi)], cw likewise, then the
-    origin y0 in [0, h - ch], x0 in [0, w - cw] -- four integers, in that order;
+    origin y0 in [0, h - ch], x0 in [0, w - cw] -- four integers, in that order; "relative" and "absolute" fix the size
+    (`crop_size`) and draw the origin only;
   * ResizeShortestEdge(MIN_SIZE_TRAIN, MAX_SIZE_TRAIN, MIN_SIZE_TRAIN_SAMPLING) on the CROPPED size: "choice" / "range" draw
     a short edge per frame, "choice_by_clip" / "range_by_clip" once per clip; the target through `resize.shortest_edge_size`;
-  * INPUT.RANDOM_FLIP: "horizontal" a coin (p = 0.5) per frame, "flip_by_clip" once per clip, "none" never.
+  * INPUT.RANDOM_FLIP: "horizontal" a coin (p = 0.5) per frame, "flip_by_clip" once per clip, "none" never;
+  * INPUT.AUGMENTATIONS: for each of "brightness", "contrast", "saturation" that is listed, in that order, ONE
+    `uniform(0.9, 1.1)` PER FRAME after the frame's other draws -- the stock detectron2 classes know nothing of clips, so the
+    weights differ between the frames of a clip even under `flip_by_clip`.
 It reproduces the SAME DISTRIBUTIONS, not the same random stream: the reference draws from numpy's global generator inside
 detectron2's transform classes, which cannot be replayed (or checked) without detectron2; `rng` is a `numpy.random.Generator`.
-Keys absent from `cfg.INPUT` take detectron2's defaults.  A cfg that asks for what the device route does not build
-(INPUT.AUGMENTATIONS, a vertical flip, another crop type) raises: such a config keeps the host mapper.
+Keys absent from `cfg.INPUT` take detectron2's defaults.  A cfg that asks for what the device route does not build ("rotation"
+or an unknown name in INPUT.AUGMENTATIONS, a vertical flip, RandomCrop("relative_range")) raises: such a config keeps the
+host mapper.
 
 `stage_clip(frames, annotations, plan, num_classes) -> dict`: the mapper's bookkeeping that has nothing to do with pixels --
 one slot per instance id of the clip (ids in order of first appearance; the reference iterates a `set`), in every frame the
@@ -51,17 +56,55 @@ def _get(node, key, default):
     return node.get(key, default) if isinstance(node, dict) else getattr(node, key, default)
 
 
-def _read_input(cfg, who: str, styles):
+COLOR_NAMES = ("brightness", "contrast", "saturation")      # in `build_augmentation`'s order
+
+
+def color_names(cfg, who: str = "sample_plan"):
+    """INPUT.AUGMENTATIONS -> the colour steps it lists, in `build_augmentation`'s order; any other entry ("rotation": OpenCV's
+    warpAffine, which nothing here restates) raises, naming it"""
+    listed = _get(cfg.INPUT, "AUGMENTATIONS", None) or ()
+    listed = (listed,) if isinstance(listed, str) else tuple(listed)
+    for name in listed:
+        if name not in COLOR_NAMES:
+            raise ValueError("%s: INPUT.AUGMENTATIONS entry %r is not built on the device" % (who, name))
+    return tuple(name for name in COLOR_NAMES if name in listed)
+
+
+def crop_size(crop_type: str, size, h: int, w: int, rng):
+    """detectron2's `RandomCrop.get_crop_size` for an image of h x w -> (ch, cw), with its expressions:
+      "relative"        int(h * c0 + 0.5), int(w * c1 + 0.5);
+      "relative_range"  the same with fractions c + rand * (1 - c), c = `size` in float32, drawn for (h, w) together;
+      "absolute"        min(size, dim);
+      "absolute_range"  ch in [min(h, lo), min(h, hi)], then cw likewise."""
+    if crop_type == "relative":
+        return int(h * size[0] + 0.5), int(w * size[1] + 0.5)
+    if crop_type == "relative_range":
+        lo = np.asarray(size, dtype=np.float32)
+        fh, fw = lo + rng.random(2) * (1 - lo)
+        return int(h * fh + 0.5), int(w * fw + 0.5)
+    if crop_type == "absolute":
+        return min(int(size[0]), h), min(int(size[1]), w)
+    if crop_type == "absolute_range":
+        ch = int(rng.integers(min(h, size[0]), min(h, size[1]) + 1))
+        return ch, int(rng.integers(min(w, size[0]), min(w, size[1]) + 1))
+    raise ValueError("crop_size: RandomCrop(%r)" % (crop_type,))
+
+
+def _read_input(cfg, who: str, styles, crop_types=("absolute_range",), color: bool = False):
     """What both samplers read of `cfg.INPUT`, and their refusals (`who`: the sampler's name in the messages; `styles`: the
-    MIN_SIZE_TRAIN_SAMPLING values it takes) -> (crop on, crop lo, crop hi, short edges, max size, sampling, flip mode)"""
+    MIN_SIZE_TRAIN_SAMPLING values it takes; `crop_types`: the RandomCrop types; `color`: INPUT.AUGMENTATIONS is the
+    caller's to read) -> (crop on, crop SIZE's two values, short edges, max size, sampling, flip mode)"""
     inp = cfg.INPUT
-    if _get(inp, "AUGMENTATIONS", None):
+    if not color and _get(inp, "AUGMENTATIONS", None):
         raise ValueError("%s: INPUT.AUGMENTATIONS %r are not built on the device" % (who, inp.AUGMENTATIONS))
     crop = _get(inp, "CROP", None)
     crop_on = bool(_get(crop, "ENABLED", False))
-    if crop_on and _get(crop, "TYPE", "relative_range") != "absolute_range":
-        raise ValueError("%s: only RandomCrop('absolute_range') is built on the device" % who)
-    lo, hi = (int(v) for v in _get(crop, "SIZE", (384, 600))) if crop_on else (0, 0)
+    crop_type = _get(crop, "TYPE", "relative_range")
+    if crop_on and crop_type not in crop_types:
+        raise ValueError("%s: RandomCrop(%r) is not built on the device (it takes %s)" % (who, crop_type, ", ".join(crop_types)))
+    lo, hi = _get(crop, "SIZE", (384, 600)) if crop_on else (0, 0)
+    if not crop_type.startswith("relative"):
+        lo, hi = int(lo), int(hi)
     short = _get(inp, "MIN_SIZE_TRAIN", (800,))
     short = (int(short),) if isinstance(short, int) else tuple(int(s) for s in short)
     max_size = int(_get(inp, "MAX_SIZE_TRAIN", 1333))
@@ -80,15 +123,17 @@ def sample_plan(cfg, sizes, num_frames, rng):
     """-> a FramePlan per frame of one clip; see the module docstring"""
     assert len(sizes) == num_frames
     crop_on, lo, hi, short, max_size, style, flip_mode = _read_input(
-        cfg, "sample_plan", ("choice", "range", "choice_by_clip", "range_by_clip"))
+        cfg, "sample_plan", ("choice", "range", "choice_by_clip", "range_by_clip"),
+        crop_types=("absolute_range", "absolute", "relative"), color=True)
+    crop_type = _get(_get(cfg.INPUT, "CROP", None), "TYPE", "relative_range")
+    steps = color_names(cfg)
 
     use_crop = crop_on and not rng.random() > 0.5      # the coin per clip
     plan, size, flip = [], None, False
     for i, (h, w) in enumerate(sizes):
         x0, y0, cw, ch = 0, 0, int(w), int(h)
         if use_crop:
-            ch = int(rng.integers(min(h, lo), min(h, hi) + 1))
-            cw = int(rng.integers(min(w, lo), min(w, hi) + 1))
+            ch, cw = crop_size(crop_type, (lo, hi), int(h), int(w), rng)
             y0 = int(rng.integers(h - ch + 1))
             x0 = int(rng.integers(w - cw + 1))
         if size is None or "by_clip" not in style:
@@ -96,7 +141,8 @@ def sample_plan(cfg, sizes, num_frames, rng):
         if flip_mode != "none" and (i == 0 or flip_mode == "horizontal"):
             flip = bool(rng.random() < 0.5)
         nh, nw = resize.shortest_edge_size(ch, cw, size, max_size)
-        plan.append(FramePlan(x0, y0, cw, ch, nh, nw, flip))
+        drawn = {name: float(rng.uniform(0.9, 1.1)) for name in steps}      # per frame, in the steps' order
+        plan.append(FramePlan(x0, y0, cw, ch, nh, nw, flip, *(drawn.get(name) for name in COLOR_NAMES)))
     return plan
 
 
@@ -114,8 +160,9 @@ def sample_coco_plan(cfg, size, rng, frames: int = 2):
       * ResizeShortestEdge(MIN_SIZE_TRAIN, MAX_SIZE_TRAIN, MIN_SIZE_TRAIN_SAMPLING) on the cropped size.
     As `sample_plan`, it reproduces the same DISTRIBUTIONS, not the same random stream: the reference draws from numpy's
     global generator inside detectron2's transform classes, which cannot be replayed (or checked) without detectron2; `rng`
-    is a `numpy.random.Generator`.  What `sample_plan` refuses is refused here: INPUT.AUGMENTATIONS, another crop type, a
-    RANDOM_FLIP it does not know (a vertical flip).  The mapper itself never reads RANDOM_FLIP -- it always builds
+    is a `numpy.random.Generator`.  Refused here: INPUT.AUGMENTATIONS (the mapper builds its own list and never reads the
+    key: a config that sets it means the other mapper), a crop type other than "absolute_range", a RANDOM_FLIP it does not
+    know (a vertical flip).  The mapper itself never reads RANDOM_FLIP -- it always builds
     RandomFlip() -- so every accepted value flips per frame; and its ResizeShortestEdge takes "choice" or "range" only."""
     crop_on, lo, hi, short, max_size, style, _ = _read_input(cfg, "sample_coco_plan", ("choice", "range"))
     h, w = int(size[0]), int(size[1])

@@ -98,7 +98,8 @@ def resize_staged(pixels, src_table, dst_table, coeffs, B, H, W, layout, stats):
 def augment_staged(staged, stats, backbone):
     """one step's staged SOURCE frames (`augment.stage_step`) -> (x, mask, table) of the frames cropped, resized and flipped
     as their plan says: one launch; channels-last where `ingest_staged` would be (a training step); the table is the
-    destination geometry `level_inputs` hands to the level launch"""
+    destination geometry `level_inputs` hands to the level launch.  Plans that carry colour weights have
+    them applied by the same call: still one launch for brightness and saturation, one more when a frame asks for contrast"""
     asks = getattr(backbone, "wants_channels_last", None)
     nhwc = bool(staged.pixels.is_cuda and asks is not None and asks())
     x, mask = augment.augment_frames(staged, *stats, channels_last=nhwc)
@@ -109,8 +110,8 @@ def host_augmented(batched_inputs):
     """The host route of the same plan: every clip's frames and ground truth through `augment.reference_*` on the CPU
     -> `batched_inputs` as a mapper of the reference would have made them (CHW uint8 frames at their targets; gt_masks,
     gt_boxes, the filtered gt_ids).  What a model with `device_augment` takes when `augment.applies` says no, and what the
-    tests compare the device route with.  Frames, RLE masks and polygons go through their own plan's `frame`, `mask` and
-    `coords`; only the boxes and the keep flags differ by kind (`truth`): a FramePlan takes them from the masks, a ChainPlan
+    tests compare the device route with.  Frames, RLE masks and polygons go through their own plan's `frame` (which ends
+    with the plan's colour steps, `augment.color_frame`), `mask` and `coords`; only the boxes and the keep flags differ by kind (`truth`): a FramePlan takes them from the masks, a ChainPlan
     (a COCO pre-training pair) from the annotations' boxes (`chain_boxes`), gt_ids = -1 where the box OR
     the mask is empty."""
     out = []

@@ -47,6 +47,16 @@ fills the slots with the (mirrored, where the frame is flipped) crop window of t
 slot as a source frame.  Pillow's 8-bit bilinear resize commutes with a horizontal flip, so flip-first equals the mirrored
 window with the flip applied last -- which is what the kernels do, and what the tests hold to the literal order.
 `BYTES_CALLS` counts those launches.
+
+Colour: a FramePlan may carry `brightness`, `contrast`, `saturation` -- the weights detectron2's
+RandomBrightness / RandomContrast / RandomSaturation drew for THIS frame, None where the step is off (the default: every
+positional construction keeps its meaning).  `color_frame` is the three steps in numpy, literally, on the resized and flipped
+bytes; `FramePlan.frame` ends with it, so `reference_augment_frames` and `host_augmented` take them.  `stage_step` packs the
+weights of a step that has any into a colour table [n, 8] (`color_words`: the float as its bit pattern, the doubles as two
+words) in the same upload, and with contrast reserves the kernels' workspace behind the frames in the same allocation;
+`augment_frames` then calls `vnx_augment_frames_color`: one launch, two with contrast (the mean of a whole frame after
+brightness needs a pass of its own).  A step without a weight stages the tables and makes the launch it always did.
+`COLOR_CALLS` counts those calls and their launches.
 """
 from __future__ import annotations
 
@@ -61,7 +71,10 @@ from . import ingest, poly_rle, resize
 
 CALLS = {"augment_frames": 0, "augment_masks": 0}      # calls through the C ABI (tests: the ops ran / did not run)
 BYTES_CALLS = {"resize_window_bytes": 0}               # (a dict of its own: tests compare CALLS as a whole)
-SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS, WIN_WORDS = 8, 8, 4, 16
+COLOR_CALLS = {"augment_frames_color": 0, "launches": 0}      # (likewise; every such call also counts as an augment_frames)
+SRC_WORDS, COEFF_WORDS, MASK_ROW_WORDS, WIN_WORDS, COLOR_WORDS = 8, 8, 4, 16, 8
+BRIGHTNESS, CONTRAST, SATURATION = 1, 2, 4             # the flags of a colour row
+NO_COLOR = (None, None, None)
 
 
 nearest_table = resize.nearest_table
@@ -78,8 +91,34 @@ def _window_inside(p, h: int, w: int) -> bool:
     return p.x0 >= 0 and p.y0 >= 0 and p.cw >= 1 and p.ch >= 1 and p.x0 + p.cw <= w and p.y0 + p.ch <= h
 
 
+def _to_bytes(x):
+    """what every BlendTransform returns: `np.clip(x, 0, 255).astype(np.uint8)` (the conversion truncates)"""
+    return np.clip(x, 0, 255).astype(np.uint8)
+
+
+def color_frame(a, ac: int, brightness=None, contrast=None, saturation=None):
+    """detectron2's RandomBrightness, RandomContrast, RandomSaturation with the weights they drew (None: the step is off), in
+    `build_augmentation`'s order, on a uint8 frame whose channels are axis `ac`; every step returns bytes, so the next one
+    sees bytes.  numpy 2 types: brightness in float32, one rounding; contrast and saturation in float64, every product and
+    every sum rounded on its own.  The gray value is the left-to-right sum of three rounded products on the channels in stored
+    order (this package's statement of `image.dot([0.299, 0.587, 0.114])`, whose rounding is the BLAS's).  The oracle of the
+    kernels."""
+    if brightness is not None:
+        a = _to_bytes(np.float32(brightness) * a.astype(np.float32))
+    if contrast is not None:
+        w = float(contrast)
+        a = _to_bytes((1 - w) * a.mean() + w * a.astype(np.float64))
+    if saturation is not None:
+        w = float(saturation)
+        c = np.moveaxis(a, ac, 0).astype(np.float64)
+        gray = c[0] * 0.299 + c[1] * 0.587 + c[2] * 0.114
+        a = _to_bytes((1 - w) * np.expand_dims(gray, ac) + w * a.astype(np.float64))
+    return a
+
+
 class FramePlan(NamedTuple):
-    """One frame's draw of crop -> resize -> flip: the window {x0, y0, cw, ch} inside the source, the target, the flip"""
+    """One frame's draw of crop -> resize -> flip: the window {x0, y0, cw, ch} inside the source, the target, the flip; then
+    the colour weights drawn for this frame, None where the step is off"""
     x0: int
     y0: int
     cw: int
@@ -87,6 +126,13 @@ class FramePlan(NamedTuple):
     nh: int
     nw: int
     flip: bool
+    brightness: float = None
+    contrast: float = None
+    saturation: float = None
+
+    @property
+    def color(self):
+        return (self.brightness, self.contrast, self.saturation)
 
     def inside(self, h: int, w: int) -> bool:
         """the window lies inside a source of h x w"""
@@ -109,9 +155,10 @@ class FramePlan(NamedTuple):
         return xy
 
     def frame(self, a, ah: int, aw: int, layout: str):
-        """a uint8 source array -> the augmented one: slicing, `resize.reference_resize`, `np.flip`"""
+        """a uint8 source array -> the augmented one: slicing, `resize.reference_resize`, `np.flip`, `color_frame`"""
         a = resize.reference_resize(_window(a, self, ah, aw), self.nh, self.nw, layout)
-        return np.flip(a, axis=aw) if self.flip else a
+        a = np.flip(a, axis=aw) if self.flip else a
+        return a if self.color == NO_COLOR else color_frame(a, 3 - ah - aw, *self.color)
 
     def mask(self, dense):
         """a bool [h, w] mask at the source size -> bool [nh, nw]: slicing, the index tables, `np.flip`"""
@@ -139,6 +186,8 @@ class ChainPlan(NamedTuple):
     ch: int
     nh: int
     nw: int
+
+    color = NO_COLOR      # (the COCO mapper builds its own list and never reads INPUT.AUGMENTATIONS)
 
     @property
     def resamples_twice(self) -> bool:
@@ -354,6 +403,31 @@ def window_words(words, win):
     return tables.words(words), win
 
 
+def color_words(plan):
+    """the colour table of a step: int32 [n, 8] = {flags, brightness as the float's bit pattern, contrast as a double's two
+    words (low, high), saturation likewise, 0, 0}; a frame without a weight is a row of zeros"""
+    rows = np.zeros((len(plan), COLOR_WORDS), dtype=np.int32)
+    for row, p in zip(rows, plan):
+        wb, wc, ws = p.color
+        row[0] = BRIGHTNESS * (wb is not None) | CONTRAST * (wc is not None) | SATURATION * (ws is not None)
+        row[1:2] = np.array([0.0 if wb is None else wb], dtype=np.float32).view(np.int32)
+        row[2:6] = np.array([0.0 if wc is None else wc, 0.0 if ws is None else ws], dtype="<f8").view(np.int32)
+    return rows
+
+
+def color_of(row):
+    """a colour row (a list of 8) -> (brightness, contrast, saturation), None where the flag is clear"""
+    words = np.array(row, dtype=np.int32)
+    wb, (wc, ws) = float(words[1:2].view(np.float32)[0]), words[2:6].view("<f8").tolist()
+    return (wb if row[0] & BRIGHTNESS else None, wc if row[0] & CONTRAST else None, ws if row[0] & SATURATION else None)
+
+
+def color_workspace(n: int, H: int, W: int) -> int:
+    """the bytes `vnx_augment_frames_color` wants behind the frames when contrast is on: the post-brightness bytes
+    [n, 3, H, W] and a uint32 per (frame, 32 x 32 tile) (vnx_augment_color_workspace)"""
+    return n * 3 * H * W + 4 * n * (H // 32) * (W // 32)
+
+
 _coeff_words, _window_words = coeff_words, window_words      # (their names while private: callers written against them keep working)
 
 
@@ -374,6 +448,8 @@ class Staged(NamedTuple):
     win_table: torch.Tensor     # int32 [k, 16], the rows of `resize_window_bytes`: k = 0 unless a step of ChainPlans needs it
     win_size: tuple             # (H1, W1) that launch is padded to
     boxes: object = None        # a step of ChainPlans: fp32 [m, 4], the masks' boxes the caller computed (`chain_boxes`)
+    color: object = None        # a step with a colour weight: int32 [n, 8] (`color_words`); None: the plain launch
+    workspace: int = -1         # ... with contrast, on the device: the byte offset inside `pixels` of the kernels' workspace
 
     def mask_views(self, masks):
         """the flat output of `augment_masks` -> per frame bool [n_inst, nh, nw] (views)"""
@@ -466,21 +542,30 @@ def stage_step(frames, plan, masks, device, layout: str = "chw", ids=None, poly_
     words, win = window_words(coeff_words(list(plan) + full), win)      # the first resample's tables ride behind the others
     idv = np.zeros(m, dtype=np.int32) if ids is None else np.asarray(ids, dtype=np.int32).reshape(m)
     ints = [src, dst, words, ends, rows, idv, win]
+    colored = any(p.color != NO_COLOR for p in plan)
+    workspace = -1
+    if colored:                              # (never a chain step: the table rides last, nothing else moves)
+        ints.append(color_words(plan))
+        if device.type == "cuda" and any(p.contrast is not None for p in plan):
+            workspace, slots = nbytes + slots, slots + color_workspace(n, *padded_size(plan))
     if with_boxes:
         box_bits = np.zeros((m, 4), dtype=np.float32) if boxes is None else np.asarray(boxes, dtype=np.float32).reshape(m, 4)
         ints.append(box_bits.view(np.int32))
-    (src_d, dst_d, words_d, ends_d, rows_d, ids_d, win_d, *box_d), pixels = ingest.pack_upload(
+    (src_d, dst_d, words_d, ends_d, rows_d, ids_d, win_d, *rest), pixels = ingest.pack_upload(
         ints, uploads, nbytes, device, extra=slots)
+    color_d, box_d = (rest[0], rest[1:]) if colored else (None, rest)
     if pseudo:
         ends_d = torch.cat((ends_d, poly_ends.to(torch.int32)))
     win_size = ingest.padded_hw([(r[8], r[7]) for r in win.tolist()] or [(1, 1)])
     return Staged(pixels, src_d[:n], dst_d[:n], words_d, ends_d, rows_d, ids_d, padded_size(plan), layout, mask_bytes, groups,
-                  src_d, dst_d, win_d, win_size, *(b.view(torch.float32) for b in box_d))
+                  src_d, dst_d, win_d, win_size, box_d[0].view(torch.float32) if box_d else None, color_d, workspace)
 
 
 def _plan_of(staged: Staged):
-    return [FramePlan(x0, y0, cw, ch, nh, nw, bool(fl)) for (_, _, _, x0, y0, cw, ch, fl), (_, nh, nw)
-            in zip(staged.src_table.tolist(), staged.dst_table.tolist())]
+    n = staged.src_table.shape[0]
+    colors = [NO_COLOR] * n if staged.color is None else [color_of(r) for r in staged.color.tolist()]
+    return [FramePlan(x0, y0, cw, ch, nh, nw, bool(fl), *c) for (_, _, _, x0, y0, cw, ch, fl), (_, nh, nw), c
+            in zip(staged.src_table.tolist(), staged.dst_table.tolist(), colors)]
 
 
 # ---- the ops ----------------------------------------------------------------------------------------------------------------
@@ -508,7 +593,8 @@ def resize_window_bytes(staged: Staged) -> None:
 
 
 def augment_frames(staged: Staged, mean, std, channels_last: bool = False):
-    """-> (x fp32 [B, 3, H, W], mask bool [B, H, W]) of the augmented frames; one launch"""
+    """-> (x fp32 [B, 3, H, W], mask bool [B, H, W]) of the augmented frames; one launch -- with a colour table the launch
+    that also applies brightness and saturation, and one more when a frame asks for contrast"""
     pixels, layout, (H, W) = staged.pixels, staged.layout, staged.size
     B = staged.src_table.shape[0]
     if not pixels.is_cuda:
@@ -521,10 +607,20 @@ def augment_frames(staged: Staged, mean, std, channels_last: bool = False):
     x = torch.empty((B, 3, H, W), dtype=torch.float32, device=pixels.device, memory_format=fmt)
     mask = torch.empty((B, H, W), dtype=torch.bool, device=pixels.device)
     with torch.cuda.device(pixels.device):
-        _lib.check(_lib.lib().vnx_augment_frames(
-            pixels.data_ptr(), pixels.numel(), staged.src_table.data_ptr(), staged.dst_table.data_ptr(),
-            staged.coeffs.data_ptr(), staged.coeffs.numel(), B, H, W, *ingest._stats(mean), *ingest._stats(std),
-            int(bool(channels_last)), int(layout == "hwc"), x.data_ptr(), mask.data_ptr(), _lib.current_stream(pixels)))
+        if staged.color is None:
+            _lib.check(_lib.lib().vnx_augment_frames(
+                pixels.data_ptr(), pixels.numel(), staged.src_table.data_ptr(), staged.dst_table.data_ptr(),
+                staged.coeffs.data_ptr(), staged.coeffs.numel(), B, H, W, *ingest._stats(mean), *ingest._stats(std),
+                int(bool(channels_last)), int(layout == "hwc"), x.data_ptr(), mask.data_ptr(), _lib.current_stream(pixels)))
+        else:
+            contrast = staged.workspace >= 0
+            _lib.check(_lib.lib().vnx_augment_frames_color(
+                pixels.data_ptr(), pixels.numel(), staged.src_table.data_ptr(), staged.dst_table.data_ptr(),
+                staged.coeffs.data_ptr(), staged.coeffs.numel(), staged.color.data_ptr(), B, H, W, *ingest._stats(mean),
+                *ingest._stats(std), int(bool(channels_last)), int(layout == "hwc"), int(contrast),
+                max(staged.workspace, 0), x.data_ptr(), mask.data_ptr(), _lib.current_stream(pixels)))
+            COLOR_CALLS["augment_frames_color"] += 1
+            COLOR_CALLS["launches"] += 1 + contrast
     CALLS["augment_frames"] += 1
     return x, mask
 
