@@ -91,6 +91,86 @@ def test_seqformer_folds_frames_into_one_launch(monkeypatch):
     assert len(calls) == 1 and calls[0][0] == N * T  # the reference launches T times (:107-120)
 
 
+@pytest.mark.parametrize("name", CASES)
+def test_the_two_linears_run_once_when_the_fused_prologue_is_turned_away(name, monkeypatch):
+    """fused_prologue on, nobody wants the samples back, and the fused kernels do not take the case (CPU tensors): the
+    unfused fallback takes its softmax from the logits already computed -- one GEMM per Linear, same values."""
+    monkeypatch.setattr(func_mod, "MSDA", _OracleOp)
+    g = load(name)
+    m = build(name, g, "cpu", torch.float64)
+    m.fused_prologue, m.return_samples = True, False
+    fired = {"sampling_offsets": 0, "attention_weights": 0}
+    for key in fired:
+        getattr(m, key).register_forward_hook(lambda mod, args, out, key=key: fired.__setitem__(key, fired[key] + 1))
+    with torch.no_grad():
+        got = run(name, m, g, "cpu", torch.float64)
+    assert fired == {"sampling_offsets": 1, "attention_weights": 1}
+    for k, v in got.items():
+        assert tuple(v.shape) == g[k].shape, f"{k}: {tuple(v.shape)} vs {g[k].shape}"
+        np.testing.assert_allclose(v.numpy(), g[k], rtol=1e-9, atol=1e-11, err_msg=k)
+
+
+@pytest.mark.parametrize("keep", [True, False])
+def test_return_samples_survives_a_failing_fused_call(keep, monkeypatch):
+    """encode_forward takes the fused kernels whatever `return_samples` says -- as an argument, not by writing the attribute:
+    a fused call that raises leaves the module as it was, and the class default is still what an untouched module reads."""
+    from vnext_amd import msda_ext
+    from vnext_amd.ops.modules import ms_deform_attn as mod
+
+    class Failing:
+        @staticmethod
+        def apply(*args):
+            raise RuntimeError("fused call failed")
+
+    monkeypatch.setattr(msda_ext, "fused_supported", lambda *a: True)
+    monkeypatch.setattr(mod, "MSDeformAttnFusedFunction", Failing)
+    g = load("seq_encode")
+    m = build("seq_encode", g, "cpu", torch.float64)
+    before = dict(m.__dict__)
+    if keep:
+        assert m.return_samples is True and "return_samples" not in m.__dict__      # the class default
+    else:
+        m.return_samples = False
+    with pytest.raises(RuntimeError, match="fused call failed"), torch.no_grad():
+        run("seq_encode", m, g, "cpu", torch.float64)
+    assert m.return_samples is keep
+    assert ("return_samples" in m.__dict__) == (not keep)       # no instance attribute has appeared
+    assert set(m.__dict__) - {"return_samples"} == set(before)
+
+
+@pytest.mark.gpu
+def test_fused_encode_path_with_return_samples_on():
+    """A SeqFormer encode module never returned locations / weights: with `return_samples = True` one forward is still ONE
+    fused launch and no unfused one, and equals the unfused composition.  The smallest shapes the fused kernels accept
+    (D == 32, L * P == 16)."""
+    import model_grad_harness as H
+    from vnext_amd.ops.functions import level_tensors
+    dev = "cuda:0"
+    C, M, L, P, N, T = 64, 2, 4, 4, 1, 2
+    pyramid = [(4, 6), (2, 3), (1, 2), (1, 1)]
+    S = sum(h * w for h, w in pyramid)
+    torch.manual_seed(5)
+    m = MSDeformAttnSeqFormer(C, L, M, P, "encode").to(dev)
+    with torch.no_grad():
+        m.sampling_offsets.weight.normal_(0, 0.02)
+        m.attention_weights.weight.normal_(0, 0.05)
+    m.return_samples = True
+    shapes_t, lsi = level_tensors(pyramid, dev)
+    src, pos = torch.randn(N, T, S, C, device=dev), torch.randn(N, T, S, C, device=dev)
+    ref = torch.rand(N, S, L, 2, device=dev)
+    with torch.no_grad():
+        with H.counting_launches() as counts:
+            got = m(src + pos, None, ref, src, shapes_t, lsi, None)
+        assert counts.get("vnx_msda_fused_forward", 0) == 1 and counts.get("vnx_msda_forward", 0) == 0, counts
+        m.fused_prologue = False
+        with H.counting_launches() as counts:
+            want = m(src + pos, None, ref, src, shapes_t, lsi, None)
+        assert counts.get("vnx_msda_fused_forward", 0) == 0 and counts.get("vnx_msda_forward", 0) == 1, counts
+    assert m.return_samples is True
+    assert got.shape == want.shape == (N, T, S, C)
+    assert float((got - want).abs().max()) <= 2e-5 * float(want.abs().max())
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype,tol", [(torch.float64, 1e-9), (torch.float32, 2e-5)])
 @pytest.mark.parametrize("name", CASES)

@@ -115,6 +115,45 @@ def test_idol_transformer_on_gpu(dtype, tol):
     check_idol(out, g, tol)
 
 
+# ---------------------------------------------------------------- state-dict key ORDER (what seeded initialisation walks)
+def _wb(*names):
+    return [f"{n}.{p}" for n in names for p in ("weight", "bias")]
+
+
+_MHA = ["in_proj_weight", "in_proj_bias", "out_proj.weight", "out_proj.bias"]
+_MSDA = ["sampling_offsets", "attention_weights", "value_proj", "output_proj"]      # the module's Linears, construction order
+
+
+def _expected_keys(encoder_layer, decoder_layer, layers=2):
+    keys = ["level_embed"]
+    for stack, layer in (("encoder", encoder_layer), ("decoder", decoder_layer)):
+        keys += [f"{stack}.layers.{i}.{k}" for i in range(layers) for k in layer]
+    return keys + _wb("reference_points")
+
+
+@pytest.mark.parametrize("kind", ["seqformer", "idol"])
+def test_state_dict_key_order(kind):
+    """Per layer: the attention module's Linears in construction order, then the norms and Linears in registration order.
+    `_reset_parameters` walks the parameters in this order, so it is part of what a seed means."""
+    from vnext_amd.models.idol_transformer import DeformableTransformer as IdolTransformer
+    if kind == "seqformer":
+        cls, msda = DeformableTransformer, _MSDA + ["output_proj_box"]
+        decoder_layer = (_wb(*(f"cross_attn.{n}" for n in msda)) + _wb("norm1", "norm1_box")
+                         + [f"self_attn.{k}" for k in _MHA] + _wb("norm2") + [f"self_attn_box.{k}" for k in _MHA]
+                         + _wb("norm2_box", "linear1", "linear2", "norm3", "linear1_box", "linear2_box", "norm3_box",
+                               "time_attention_weights"))
+    else:
+        cls, msda = IdolTransformer, _MSDA
+        decoder_layer = (_wb(*(f"cross_attn.{n}" for n in msda)) + _wb("norm1") + [f"self_attn.{k}" for k in _MHA]
+                         + _wb("norm2", "linear1", "linear2", "norm3"))
+    encoder_layer = _wb(*(f"self_attn.{n}" for n in msda)) + _wb("norm1", "linear1", "linear2", "norm2")
+    tr = cls(d_model=64, nhead=2, num_encoder_layers=2, num_decoder_layers=2, dim_feedforward=128,
+             return_intermediate_dec=True, num_feature_levels=4)
+    want = _expected_keys(encoder_layer, decoder_layer)
+    assert len(want) == {"seqformer": 119, "idol": 79}[kind]
+    assert list(tr.state_dict()) == want
+
+
 # ---------------------------------------------------------------- gradients against the reference (train() mode)
 def _fixture_gradients(kind, g, gg, tr, L):
     """fp64 on the CPU, MSDA through F.grid_sample: the fixture's upstream gradients on what the detector consumes, then every

@@ -16,56 +16,14 @@ from __future__ import annotations
 
 import torch
 from torch import nn
-from torch.nn.init import constant_, normal_, xavier_uniform_
 
 from ..ops.fused_ffn import autocast_once, ffn_block
 from ..ops import shadow_weights
 from ..ops.fused_norm import add_dropout_norm
 from ..ops.self_attention import query_self_attention_block
 from ..ops.modules import MSDeformAttnIDOL
-from .seqformer_transformer import DeformableTransformerEncoder as _ClipEncoder
-from .seqformer_transformer import _get_activation_fn, _get_clones
-from .transformer_common import ReferenceScaler, flatten_levels, refined_boxes
-
-
-class DeformableTransformerEncoderLayer(nn.Module):
-    def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4, n_heads=8, n_points=4):
-        super().__init__()
-        self.self_attn = MSDeformAttnIDOL(d_model, n_levels, n_heads, n_points)
-        self.self_attn.defer_output_bias = True      # added in norm1's pass (forward below)
-        self.dropout1 = nn.Dropout(dropout)
-        self.norm1 = nn.LayerNorm(d_model)
-        self.linear1 = nn.Linear(d_model, d_ffn)
-        self.activation = _get_activation_fn(activation)
-        self.dropout2 = nn.Dropout(dropout)
-        self.linear2 = nn.Linear(d_ffn, d_model)
-        self.dropout3 = nn.Dropout(dropout)
-        self.norm2 = nn.LayerNorm(d_model)
-        shadow_weights.install(self)     # under autocast: this layer's GEMM weights cast once, together
-
-    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
-        q = src if pos is None else src + pos
-        src2 = self.self_attn(q, reference_points, src, spatial_shapes, level_start_index, padding_mask)[0]
-        src = add_dropout_norm(src, src2, self.dropout1, self.norm1, r_bias=self.self_attn.output_proj.bias)
-        # norm2(src + dropout3(linear2(dropout2(activation(linear1(src)))))) -- vnext_amd/ops/fused_ffn.py
-        return ffn_block(src, self.linear1, self.activation, self.dropout2, self.linear2, self.dropout3, self.norm2)
-
-
-class DeformableTransformerEncoder(nn.Module):
-    def __init__(self, encoder_layer, num_layers):
-        super().__init__()
-        self.layers = _get_clones(encoder_layer, num_layers)
-        self.num_layers = num_layers
-
-    get_reference_points = staticmethod(_ClipEncoder.get_reference_points)   # same construction (:249-261)
-
-    def forward(self, src, spatial_shapes, level_start_index, valid_ratios, pos=None, padding_mask=None,
-                spatial_shapes_list=None):
-        shapes = spatial_shapes_list if spatial_shapes_list is not None else spatial_shapes.tolist()
-        reference_points = self.get_reference_points(shapes, valid_ratios, device=src.device)
-        for layer in self.layers:
-            src = layer(src, pos, reference_points, spatial_shapes, level_start_index, padding_mask)
-        return src
+from .transformer_common import DeformableTransformerEncoder, DeformableTransformerEncoderLayer  # (shared: re-exported)
+from .transformer_common import DeformableTransformerBase, ReferenceScaler, _get_activation_fn, _get_clones, refined_boxes
 
 
 class DeformableTransformerDecoderLayer(nn.Module):
@@ -137,59 +95,28 @@ class DeformableTransformerDecoder(nn.Module):
                 (torch.stack(kept_boxes) if kept_boxes else None))
 
 
-class DeformableTransformer(nn.Module):
+class DeformableTransformer(DeformableTransformerBase):
     def __init__(self, d_model=256, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=1024,
                  dropout=0.1, activation="relu", return_intermediate_dec=False, num_frames=1,
                  num_feature_levels=4, dec_n_points=4, enc_n_points=4, two_stage=False, return_samples=False):
-        super().__init__()
         if two_stage:
             raise NotImplementedError("two_stage is never enabled by IDOL's configs")
-        self.d_model, self.nhead, self.two_stage = d_model, nhead, False
-        self.num_frames = 1
-        self.num_feature_levels = num_feature_levels
-        enc = DeformableTransformerEncoderLayer(d_model, dim_feedforward, dropout, activation, num_feature_levels,
-                                                nhead, enc_n_points)
-        self.encoder = DeformableTransformerEncoder(enc, num_encoder_layers)
+        enc = DeformableTransformerEncoderLayer(MSDeformAttnIDOL, d_model, dim_feedforward, dropout, activation,
+                                                num_feature_levels, nhead, enc_n_points)
+        encoder = DeformableTransformerEncoder(enc, num_encoder_layers)
         dec = DeformableTransformerDecoderLayer(d_model, dim_feedforward, dropout, activation, num_feature_levels,
                                                 nhead, dec_n_points)
-        self.decoder = DeformableTransformerDecoder(dec, num_decoder_layers, return_intermediate_dec, return_samples)
-        self.level_embed = nn.Parameter(torch.Tensor(num_feature_levels, d_model))
-        self.reference_points = nn.Linear(d_model, 2)
-        self._reset_parameters()
-        for m in self.encoder.modules():   # the encoder never reads locations / weights: fused prologue
-            if isinstance(m, MSDeformAttnIDOL):
-                m.return_samples = False
-        if not return_samples:             # nor does the decoder, unless the sample keeper is on
-            for m in self.decoder.modules():
-                if isinstance(m, MSDeformAttnIDOL):
-                    m.return_samples = False
-
-    def _reset_parameters(self):
-        for p in self.parameters():
-            if p.dim() > 1:
-                nn.init.xavier_uniform_(p)
-        for m in self.modules():
-            if isinstance(m, MSDeformAttnIDOL):
-                m._reset_parameters()
-        xavier_uniform_(self.reference_points.weight.data, gain=1.0)
-        constant_(self.reference_points.bias.data, 0.)
-        normal_(self.level_embed)
-
-    @staticmethod
-    def get_valid_ratio(mask):
-        _, H, W = mask.shape
-        valid_H = torch.sum(~mask[:, :, 0], 1)
-        valid_W = torch.sum(~mask[:, 0, :], 1)
-        return torch.stack([valid_W.float() / W, valid_H.float() / H], -1)
+        decoder = DeformableTransformerDecoder(dec, num_decoder_layers, return_intermediate_dec, return_samples)
+        super().__init__(encoder, decoder, d_model, nhead, num_feature_levels, decoder_returns_samples=return_samples)
+        self.two_stage, self.num_frames = False, 1
 
     def forward(self, srcs, masks, pos_embeds, query_embed=None):
         """srcs: per level [N, C, H_l, W_l]; -> (hs [Ld, N, Q, C], memory [N, S, C], init_reference
         [N, Q, 2], inter_references [Ld, N, Q, 4], inter_samples | None, the layers' box predictions (with their graph) | None,
         None)  (:135-198)"""
         assert query_embed is not None
-        memory_in, padding, pos, shapes_t, start_t, sizes = flatten_levels(srcs, masks, pos_embeds, self.level_embed)
         valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
-        memory = self.encoder(memory_in, shapes_t, start_t, valid_ratios, pos, padding, spatial_shapes_list=sizes)
+        memory, padding, shapes_t, start_t = self.encode(srcs, masks, pos_embeds, valid_ratios)
         images, channels = memory.shape[0], memory.shape[-1]
         query_pos = query_embed[:, :channels].unsqueeze(0).expand(images, -1, -1)
         tgt = query_embed[:, channels:].unsqueeze(0).expand(images, -1, -1)

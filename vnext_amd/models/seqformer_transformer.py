@@ -14,12 +14,10 @@ differently onto the machine:
 """
 from __future__ import annotations
 
-import copy
+from functools import partial
 
 import torch
-import torch.nn.functional as F
 from torch import nn
-from torch.nn.init import constant_, normal_, xavier_uniform_
 
 from ..ops.fused_ffn import autocast_once, ffn_block
 from ..ops import shadow_weights
@@ -27,84 +25,9 @@ from ..ops.fused_norm import add_dropout_norm
 from ..ops.decoder_glue import time_weighted_sum
 from ..ops.modules import MSDeformAttnSeqFormer
 from ..ops.self_attention import query_self_attention_block
-from .transformer_common import ReferenceScaler, flatten_levels, inverse_sigmoid, refined_boxes  # noqa: F401  (inverse_sigmoid: re-exported)
-
-
-
-def _get_clones(module, n):
-    return nn.ModuleList([copy.deepcopy(module) for _ in range(n)])
-
-
-def _get_activation_fn(activation):
-    if activation == "relu":
-        return F.relu
-    if activation == "gelu":
-        return F.gelu
-    if activation == "glu":
-        return F.glu
-    raise RuntimeError(f"activation should be relu/gelu, not {activation}.")
-
-
-class DeformableTransformerEncoderLayer(nn.Module):
-    def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4, n_heads=8,
-                 n_points=4):
-        super().__init__()
-        self.self_attn = MSDeformAttnSeqFormer(d_model, n_levels, n_heads, n_points, 'encode')
-        self.self_attn.defer_output_bias = True      # added in norm1's pass (forward below)
-        self.dropout1 = nn.Dropout(dropout)
-        self.norm1 = nn.LayerNorm(d_model)
-        self.linear1 = nn.Linear(d_model, d_ffn)
-        self.activation = _get_activation_fn(activation)
-        self.dropout2 = nn.Dropout(dropout)
-        self.linear2 = nn.Linear(d_ffn, d_model)
-        self.dropout3 = nn.Dropout(dropout)
-        self.norm2 = nn.LayerNorm(d_model)
-        shadow_weights.install(self)     # under autocast: this layer's GEMM weights cast once, together
-
-    @staticmethod
-    def with_pos_embed(tensor, pos):
-        return tensor if pos is None else tensor + pos
-
-    def forward_ffn(self, src):
-        # src2 = linear2(dropout2(activation(linear1(src)))); norm2(src + dropout3(src2)) -- vnext_amd/ops/fused_ffn.py
-        return ffn_block(src, self.linear1, self.activation, self.dropout2, self.linear2, self.dropout3, self.norm2)
-
-    def forward(self, src, pos, reference_points, spatial_shapes, level_start_index, padding_mask=None):
-        src2 = self.self_attn(self.with_pos_embed(src, pos), None, reference_points, src, spatial_shapes,
-                              level_start_index, padding_mask)
-        src = add_dropout_norm(src, src2, self.dropout1, self.norm1, r_bias=self.self_attn.output_proj.bias)
-        return self.forward_ffn(src)
-
-
-class DeformableTransformerEncoder(nn.Module):
-    def __init__(self, encoder_layer, num_layers):
-        super().__init__()
-        self.layers = _get_clones(encoder_layer, num_layers)
-        self.num_layers = num_layers
-
-    @staticmethod
-    def get_reference_points(spatial_shapes, valid_ratios, device):
-        # pixel centres / (valid ratio * size), then * valid ratio  (reference :183-196)
-        refs = []
-        for lvl, (H_, W_) in enumerate(spatial_shapes):
-            H_, W_ = int(H_), int(W_)
-            ref_y, ref_x = torch.meshgrid(
-                torch.linspace(0.5, H_ - 0.5, H_, dtype=torch.float32, device=device),
-                torch.linspace(0.5, W_ - 0.5, W_, dtype=torch.float32, device=device), indexing="ij")
-            ref_y = ref_y.reshape(-1)[None] / (valid_ratios[:, None, lvl, 1] * H_)
-            ref_x = ref_x.reshape(-1)[None] / (valid_ratios[:, None, lvl, 0] * W_)
-            refs.append(torch.stack((ref_x, ref_y), -1))
-        reference_points = torch.cat(refs, 1)
-        return reference_points[:, :, None] * valid_ratios[:, None]
-
-    def forward(self, src, spatial_shapes, level_start_index, valid_ratios, pos=None, padding_mask=None,
-                spatial_shapes_list=None):
-        shapes_iter = spatial_shapes_list if spatial_shapes_list is not None else spatial_shapes.tolist()
-        reference_points = self.get_reference_points(shapes_iter, valid_ratios, device=src.device)
-        output = src
-        for layer in self.layers:
-            output = layer(output, pos, reference_points, spatial_shapes, level_start_index, padding_mask)
-        return output
+from .transformer_common import DeformableTransformerEncoder, DeformableTransformerEncoderLayer  # (shared: re-exported)
+from .transformer_common import DeformableTransformerBase, ReferenceScaler, _get_activation_fn, _get_clones, refined_boxes
+from .transformer_common import inverse_sigmoid  # noqa: F401  (re-exported)
 
 
 class DeformableTransformerDecoderLayer(nn.Module):
@@ -219,53 +142,26 @@ class DeformableTransformerDecoder(nn.Module):
         return tuple(torch.stack(store) for store in kept[:3]) + (torch.stack(kept[3]) if self.bbox_embed is not None else None,)
 
 
-class DeformableTransformer(nn.Module):
+class DeformableTransformer(DeformableTransformerBase):
     def __init__(self, d_model=256, nhead=8, num_encoder_layers=6, num_decoder_layers=6, dim_feedforward=1024,
                  dropout=0.1, activation="relu", return_intermediate_dec=False, num_frames=1,
                  num_feature_levels=4, dec_n_points=4, enc_n_points=4):
-        super().__init__()
-        self.d_model = d_model
-        self.nhead = nhead
-        self.num_feature_levels = num_feature_levels
-        encoder_layer = DeformableTransformerEncoderLayer(d_model, dim_feedforward, dropout, activation,
-                                                          num_feature_levels, nhead, enc_n_points)
-        self.encoder = DeformableTransformerEncoder(encoder_layer, num_encoder_layers)
+        encoder_layer = DeformableTransformerEncoderLayer(partial(MSDeformAttnSeqFormer, mode='encode'), d_model,
+                                                          dim_feedforward, dropout, activation, num_feature_levels, nhead,
+                                                          enc_n_points)
+        encoder = DeformableTransformerEncoder(encoder_layer, num_encoder_layers)
         decoder_layer = DeformableTransformerDecoderLayer(d_model, dim_feedforward, dropout, activation,
                                                           num_feature_levels, nhead, dec_n_points)
-        self.decoder = DeformableTransformerDecoder(decoder_layer, num_decoder_layers, return_intermediate_dec)
-        self.level_embed = nn.Parameter(torch.Tensor(num_feature_levels, d_model))
-        self.reference_points = nn.Linear(d_model, 2)
-        self._reset_parameters()
-        for m in self.modules():     # nothing here reads the modules' locations / weights: fused prologue
-            if isinstance(m, MSDeformAttnSeqFormer):
-                m.return_samples = False
-
-    def _reset_parameters(self):
-        for p in self.parameters():
-            if p.dim() > 1:
-                nn.init.xavier_uniform_(p)
-        for m in self.modules():
-            if isinstance(m, MSDeformAttnSeqFormer):
-                m._reset_parameters()
-        xavier_uniform_(self.reference_points.weight.data, gain=1.0)
-        constant_(self.reference_points.bias.data, 0.)
-        normal_(self.level_embed)
-
-    @staticmethod
-    def get_valid_ratio(mask):
-        _, H, W = mask.shape
-        valid_H = torch.sum(~mask[:, :, 0], 1)
-        valid_W = torch.sum(~mask[:, 0, :], 1)
-        return torch.stack([valid_W.float() / W, valid_H.float() / H], -1)
+        decoder = DeformableTransformerDecoder(decoder_layer, num_decoder_layers, return_intermediate_dec)
+        super().__init__(encoder, decoder, d_model, nhead, num_feature_levels)
 
     def forward(self, srcs, masks, pos_embeds, query_embed=None):
         """srcs / pos_embeds per level [N, T, C, H_l, W_l], masks [N, T, H_l, W_l], query_embed [Q, 2C] ->
         (hs, hs_box, memory [N, T, S, C], initial references [N, T, Q, 2], per-layer references, per-layer box predictions
         (with their graph; None without a box head on the decoder), None, valid_ratios)."""
         assert query_embed is not None
-        memory_in, padding, pos, shapes_t, start_t, sizes = flatten_levels(srcs, masks, pos_embeds, self.level_embed)
         valid_ratios = torch.stack([self.get_valid_ratio(m[:, 0]) for m in masks], 1)      # of the clip's first frame
-        memory = self.encoder(memory_in, shapes_t, start_t, valid_ratios, pos, padding, spatial_shapes_list=sizes)
+        memory, padding, shapes_t, start_t = self.encode(srcs, masks, pos_embeds, valid_ratios)
 
         clips, frames, channels = memory.shape[0], memory.shape[1], memory.shape[-1]
         # (materialised once: every layer's kernels want dense rows, and an expanded view would be copied per use)

@@ -8,6 +8,9 @@ Two classes, because the reference has two (same name, different forward):
 * `MSDeformAttnSeqFormer` <- projects/SeqFormer/seqformer/models/ops/modules/ms_deform_attn.py:32-217
   `mode='encode'|'decode'`, clip tensors `[N, T, ...]`, extra `output_proj_box`.
 
+Both offer `encode_forward(query, reference_points, input_flatten, spatial_shapes, level_start_index,
+padding_mask) -> output`: what the shared encoder layer (vnext_amd/models/transformer_common.py) calls.
+
 Parameter names, shapes and initialisation are the reference's (checkpoints load
 unchanged).  What differs is the mapping onto the machine: the
 reference loops over the T frames of a clip in Python and launches the op once per frame
@@ -88,44 +91,28 @@ class _MSDeformAttnBase(nn.Module):
     return_samples = True
     fused_prologue = True
 
-    def _raw_offsets_and_logits(self, query):
+    # -- one path from the query to the sampled rows -------------------------------------------
+    # Every tensor below may carry the frame axis of a clip behind the batch axis ([N, T, ...]); whatever leads folds into
+    # the op's batch axis for the launch and unfolds afterwards.
+    def _project_value(self, input_flatten, input_padding_mask, spatial_shapes):
+        """input [..., S, C] -> value [..., S, M, D], padded rows zero."""
+        check_flattened_length(spatial_shapes, input_flatten.shape[-2])
+        # value = self.value_proj(input_flatten); value.masked_fill(input_padding_mask[..., None], 0)  (SeqFormer :94-96):
+        # one GEMM + one in-place pass on the GPU (vnext_amd/ops/fused_ffn.py), the expression itself elsewhere
+        value = linear_masked(input_flatten, self.value_proj, input_padding_mask)
+        return value.view(*value.shape[:-1], self.n_heads, self.d_model // self.n_heads)
+
+    def _offsets_and_logits(self, query):
+        """The two Linears, once: raw offsets [..., Lq, M, L, P, 2] and attention logits [..., Lq, M, L*P].  The fused
+        kernels read them as they are; the unfused op takes `_weights(logits)` and `_locations(..., offsets, ...)`."""
         lead = query.shape[:-1]
         query = autocast_once(query)      # (feeds two Linears: one cast under autocast instead of two)
         offsets = self.sampling_offsets(query).view(*lead, self.n_heads, self.n_levels, self.n_points, 2)
         logits = self.attention_weights(query).view(*lead, self.n_heads, self.n_levels * self.n_points)
         return offsets, logits
 
-    def _try_fused(self, value, offsets, logits, reference, spatial_shapes, level_start_index):
-        """value [B,S,M,D], offsets [B,Lq,M,L,P,2], logits [B,Lq,M,L*P], reference [B or B/T,Lq,L,2|4]
-        -> sampled [B, Lq, C] or None when the fused kernels do not take this case."""
-        if self.return_samples or not self.fused_prologue:
-            return None
-        if reference.dtype != offsets.dtype and not (offsets.dtype == torch.bfloat16 and value.dtype == torch.bfloat16
-                                                     and reference.dtype == torch.float32):
-            # autocast: the Linears emit 16-bit tensors, the reference points stay fp32 -- rounding positions to 8 mantissa bits
-            # would cost more than half a pixel at 720p.  bf16: the kernels read the offsets / logits as they are beside fp32
-            # reference points (VNX_MSDA_REF_F32, round 6: until then both were promoted here, two casts forward and two
-            # backward per call, 78 MB each on an encoder call); other combinations are promoted.
-            offsets, logits, reference = offsets.float(), logits.float(), reference.float()
-        reference = reference.contiguous()
-        if not msda_ext.fused_supported(value, spatial_shapes, offsets, logits, reference, level_start_index):
-            return None
-        return MSDeformAttnFusedFunction.apply(value.contiguous(), spatial_shapes, level_start_index,
-                                               offsets.contiguous(), logits.contiguous(), reference)
-
-    # -- shared pieces ------------------------------------------------------------------------
-    def _project_value(self, input_flatten, input_padding_mask):
-        # value = self.value_proj(input_flatten); value.masked_fill(input_padding_mask[..., None], 0)  (SeqFormer :94-96):
-        # one GEMM + one in-place pass on the GPU (vnext_amd/ops/fused_ffn.py), the expression itself elsewhere
-        return linear_masked(input_flatten, self.value_proj, input_padding_mask)
-
-    def _offsets_and_weights(self, query):
-        lead = query.shape[:-1]
-        query = autocast_once(query)
-        offsets = self.sampling_offsets(query).view(*lead, self.n_heads, self.n_levels, self.n_points, 2)
-        weights = self.attention_weights(query).view(*lead, self.n_heads, self.n_levels * self.n_points)
-        weights = F.softmax(weights, -1).view(*lead, self.n_heads, self.n_levels, self.n_points)
-        return offsets, weights
+    def _weights(self, logits):
+        return F.softmax(logits, -1).view(*logits.shape[:-1], self.n_levels, self.n_points)
 
     def _locations(self, reference_points, offsets, spatial_shapes):
         """reference_points [..., Lq, L, 2|4] and offsets [..., Lq, M, L, P, 2] broadcast over
@@ -139,6 +126,37 @@ class _MSDeformAttnBase(nn.Module):
         raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(
             reference_points.shape[-1]))
 
+    def _sample_fused(self, value, offsets, logits, reference, spatial_shapes, level_start_index, want_samples):
+        """value [..., S, M, D], offsets [..., Lq, M, L, P, 2], logits [..., Lq, M, L*P], reference [..., Lq, L, 2|4] (with
+        the frame axis, or without it when the frames share the points) -> sampled [..., Lq, C], or None when the caller
+        wants the locations / weights back (`want_samples`) or the fused kernels do not take this case."""
+        if want_samples or not self.fused_prologue:
+            return None
+        lead = value.shape[:-3]
+        value, offsets, logits = value.flatten(0, -4), offsets.flatten(0, -6), logits.flatten(0, -4)
+        reference = reference.flatten(0, -4)
+        if reference.dtype != offsets.dtype and not (offsets.dtype == torch.bfloat16 and value.dtype == torch.bfloat16
+                                                     and reference.dtype == torch.float32):
+            # autocast: the Linears emit 16-bit tensors, the reference points stay fp32 -- rounding positions to 8 mantissa bits
+            # would cost more than half a pixel at 720p.  bf16: the kernels read the offsets / logits as they are beside fp32
+            # reference points (VNX_MSDA_REF_F32, round 6: until then both were promoted here, two casts forward and two
+            # backward per call, 78 MB each on an encoder call); other combinations are promoted.
+            offsets, logits, reference = offsets.float(), logits.float(), reference.float()
+        reference = reference.contiguous()
+        if not msda_ext.fused_supported(value, spatial_shapes, offsets, logits, reference, level_start_index):
+            return None
+        out = MSDeformAttnFusedFunction.apply(value.contiguous(), spatial_shapes, level_start_index,
+                                              offsets.contiguous(), logits.contiguous(), reference)
+        return out.view(*lead, *out.shape[1:])
+
+    def _sample(self, value, locations, weights, spatial_shapes, level_start_index):
+        """The unfused op: value [..., S, M, D], locations [..., Lq, M, L, P, 2], weights [..., Lq, M, L, P] -> [..., Lq, C]"""
+        lead = value.shape[:-3]
+        out = MSDeformAttnFunction.apply(value.flatten(0, -4), spatial_shapes, level_start_index,
+                                         locations.flatten(0, -6).contiguous(), weights.flatten(0, -5).contiguous(),
+                                         self.im2col_step)
+        return out.view(*lead, *out.shape[1:])
+
 
 class MSDeformAttnIDOL(_MSDeformAttnBase):
     """IDOL's module (no frame axis)."""
@@ -149,23 +167,21 @@ class MSDeformAttnIDOL(_MSDeformAttnBase):
 
     def forward(self, query, reference_points, input_flatten, input_spatial_shapes,
                 input_level_start_index, input_padding_mask=None):
-        N, Len_q, _ = query.shape
-        N, Len_in, _ = input_flatten.shape
-        check_flattened_length(input_spatial_shapes, Len_in)
-        value = self._project_value(input_flatten, input_padding_mask)
-        value = value.view(N, Len_in, self.n_heads, self.d_model // self.n_heads)
-        if not self.return_samples and self.fused_prologue:
-            offsets, logits = self._raw_offsets_and_logits(query)
-            output = self._try_fused(value, offsets, logits, reference_points, input_spatial_shapes,
-                                     input_level_start_index)
-            if output is not None:
-                return self._project_output(output, self.output_proj), None, None
-        sampling_offsets, attention_weights = self._offsets_and_weights(query)
-        sampling_locations = self._locations(reference_points, sampling_offsets, input_spatial_shapes)
-        output = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
-                                            sampling_locations.contiguous(), attention_weights,
-                                            self.im2col_step)
-        return self._project_output(output, self.output_proj), sampling_locations, attention_weights
+        value = self._project_value(input_flatten, input_padding_mask, input_spatial_shapes)
+        offsets, logits = self._offsets_and_logits(query)
+        sampled = self._sample_fused(value, offsets, logits, reference_points, input_spatial_shapes,
+                                     input_level_start_index, self.return_samples)
+        locations = weights = None
+        if sampled is None:
+            weights = self._weights(logits)
+            locations = self._locations(reference_points, offsets, input_spatial_shapes)
+            sampled = self._sample(value, locations, weights, input_spatial_shapes, input_level_start_index)
+        return self._project_output(sampled, self.output_proj), locations, weights
+
+    def encode_forward(self, query, reference_points, input_flatten, input_spatial_shapes,
+                       input_level_start_index, input_padding_mask=None):
+        return self.forward(query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
+                            input_padding_mask)[0]
 
 
 class MSDeformAttnSeqFormer(_MSDeformAttnBase):
@@ -188,68 +204,40 @@ class MSDeformAttnSeqFormer(_MSDeformAttnBase):
             return self.decode_forward(query, query_box, reference_points, input_flatten,
                                        input_spatial_shapes, input_level_start_index, input_padding_mask)
 
-    def _apply_folded(self, value, locations, weights, shapes, level_start_index):
-        """value [N,T,S,M,D], locations [N,T,Lq,M,L,P,2], weights [N,T,Lq,M,L,P] -> [N,T,Lq,C]"""
-        N, T = value.shape[:2]
-        out = MSDeformAttnFunction.apply(
-            value.reshape(N * T, *value.shape[2:]), shapes, level_start_index,
-            locations.reshape(N * T, *locations.shape[2:]).contiguous(),
-            weights.reshape(N * T, *weights.shape[2:]).contiguous(), self.im2col_step)
-        return out.view(N, T, out.shape[1], out.shape[2])
-
     def encode_forward(self, query, reference_points, input_flatten, input_spatial_shapes,
                        input_level_start_index, input_padding_mask=None):
-        N, nf, Len_q, _ = query.shape
-        N, nf, Len_in, _ = input_flatten.shape
-        check_flattened_length(input_spatial_shapes, Len_in)
-        value = self._project_value(input_flatten, input_padding_mask)
-        value = value.view(N, nf, Len_in, self.n_heads, self.d_model // self.n_heads)
+        value = self._project_value(input_flatten, input_padding_mask, input_spatial_shapes)
         if reference_points.shape[-1] != 2:
             raise ValueError('Last dim of reference_points must be 2 or 4, but get {} instead.'.format(
                 reference_points.shape[-1]))
-        if self.fused_prologue:      # encode_forward never returned locations / weights
-            offsets, logits = self._raw_offsets_and_logits(query)
-            keep, self.return_samples = self.return_samples, False
-            sampled = self._try_fused(value.reshape(N * nf, *value.shape[2:]), offsets.reshape(N * nf, *offsets.shape[2:]),
-                                      logits.reshape(N * nf, *logits.shape[2:]), reference_points,
-                                      input_spatial_shapes, input_level_start_index)
-            self.return_samples = keep
-            if sampled is not None:
-                return self._project_output(sampled.view(N, nf, Len_q, -1), self.output_proj)
-        sampling_offsets, attention_weights = self._offsets_and_weights(query)  # [N,nf,Lq,M,L,P(,2)]
-        # the encoder's reference points are shared by the frames: [N, Lq, L, 2] (SeqFormer :107-112)
-        locations = self._locations(reference_points[:, None], sampling_offsets, input_spatial_shapes)
-        sampled = self._apply_folded(value, locations, attention_weights, input_spatial_shapes,
-                                     input_level_start_index)
+        offsets, logits = self._offsets_and_logits(query)  # [N,nf,Lq,M,L,P,2], [N,nf,Lq,M,L*P]
+        # (never returned locations / weights: the fused kernels whatever `return_samples` says)
+        sampled = self._sample_fused(value, offsets, logits, reference_points, input_spatial_shapes,
+                                     input_level_start_index, want_samples=False)
+        if sampled is None:
+            weights = self._weights(logits)
+            # the encoder's reference points are shared by the frames: [N, Lq, L, 2] (SeqFormer :107-112)
+            locations = self._locations(reference_points[:, None], offsets, input_spatial_shapes)
+            sampled = self._sample(value, locations, weights, input_spatial_shapes, input_level_start_index)
         return self._project_output(sampled, self.output_proj)
 
     def decode_forward(self, query, query_box, reference_points, input_flatten, input_spatial_shapes,
                        input_level_start_index, input_padding_mask=None):
-        N, nf, Len_in, _ = input_flatten.shape
-        check_flattened_length(input_spatial_shapes, Len_in)
-        value = self._project_value(input_flatten, input_padding_mask)
-        value = value.view(N, nf, Len_in, self.n_heads, self.d_model // self.n_heads)
-        if query_box.dim() == 4 and not self.return_samples and self.fused_prologue:
-            offsets, logits = self._raw_offsets_and_logits(query_box)          # per-frame box queries
-            sampled = self._try_fused(value.reshape(N * nf, *value.shape[2:]), offsets.reshape(N * nf, *offsets.shape[2:]),
-                                      logits.reshape(N * nf, *logits.shape[2:]),
-                                      reference_points.reshape(N * nf, *reference_points.shape[2:]),
-                                      input_spatial_shapes, input_level_start_index)
-            if sampled is not None:
-                sampled = sampled.view(N, nf, sampled.shape[1], -1)
-                return self._project_output(sampled, self.output_proj), self._project_output(sampled, self.output_proj_box), None, None
-        sampling_offsets, attention_weights = self._offsets_and_weights(query_box)
-        if query_box.dim() == 3:
-            # first decoder layer: one set of offsets / weights per query, shared by the frames
-            # (SeqFormer :128-171); reference_points are per frame [N, nf, Lq, L, 2|4]
-            locations = self._locations(reference_points, sampling_offsets[:, None], input_spatial_shapes)
-            weights = attention_weights[:, None].expand(N, nf, *attention_weights.shape[1:])
-        else:
-            assert query_box.dim() == 4  # [N, nf, Lq, C]: per-frame box queries (SeqFormer :172-217)
-            locations = self._locations(reference_points, sampling_offsets, input_spatial_shapes)
-            weights = attention_weights
-        sampled = self._apply_folded(value, locations, weights, input_spatial_shapes, input_level_start_index)
-        output = self._project_output(sampled, self.output_proj)
-        output_box = self._project_output(sampled, self.output_proj_box)
-        # the reference returns the LAST frame's locations (the loop variable, :171,217)
-        return output, output_box, locations[:, -1], attention_weights
+        value = self._project_value(input_flatten, input_padding_mask, input_spatial_shapes)
+        offsets, logits = self._offsets_and_logits(query_box)
+        # first decoder layer, query_box [N, Lq, C]: one set of offsets / weights per query, shared by the frames
+        # (SeqFormer :128-171), which the fused kernels do not take; later [N, nf, Lq, C]: per-frame box queries (:172-217).
+        # reference_points are per frame either way [N, nf, Lq, L, 2|4]
+        shared = query_box.dim() == 3
+        assert shared or query_box.dim() == 4
+        sampled = None if shared else self._sample_fused(value, offsets, logits, reference_points, input_spatial_shapes,
+                                                         input_level_start_index, self.return_samples)
+        locations = weights = None
+        if sampled is None:
+            weights = self._weights(logits)
+            locations = self._locations(reference_points, offsets[:, None] if shared else offsets, input_spatial_shapes)
+            per_frame = weights[:, None].expand(*value.shape[:2], *weights.shape[1:]) if shared else weights
+            sampled = self._sample(value, locations, per_frame, input_spatial_shapes, input_level_start_index)
+            locations = locations[:, -1]      # the reference returns the LAST frame's locations (the loop variable, :171,217)
+        return (self._project_output(sampled, self.output_proj), self._project_output(sampled, self.output_proj_box),
+                locations, weights)

@@ -34,7 +34,7 @@ import torch
 from torch import nn
 
 ENABLED = os.environ.get("VNX_SHADOW_WEIGHTS", "1") != "0"
-# biases that reach a GEMM epilogue through a plain `linear(x)` call (ops/modules/ms_deform_attn.py:_raw_offsets_and_logits)
+# biases that reach a GEMM epilogue through a plain `linear(x)` call (ops/modules/ms_deform_attn.py:_offsets_and_logits)
 _PLAIN_BIAS_OWNERS = ("sampling_offsets", "attention_weights")
 
 
