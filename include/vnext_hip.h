@@ -516,6 +516,32 @@ int vnx_mask_rle_write(int mode, const void* input, int masks, int height, int w
                        long long arena_bytes, void* hip_stream);
 
 /*
+ * The thresholded result masks themselves, at the output size, from the mask logits in one launch (mask_dense.hip).
+ * ADDITIVE: this symbol was added without a change to any existing signature, so VNX_ABI_VERSION stays 17 and a
+ * binding written against the earlier ABI 17 keeps working; a binding that needs it looks the symbol up.
+ *
+ * logits fp32 [masks][height][width] (4-byte aligned).  Output pixel (y, x) of mask m is the bit VNX_MASK_RLE_LOGITS
+ * encodes, from the same device code: yi = min(floor(y * (image_height / out_height as fp32)), image_height - 1), xi
+ * likewise, v = ATen's align_corners=False bilinear value of the stride-times upsampled map at (yi, xi), bit = v > 0 --
+ * sigmoid(v) > 0.5 apart from |v| within fp32 rounding of 0.  The two entry points agree on every pixel.
+ * format VNX_MASK_DENSE_U8:   out uint8 [masks][out_height][out_width], 0 or 1; any byte alignment.
+ * format VNX_MASK_DENSE_BITS: out [masks][out_height][pitch] bytes, pitch = 8 * ceil(out_width / 64); pixel x is bit
+ *   x & 7 of byte x >> 3 of its row (numpy bitorder="little"), padding bits and bytes are zero; out 8-byte aligned.
+ * out_bytes: the size of out; every byte of the masks * out_height rows is written, no byte outside them.
+ * Before any launch: an unknown format, masks < 0, non-positive sizes, out_bytes < 0 or smaller than the rows, a crop
+ * larger than the upsampled map, null or misaligned pointers (VNX_ERR_INVALID_ARGUMENT); height * width >= 2^31
+ * (VNX_ERR_UNSUPPORTED).  masks == 0 is a no-op.  The output may exceed 2^31 bytes and masks * out_height any grid
+ * dimension.  No atomics: the output is a function of the input alone.  No workspace, no allocation, no
+ * synchronisation: capturable in a hipGraph.
+ */
+enum {
+  VNX_MASK_DENSE_U8 = 0,
+  VNX_MASK_DENSE_BITS = 1
+};
+int vnx_mask_dense(int format, const void* logits, int masks, int height, int width, int stride, int image_height,
+                   int image_width, int out_height, int out_width, void* out, long long out_bytes, void* hip_stream);
+
+/*
  * Linear sum assignment on the device: SeqFormer's Hungarian matching without a host round trip (lsap.hip).
  * ADDITIVE: these two symbols were added without a change to any existing signature, so VNX_ABI_VERSION stays 17 and a
  * binding written against the earlier ABI 17 keeps working; a binding that needs them looks the symbols up.

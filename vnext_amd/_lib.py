@@ -21,6 +21,7 @@ ABI_VERSION = 17
 MSDA_LEVELS_PACKED = 1
 MSDA_REF_F32 = 0x100       # or-ed into ref_dim of vnx_msda_fused_*: fp32 reference points beside 16-bit offsets / logits
 MASK_RLE_LOGITS, MASK_RLE_BINARY = 0, 1   # vnx_mask_rle_*: input modes
+MASK_DENSE_U8, MASK_DENSE_BITS = 0, 1     # vnx_mask_dense: output formats
 MSDA_FORK = 2              # vnx_msda_backward: grad_value kernel on the library's side stream (include/vnext_hip.h)
 # limits of include/vnext_hip.h, by their names there
 MASK_LOSS_MAX_CLIPS, MASK_LOSS_PIECE = 16, 4096            # VNX_MASK_LOSS_MAX_CLIPS, VNX_MASK_LOSS_PIECE
@@ -83,6 +84,7 @@ SIGNATURES = {
     "vnx_window_attention_backward": (_i, [_i] + [_vp] * 10 + [_sz] + [_i] * 8 + [ctypes.c_float, _vp]),
     "vnx_mask_rle_measure": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp]),
     "vnx_mask_rle_write": (_i, [_i, _vp] + [_i] * 8 + [_vp, _vp, _ll, _vp]),
+    "vnx_mask_dense": (_i, [_i, _vp] + [_i] * 8 + [_vp, _ll, _vp]),
     "vnx_seqformer_match": (_i, [_vp] * 5 + [_i] * 7 + [ctypes.c_float] * 3 + [_vp] * 4),
     "vnx_lsap_solve": (_i, [_vp, _i, _i, _i, _ll, _ll, _ll, _i, _vp, _vp, _vp]),
     "vnx_mask_loss_forward": (_i, [_vp] * 3 + [_i] * 5 + [ctypes.c_float] * 2 + [_vp, _sz] + [_vp] * 4),

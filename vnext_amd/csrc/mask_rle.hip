@@ -18,7 +18,7 @@
 // The measure launch writes each mask's string length; the write launch repeats the walk and stores the characters at
 // the caller's offsets.  Nothing at full resolution is stored: no upsampled map, no bool mask.  No atomics: the output
 // is a function of the input alone.  Every character store is bounds-checked against the arena.
-#include "vnx_common.h"
+#include "mask_sample.h"
 
 namespace vnx {
 
@@ -29,31 +29,11 @@ constexpr int kRleWords = kRleChunk / 64;
 
 struct RleArgs {
   const void* in;
-  int h, w;          // logit map (logits mode)
-  int ih, iw;        // image size on the upsampled grid: the crop
+  MaskSample s;      // logits mode: the map, the crop and the scales (mask_sample.h)
   int oh, ow;        // output mask
-  float ry, rx;      // bilinear scales h / (h s), w / (w s) (ATen area_pixel_compute_scale)
-  float ny, nx;      // nearest scales ih / oh, iw / ow (ATen compute_scales_value)
   int n;             // oh * ow
   int dq, dr;        // 256 / oh, 256 % oh: the walk's step in (column, row)
 };
-
-// ATen upsample_bilinear2d (align_corners=False) of the [h, w] map to [h s, w s], read at (yi, xi) of that grid
-__device__ __forceinline__ bool rle_logit_bit(const float* __restrict__ map, const RleArgs& a, int y, int x) {
-  const int yi = min(int(floorf(float(y) * a.ny)), a.ih - 1);        // ATen nearest_neighbor_compute_source_index
-  const int xi = min(int(floorf(float(x) * a.nx)), a.iw - 1);
-  float sy = a.ry * (float(yi) + 0.5f) - 0.5f;                        // area_pixel_compute_source_index
-  float sx = a.rx * (float(xi) + 0.5f) - 0.5f;
-  sy = sy < 0.f ? 0.f : sy;
-  sx = sx < 0.f ? 0.f : sx;
-  const int h1 = int(sy), w1 = int(sx);
-  const int h1p = h1 < a.h - 1 ? a.w : 0, w1p = w1 < a.w - 1 ? 1 : 0;
-  const float h1l = sy - float(h1), h0l = 1.f - h1l;
-  const float w1l = sx - float(w1), w0l = 1.f - w1l;
-  const float* p = map + h1 * a.w + w1;
-  const float v = h0l * (w0l * p[0] + w1l * p[w1p]) + h1l * (w0l * p[h1p] + w1l * p[h1p + w1p]);
-  return v > 0.f;
-}
 
 // exclusive scan of one int per thread over the workgroup (4 waves); one barrier
 __device__ __forceinline__ int rle_block_scan(int v, int* s, int* total) {
@@ -113,7 +93,7 @@ __global__ void __launch_bounds__(kRleThreads) mask_rle_kernel(RleArgs a, int64_
   __shared__ int s_scan[2][kRleThreads / 64];
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int64_t m = blockIdx.x;
-  const float* map = LOGITS ? (const float*)a.in + m * a.h * a.w : nullptr;
+  const float* map = LOGITS ? (const float*)a.in + m * a.s.h * a.s.w : nullptr;
   const uint8_t* bin = LOGITS ? nullptr : (const uint8_t*)a.in + m * a.n;
   int y = t % a.oh, x = t / a.oh;            // this thread's pixel of the current step
   uint32_t last_bit = 0;
@@ -124,7 +104,7 @@ __global__ void __launch_bounds__(kRleThreads) mask_rle_kernel(RleArgs a, int64_
     for (int k = 0; k < kRleSteps; ++k) {
       const int64_t p = base + k * kRleThreads + t;
       bool bit = false;
-      if (p < a.n) bit = LOGITS ? rle_logit_bit(map, a, y, x) : bin[int64_t(y) * a.ow + x] != 0;
+      if (p < a.n) bit = LOGITS ? mask_logit_bit(map, a.s, y, x) : bin[int64_t(y) * a.ow + x] != 0;
       const uint64_t word = __ballot(bit);
       if (lane == 0) s_words[k * (kRleThreads / 64) + wv] = word;
       y += a.dr;
@@ -183,17 +163,9 @@ static int mask_rle_launch(bool write, int mode, const void* input, int masks, i
                            const int64_t* offsets, void* arena, int64_t arena_bytes, hipStream_t stream) {
   RleArgs a;
   a.in = input;
-  a.h = height; a.w = width;
-  a.ih = image_height; a.iw = image_width;
   a.oh = out_height; a.ow = out_width;
-  if (mode == VNX_MASK_RLE_LOGITS) {
-    a.ry = float(height) / float(int64_t(height) * stride);
-    a.rx = float(width) / float(int64_t(width) * stride);
-    a.ny = float(image_height) / float(out_height);
-    a.nx = float(image_width) / float(out_width);
-  } else {
-    a.ry = a.rx = a.ny = a.nx = 0.f;
-  }
+  a.s = mode == VNX_MASK_RLE_LOGITS ? mask_sample(height, width, stride, image_height, image_width, out_height, out_width)
+                                    : MaskSample{};
   a.n = out_height * out_width;
   a.dq = kRleThreads / out_height;
   a.dr = kRleThreads % out_height;

@@ -43,6 +43,7 @@ from .seqformer import MLP, DeformableDETR, MaskHeadSmallConv, scale_tensor
 from .seqformer_transformer import inverse_sigmoid
 from .tracker import DeviceTracker, IDOL_Tracker
 from ..ops.det_select import DetSelectUnsupported, class_aware_nms, select_detections, select_detections_host  # noqa: F401 (class_aware_nms: the host NMS, re-exported)
+from ..ops.mask_dense import masks_from_logits
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import rle_encode, ytvis_records
 
@@ -115,6 +116,10 @@ class IDOL(nn.Module):
         # training mode, clips staged by `data.clip_mapper.stage_clip`: crop, resize and flip of the source frames AND of their
         # run-length ground truth on the device (vnext_amd/ops/augment.py; opt-in: train.enable_device_augment)
         self.device_augment = False
+        # eval mode, `model(inputs)`: the full-resolution masks of the tracks (and of COCO-pretrain detections) from the logits
+        # by one kernel (vnext_amd/ops/mask_dense.py) instead of the bilinear -> sigmoid -> nearest chain (opt-in:
+        # train.enable_device_masks); CUDA tensors only
+        self.device_masks = False
         self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 480)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
@@ -370,12 +375,18 @@ class IDOL(nn.Module):
         the named queries (None: no masks), the images' sizes (h, w) before padding and the sizes to report at.
         -> per image {"instances": {"image_size", "pred_boxes" [n, 4], "scores", "pred_classes", "pred_masks" uint8
         [n, height, width]}}: plain tensors under the reference's field names.  Selection: ops/det_select.py (the
-        kernel for CUDA tensors; the host expression for a shape it refuses).  Masks: bilinear x4, sigmoid > 0.5, crop to the image, nearest to the output size."""
+        kernel for CUDA tensors; the host expression for a shape it refuses).  Masks: bilinear x4, sigmoid > 0.5, crop to the image, nearest to the output size.
+        `device_masks` (CUDA tensors): the masks come from ops/mask_dense.py, one call per distinct (image size, output
+        size) as in `coco_records`; no full-resolution float is formed."""
         results = []
-        for b, r in enumerate(self._coco_select(logits, boxes, masks_of, image_sizes, out_sizes)):
+        selected = self._coco_select(logits, boxes, masks_of, image_sizes, out_sizes)
+        dense = self._coco_device_masks(selected, image_sizes, out_sizes) if self.device_masks and logits.is_cuda else {}
+        for b, r in enumerate(selected):
             inst = {"image_size": tuple(out_sizes[b]), "pred_boxes": r["pred_boxes"], "scores": r["scores"],
                     "pred_classes": r["pred_classes"]}
-            if r["mask_logits"] is not None:
+            if b in dense:
+                inst["pred_masks"] = dense[b]
+            elif r["mask_logits"] is not None:
                 m = r["mask_logits"][:, None].float()
                 h, w = m.shape[-2:]
                 ih, iw = image_sizes[b]
@@ -387,6 +398,24 @@ class IDOL(nn.Module):
                 inst["pred_masks"] = m.to(torch.uint8)
             results.append({"instances": inst})
         return results
+
+    @staticmethod
+    def _coco_device_masks(selected, image_sizes, out_sizes):
+        """`_coco_select`'s rows -> {image: uint8 [n, height, width] on the device}, the masks of the stride-4 logits by one
+        kernel call per distinct (image size, output size); an image without detections keeps the host expression's empty."""
+        groups = {}
+        for b, r in enumerate(selected):
+            if r["mask_logits"] is not None and r["mask_logits"].shape[0]:
+                groups.setdefault((tuple(image_sizes[b]), tuple(out_sizes[b])), []).append(b)
+        dense = {}
+        for (isz, osz), members in groups.items():
+            parts = [selected[b]["mask_logits"] for b in members]
+            masks = masks_from_logits(parts[0] if len(parts) == 1 else torch.cat(parts), 4, isz, osz).view(torch.uint8)
+            start = 0
+            for b, p in zip(members, parts):
+                dense[b] = masks[start:start + p.shape[0]]
+                start += p.shape[0]
+        return dense
 
     @torch.no_grad()
     def coco_inference(self, batched_inputs):
@@ -495,12 +524,26 @@ class IDOL(nn.Module):
         return self.associate(per_frame, tracker, (oh, ow), (ih, iw), host_factory=lambda: IDOL_Tracker(**args), rle=rle)
 
     @staticmethod
-    def _track_masks(tracks, n_frames, image_size, ori_size, rle=False):
+    def _track_masks(tracks, n_frames, image_size, ori_size, rle=False, device_masks=False):
         """The final mask step of `associate`: each track's remembered stride-4 logits [1, H/4, W/4] (None where the
         track is absent) -> per track, a list over frames of bool masks of `ori_size` on the host (None where absent) or,
         with `rle`, of their COCO RLE dicts (the empty mask's RLE where absent, as the YTVIS writer puts it).  The RLE
-        form encodes the seen frames of ALL tracks in one device call; no full-resolution mask is formed."""
+        form encodes the seen frames of ALL tracks in one device call; no full-resolution mask is formed.
+        `device_masks` (the model's switch; CUDA logits, `rle=False`): the bool masks of the seen frames of ALL tracks come
+        from one kernel call (vnext_amd/ops/mask_dense.py) and one copy to the host, instead of one chain and one copy
+        per track; a track's masks are rows of that one host tensor."""
         seen = [[i for i, m in enumerate(v["masks"]) if m is not None] for v in tracks]
+        logits = [v["masks"][i][0] for v, idx in zip(tracks, seen) for i in idx] if device_masks and not rle else []
+        if logits and logits[0].is_cuda:
+            m = torch.stack(logits)                                                   # [sum k, H/4, W/4]
+            rows = iter(masks_from_logits(m, 4, image_size, ori_size).cpu())
+            masks_out = []
+            for idx in seen:
+                per = [None] * n_frames
+                for i in idx:
+                    per[i] = next(rows)
+                masks_out.append(per)
+            return masks_out
         if rle:
             out = []
             if tracks:
@@ -583,7 +626,7 @@ class IDOL(nn.Module):
         for v in video.values():
             s = torch.stack([x for x in v["scores"] if x is not None])
             cls.append(s.mean(0) if self.temporal_score_type == "mean" else s.max(0)[0])
-        masks_out = self._track_masks(list(video.values()), n_frames, image_size, ori_size, rle)
+        masks_out = self._track_masks(list(video.values()), n_frames, image_size, ori_size, rle, self.device_masks)
         if not cls:
             return {"image_size": ori_size, "pred_scores": [], "pred_labels": [], "pred_masks": []}
         cls = torch.stack(cls)

@@ -28,6 +28,7 @@ from torch import nn
 
 from ..heads import dynamic_mask_head, dynamic_mask_with_coords
 from ..ops.ingest import sine_position  # noqa: F401  (its home; importable from here by name, as the three below)
+from ..ops.mask_dense import masks_from_logits
 from ..ops.mask_rle import encode_logits
 from ..utils.ytvis_json import ytvis_records
 from .criterion import HungarianMatcher, SetCriterion, box_xyxy_to_cxcywh, flat_pairs, layer_counts
@@ -162,6 +163,9 @@ class SeqFormer(nn.Module):
         # training mode, clips staged by `data.clip_mapper.stage_clip`: crop, resize and flip of the source frames AND of their
         # run-length ground truth on the device (vnext_amd/ops/augment.py; opt-in: train.enable_device_augment)
         self.device_augment = False
+        # eval mode, `model(inputs)`: the full-resolution bool masks from the logits by one kernel (vnext_amd/ops/mask_dense.py)
+        # instead of the bilinear -> sigmoid -> nearest chain (opt-in: train.enable_device_masks); CUDA tensors only
+        self.device_masks = False
         self._pixel_stats, self._test_size, self._graphs, self._train_trunks = front_end_state(cfg, 360)
         self.register_buffer("pixel_mean", torch.tensor(cfg.MODEL.PIXEL_MEAN).view(3, 1, 1), persistent=False)
         self.register_buffer("pixel_std", torch.tensor(cfg.MODEL.PIXEL_STD).view(3, 1, 1), persistent=False)
@@ -383,7 +387,10 @@ class SeqFormer(nn.Module):
         """class probabilities [n, K] + mask logits [n, T, H/4, W/4] -> the output dict
         (`whole_video_inference` :351-410 == `clip_matching_postprocess` :328-349).  `rle=True`: "pred_masks" holds
         each reported pair's T COCO RLE dicts instead of bool masks; every query is encoded once, on the device
-        (vnext_amd/ops/mask_rle.py), and a query reported under several classes shares its strings."""
+        (vnext_amd/ops/mask_rle.py), and a query reported under several classes shares its strings.
+        `device_masks` (CUDA tensors, `rle=False`): the bool masks [T, oh, ow] of the distinct reported queries come from
+        one kernel call (vnext_amd/ops/mask_dense.py) and cross to the host in one copy; the pairs of one query, reported
+        under several classes, are then views of the SAME memory (without the switch each pair owns a copy)."""
         if prob.shape[0] == 0:
             return {"image_size": out_size, "pred_scores": [], "pred_labels": [], "pred_masks": []}
         if self.multi_cls:
@@ -392,14 +399,18 @@ class SeqFormer(nn.Module):
         else:
             score, label = prob.max(-1)
             who = None
-        if rle:
+        if rle or (self.device_masks and mask_logits.is_cuda):
             n, T, h, w = mask_logits.shape
             rows = list(range(n)) if who is None else who.tolist()
             used = sorted(set(rows))
-            strings = encode_logits(mask_logits[used].reshape(len(used) * T, h, w), self.mask_stride, image_size,
-                                    out_size)
             at = {q: j for j, q in enumerate(used)}
-            masks = [strings[at[q] * T:(at[q] + 1) * T] for q in rows]
+            picked = mask_logits[used].reshape(len(used) * T, h, w)
+            if rle:
+                strings = encode_logits(picked, self.mask_stride, image_size, out_size)
+                masks = [strings[at[q] * T:(at[q] + 1) * T] for q in rows]
+            else:
+                host = masks_from_logits(picked, self.mask_stride, image_size, out_size).cpu()
+                masks = [host[at[q] * T:(at[q] + 1) * T] for q in rows]
         else:
             h, w = mask_logits.shape[-2:]
             masks = F.interpolate(mask_logits, size=(h * self.mask_stride, w * self.mask_stride), mode="bilinear",

@@ -20,10 +20,10 @@ from __future__ import annotations
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from .. import _lib
 from ..utils.ytvis_json import rle_encode
+from .mask_dense import host_masks
 
 
 def _records(lengths_end, arena, oh, ow):
@@ -73,10 +73,7 @@ def encode_logits(logits, stride, image_size, out_size):
     if not logits.is_cuda:
         if M == 0:
             return []
-        m = F.interpolate(logits.float()[:, None], size=(h * stride, w * stride), mode="bilinear",
-                          align_corners=False).sigmoid()
-        m = (F.interpolate(m[:, :, :ih, :iw], size=(oh, ow), mode="nearest") > 0.5)[:, 0]
-        return [rle_encode(x) for x in m.numpy()]
+        return [rle_encode(x) for x in host_masks(logits, stride, (ih, iw), (oh, ow)).numpy()]
     return _encode_device(_lib.MASK_RLE_LOGITS, logits.float().contiguous(), M, h, w, stride, ih, iw, oh, ow)
 
 

@@ -365,6 +365,20 @@ def enable_device_resize(model, on: bool = True) -> None:
     model.device_resize = bool(on)
 
 
+def enable_device_masks(model, on: bool = True) -> None:
+    """Opt in to dense result masks from the logits in one device pass (`SeqFormer.device_masks` / `IDOL.device_masks`,
+    vnext_amd/ops/mask_dense.py): in eval mode the full-resolution masks `model(inputs)` returns -- SeqFormer's reported
+    pairs, IDOL's tracks, and the `pred_masks` of IDOL's COCO-pretrain branch -- come from one kernel call per video (per
+    distinct size pair for COCO) instead of the bilinear -> sigmoid -> crop -> nearest chain and its two full-resolution fp32
+    tensors; the video branches then make one device-to-host copy.  Types, shapes and devices of the outputs are unchanged;
+    the masks are the chain's wherever no pixel's bilinear value is within fp32 rounding of 0 (the device bit is value > 0,
+    as in `ytvis_results`).  SeqFormer pairs of one query share memory.  CPU tensors and the RLE routes are unchanged.
+    Raises for a model without the switch."""
+    if not hasattr(model, "device_masks"):
+        raise ValueError("enable_device_masks: %s has no device_masks switch" % type(model).__name__)
+    model.device_masks = bool(on)
+
+
 def enable_device_augment(model, on: bool = True) -> None:
     """Opt in to the training-time augmentation on the device (`SeqFormer.device_augment` / `IDOL.device_augment`,
     vnext_amd/ops/augment.py): in training mode, clips that `vnext_amd.data.clip_mapper.stage_clip` made -- SOURCE frames as
